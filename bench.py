@@ -4,6 +4,12 @@
     python bench.py --gpus N --steps K --warmup W          (N > 1: one rank per GPU -- under torch.distributed.run as the
                                                             driver starts it, or started by bench.py itself when WORLD_SIZE is unset;
                                                             every rank checks WORLD_SIZE == N and exits non-zero otherwise)
+    python bench.py ... --dump-outputs DIR                 (also writes the last timed step's posterior mean as DIR/mean.npy)
+    python bench.py ... --full                             (the headline, then every other measurement of the record below)
+
+A plain run sets up, warms up, times K steps and prints the headline keys (metric, value, unit, ms_per_step, dtype, config,
+...).  Everything below beyond the headline -- the extra keys, `roofline` and the per-kernel timers, `cpu_baseline` -- is
+measured with --full only.
 
 Workload (BASELINE.json metric "GP-fits/sec + CG-iter/sec, N=1e6 d=2 SE kernel"; inputs as in the
 reference's timing driver test_timing_profiling.py:18-44): x ~ U[-1,1]^2 (float64, seeded),
@@ -349,6 +355,20 @@ def north_star(dev, rank, world, distributed, barrier):
             "survey_bytes": survey_bytes, "actual_bytes": actual_bytes}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, mean, rank, world):
+    """What a caller of the timed step receives: the posterior mean at this rank's training points, float64, as
+    out_dir/mean.npy (mean_rank<r>.npy with several ranks).  Beyond 64 MB for the whole job a fixed stride sample is written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_MAX_BYTES // (8 * world)
+    stride = -(-mean.numel() // cap)
+    name = "mean" if world == 1 else f"mean_rank{rank}"
+    np.save(os.path.join(out_dir, name + ".npy"), mean.detach()[::stride].to(torch.float64).cpu().numpy())
+
+
 def launch_ranks(n, argv):
     """One child process per GPU via torch.distributed.run on 127.0.0.1 (a free port), started BEFORE anything in this process
     touches the GPU; returns the launcher's exit code."""
@@ -372,14 +392,21 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=WARMUP_DEFAULT)
     ap.add_argument("--global-n", type=int, default=N_PER_GPU, help="points of the GLOBAL problem, sharded over the ranks")
-    ap.add_argument("--no-extras", action="store_true", help="skip the weak-scaling and north-star legs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the posterior mean of the last timed step as DIR/mean.npy (float64)")
+    ap.add_argument("--full", action="store_true", help="after the headline, every other measurement of the record: fit-only time, "
+                                                         "CG rates, gradient step, roofline and per-kernel timers, other configs, "
+                                                         "train loop, weak scaling, north star, scaling model, CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the weak-scaling, north-star, mid-grid CG, "
+                                                              "model-cost, other-config and train-loop legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--check-launch", action="store_true", help="print this rank's place in the job and exit (no GPU needed): "
                                                                 "checks the launcher and the WORLD_SIZE == --gpus rule")
     ap.add_argument("--main-only", action="store_true",
                     help="timed steps only (no CG-rate / gradient / CPU-baseline extras): for rocprofv3 --pmc passes, so "
                          "that every profiled launch belongs to the fit step")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: this process has not touched the GPU yet -- start the N ranks as children through
@@ -446,14 +473,60 @@ def main():
         if warm_done % 64 == 0:
             torch.cuda.synchronize(dev)             # the time floor is wall time of EXECUTED steps, not of enqueued ones
     barrier()
-    # inside the timed region only the roofline's kernel (the fused spread) carries HIP events: every timed launch puts two
-    # event records into the stream, and with all timers on they cost the 0.3-ms step ~10 % (measured: 0.331 vs 0.291 ms)
-    kernel_timing(True, only="spread")
+    # --full: inside the timed region only the roofline's kernel (the fused spread) carries HIP events: every timed launch puts
+    # two event records into the stream, and with all timers on they cost the 0.3-ms step ~10 % (measured: 0.331 vs 0.291 ms)
+    if args.full:
+        kernel_timing(True, only="spread")
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        mean = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, mean, rank, world)
+    if distributed:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    ms_per_step = 1e3 * elapsed / args.steps
+    fits_per_s = args.steps / elapsed
+    mean_iters = model.last_fit_stats["mean_cg_iters"]
+    mtot = model.last_fit_stats["mtot"]
+
+    def finish(rec):
+        if rank == 0:
+            print(json.dumps(rec), file=record_out, flush=True)
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if args.main_only:
+        finish({"metric": "GP-fits/sec (main-only profiling run)", "value": fits_per_s,
+                "ms_per_step": ms_per_step, "steps": args.steps, "warmup": warm_done, "n_gpus": world})
+        return
+    headline = {
+        "metric": "GP-fits/sec (fit + posterior mean at the N training points), N=1e6 d=2 SE kernel",
+        "value": fits_per_s,
+        "unit": "GP fits/s of the global N=1e6 problem (whole job; the points are sharded over the GPUs)",
+        "n_gpus": world, "rccl_ranks": world if distributed else 0, "steps": args.steps, "warmup": warm_done,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True, "scaling": "strong",
+        "scaling_note": "strong scaling of the metric's global N = 1e6: only the two N-scale launches shard; the mean solve (one "
+                        "M-sized system, ~70 % of the one-GPU step) is replicated, so the curve is capped near 1.2 x at 8 GPUs by "
+                        "construction (scaling_model, from the one-GPU timers); weak_scaling and north_star_n1e7 carry the cases "
+                        "that gain",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "2D squared-exponential l=0.2 var=2 sigma2=0.2, eps=1e-4, global N=1e6 synthetic "
+                               "(BASELINE configs[1] at the metric's N=1e6), points sharded over the GPUs",
+                   "n_per_gpu": N, "global_n": NG, "d": DIM, "mtot": mtot, "M": mtot ** DIM,
+                   "nufft_tol": NUFFT_TOL, "cg_tol": CG_TOL, "mean_cg_iters": mean_iters,
+                   "parallelism": f"points sharded over {world} GPU(s), CG replicated"},
+        "points_per_s": NG * fits_per_s,
+    }
+    if not args.full:
+        finish(headline)
+        return
+
     spread_ms, spread_n = kernel_timing_read("spread")
     kernel_timing(False)
     # gather and solve durations for the extra blocks: a second, untimed pass with all timers on
@@ -464,23 +537,6 @@ def main():
     interp_ms, interp_n = kernel_timing_read("interp")
     cgs_ms, cgs_n = kernel_timing_read("cg_solve")
     kernel_timing(False)
-    if distributed:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-    ms_per_step = 1e3 * elapsed / args.steps
-    fits_per_s = args.steps / elapsed
-    mean_iters = model.last_fit_stats["mean_cg_iters"]
-    mtot = model.last_fit_stats["mtot"]
-
-    if args.main_only:
-        if rank == 0:
-            print(json.dumps({"metric": "GP-fits/sec (main-only profiling run)", "value": fits_per_s,
-                              "ms_per_step": ms_per_step, "steps": args.steps, "warmup": warm_done, "n_gpus": world}), file=record_out, flush=True)
-        if distributed:
-            dist.barrier()
-            dist.destroy_process_group()
-        return
 
     # fit-only time and CG iteration rate (forced 200 iterations, no early stop), untimed region
     barrier()
@@ -587,6 +643,7 @@ def main():
             del mw, xw, yw
         star = north_star(dev, rank, world, distributed, barrier)
 
+    rec = None
     if rank == 0:
         m = (mtot - 1) // 2
         out_bytes = 16 * (mtot ** DIM + (4 * m + 1) ** DIM)
@@ -606,28 +663,12 @@ def main():
         for _ in range(DIM):
             ftot *= 1 << (4 * m + 1 - 1).bit_length()
         cg_bytes = 16 * (ftot + 8 * mtot ** DIM) * mean_iters        # fused-ideal bytes per iteration
-        rec = {
-            "metric": "GP-fits/sec (fit + posterior mean at the N training points), N=1e6 d=2 SE kernel",
-            "value": fits_per_s,
-            "unit": "GP fits/s of the global N=1e6 problem (whole job; the points are sharded over the GPUs)",
-            "n_gpus": world, "rccl_ranks": world if distributed else 0, "steps": args.steps, "warmup": warm_done,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "strong",
-            "scaling_note": "strong scaling of the metric's global N = 1e6: only the two N-scale launches shard; the mean solve (one "
-                            "M-sized system, ~70 % of the one-GPU step) is replicated, so the curve is capped near 1.2 x at 8 GPUs by "
-                            "construction (scaling_model, from the one-GPU timers); weak_scaling and north_star_n1e7 carry the cases "
-                            "that gain",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "2D squared-exponential l=0.2 var=2 sigma2=0.2, eps=1e-4, global N=1e6 synthetic "
-                                   "(BASELINE configs[1] at the metric's N=1e6), points sharded over the GPUs",
-                       "n_per_gpu": N, "global_n": NG, "d": DIM, "mtot": mtot, "M": mtot ** DIM,
-                       "nufft_tol": NUFFT_TOL, "cg_tol": CG_TOL, "mean_cg_iters": mean_iters,
-                       "parallelism": f"points sharded over {world} GPU(s), CG replicated"},
+        rec = dict(headline)
+        rec.update({
             "fit_only_ms": fit_only_ms,
             "cg_iter_per_s": cg_iter_per_s,
             "cg_us_per_iter": 1e6 / cg_iter_per_s,
             "cg_rhs_iter_per_s_batch64": cg_rhs_iter_per_s,
-            "points_per_s": NG * fits_per_s,
             "gradient_step_ms_T5": grad_step_ms,
             "roofline": {"bound": "hbm", "kernel": "spread_mfma_kernel (fused F*y + Toeplitz-vector pass over the per-model sorted "
                                              "point layout, MFMA register tiles)",
@@ -647,7 +688,7 @@ def main():
                          "achieved_GBs": cg_bytes / (1e-3 * cgs_ms / max(cgs_n, 1)) / 1e9 if cgs_n else None,
                          "frac_hbm": cg_bytes / (1e-3 * cgs_ms / max(cgs_n, 1)) / 1e9 / HBM_PEAK_GBS if cgs_n else None,
                          "share_of_step": (cgs_ms / max(cgs_n, 1)) / ms_per_step if cgs_n else None},
-        }
+        })
         if weak is not None:
             rec["weak_scaling"] = weak
         if star is not None:
@@ -684,10 +725,7 @@ def main():
             rec["scaling_model"] = sm
         if world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(1000)
-        print(json.dumps(rec), file=record_out, flush=True)
-    if distributed:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish(rec)
 
 
 if __name__ == "__main__":

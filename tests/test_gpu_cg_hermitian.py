@@ -13,6 +13,17 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
+@pytest.fixture(autouse=True)
+def _serial_oracle():
+    """The oracle's CG runs on torch's CPU pool, whose reductions are split by thread count: its stopping point and the true
+    residual there move with the host's pool size (131^2 system at tol 1e-6: 6.9e-7 with 16 threads, 9.0e-7 with 8, 9.7e-7 with
+    1).  One thread makes the reference the same on every host."""
+    before = torch.get_num_threads()
+    torch.set_num_threads(1)
+    yield
+    torch.set_num_threads(before)
+
+
 def _rel(a, b):
     a = a.detach().cpu()
     b = b.detach().cpu()

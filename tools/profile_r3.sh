@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-3 profiles on the GPU box (everything lands under gpurun_out/r3/final; the summaries are copied to profiles/r3_* by hand):
-#   * bench.py (the driver's command) -> bench.json
+#   * bench.py --full (the whole record) -> bench.json
 #   * rocprofv3 kernel tables + HBM-traffic counters of the fit + mean step at N = 1e6 and N = 1e7 (bench.py --main-only: every
 #     launch belongs to the step); counters in their own passes (no trace domains with --pmc)
 #   * SQ counters of the new spread / gather kernels at N = 1e7
@@ -12,7 +12,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/r3/final
 mkdir -p $O
 cd $R
-python bench.py > $O/bench.json 2> $O/bench.err || echo "bench failed"
+python bench.py --full > $O/bench.json 2> $O/bench.err || echo "bench failed"
 cd /tmp && export TMPDIR=/tmp
 for N in 1000000 10000000; do
   rocprofv3 --kernel-trace --stats -d $O/stats_$N -o run -- python3 $R/bench.py --main-only --steps 20 --warmup 5 --global-n $N > $O/stats_$N.json 2> $O/stats_$N.err || echo "stats $N failed"

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-4 profiles on the GPU box (everything lands under gpurun_out/r4/final; the summaries are copied to profiles/r4_* by hand):
-#   * bench.py (the driver's command) -> bench.json
+#   * bench.py --full (the whole record) -> bench.json
 #   * rocprofv3 kernel tables + HBM-traffic counters of the fit + mean step at N = 1e6 and N = 1e7 (bench.py --main-only)
 #   * kernel table AND per-kernel HBM traffic (separate --pmc FETCH_SIZE / WRITE_SIZE passes) of BASELINE configs[4] (3-D
 #     Matern-3/2, N = 5e6: pair pass, own_fft_pass_kernel, cg3h_*) and of configs[3]'s hard case (2-D SE l = 0.05, 256^2
@@ -15,7 +15,7 @@ mkdir -p $O
 PARTS=${@:-bench main c5 c4 grad}
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 cd $R
-if has bench; then python bench.py > $O/bench.json 2> $O/bench.err || echo "bench failed"; echo "bench done"; fi
+if has bench; then python bench.py --full > $O/bench.json 2> $O/bench.err || echo "bench failed"; echo "bench done"; fi
 cd /tmp && export TMPDIR=/tmp
 trace() {   # trace <tag> <program args...>: kernel table + per-kernel traffic of one command
   local tag=$1; shift
