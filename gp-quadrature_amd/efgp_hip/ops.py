@@ -1,11 +1,12 @@
 """Tensor-level wrappers over the C ABI: torch tensors carry the device memory and the stream,
 every computation happens in libefgp_hip.so."""
 import ctypes as C
+import math
 import os
 
 import torch
 
-from .lib import lib, check
+from .lib import EFGP_EUNSUPPORTED, check, lib
 
 _CD = torch.complex128
 _RD = torch.float64
@@ -257,6 +258,10 @@ class ToeplitzOp:
         shp = (C.c_int64 * 3)()
         check(lib().efgp_toeplitz_fft_shape(self._h, shp), "efgp_toeplitz_fft_shape")
         self.fft_shape = [int(shp[a]) for a in range(self.d)]
+        self.fft_cells = math.prod(self.fft_shape)
+        # up to 4096 cells (64 x 64, 16^3, short lines) one workgroup solves a CG system; 2-D grids beyond run cooperative launches
+        self.one_workgroup_per_system = self.fft_cells <= 4096
+        self.may_hold_dead_rows = self.d == 2 and not self.one_workgroup_per_system
 
     def cg_shape(self, hermitian=False):
         """Circulant grid the fused CG solves of this operator run on (efgp_toeplitz_cg_shape): the smallest one the solvers'
@@ -349,22 +354,20 @@ def _start_vector(x0, bb, op, dev):
 
 def cg_solve(op, ws, sigmasq, variant, b, x0, tol, max_iter=None, early_stop=True, diag=None, batched=None, hermitian=False):
     """Fused device CG on ws*T(ws*.) (+sigma^2 | /sigma^2 + 1).  Returns (x, iters, row_iters).
-    hermitian=True: see cg_solve_async (the systems are transforms of real data; grids without a specialised kernel run
-    the general solver)."""
+    hermitian=True: see cg_solve_async, whose kernels run where the grid allows (settled); elsewhere the general solver."""
+    if not hermitian:
+        return _cg_solve_sync(op, ws, sigmasq, variant, b, x0, tol, max_iter, early_stop, diag, batched, False)
+    x, its = cg_solve_lazy(op, ws, sigmasq, variant, b, x0, tol, max_iter=max_iter, early_stop=early_stop, diag=diag,
+                           batched=batched, hermitian=True)
+    its.settle()
+    return x, int(its), list(its.rows)
+
+
+def _cg_solve_sync(op, ws, sigmasq, variant, b, x0, tol, max_iter, early_stop, diag, batched, hermitian):
+    """efgp_cg_solve[_hermitian]: returns when every system is solved (those of a dead grid barrier re-solved inside)."""
     dev = op.dev
     if batched is None:
         batched = b.ndim > 1
-    if hermitian:
-        res = cg_solve_async(op, ws, sigmasq, variant, b, x0, tol, max_iter=max_iter, early_stop=early_stop, diag=diag,
-                             batched=batched, hermitian=True)
-        if res is not None:
-            try:
-                return res[0], int(res[1]), list(res[1].rows)
-            except RuntimeError as err:
-                # a cooperative launch whose grid barrier died (-3: its systems hold NaN): this entry is the one that retries --
-                # fall through to the synchronous solver, which re-solves dead systems through the multi-launch iteration
-                if "cooperative CG" not in str(err):
-                    raise
     bb = _dc(b.reshape(-1, op.size), dev, _CD)
     x = _start_vector(x0, bb, op, dev)
     wsd = _dc(ws, dev, _CD)
@@ -382,26 +385,53 @@ def cg_solve(op, ws, sigmasq, variant, b, x0, tol, max_iter=None, early_stop=Tru
     return x.reshape(b.shape), int(iters.value), [int(r) for r in rows]
 
 
-class LazyIterations:
-    """Iteration counts of an asynchronous CG solve; reading them waits for the solve (device tensor -> host)."""
+_REFUSED = ("efgp_hip: a system given to the Hermitian CG kernel is not the transform of real data "
+            "(right-hand side not conjugate-even, or ws not real and even); its solution is NaN")
 
-    def __init__(self, rows_dev, batched, max_iter):
-        self._rows_dev = rows_dev
+
+class LazyIterations:
+    """Iteration counts of an asynchronous CG solve; reading them waits for the solve (device tensor -> host).  `x` and `redo`
+    (row indices -> the synchronous entry's result for them) come with a solve that may hold dead rows (-3, NaN): settle()."""
+
+    def __init__(self, rows_dev, batched, max_iter, x=None, redo=None):
+        self.rows_tensor = rows_dev         # per-system counts (int32) as the solve writes them: readable without waiting
         self._batched = batched
         self._max_iter = max_iter
         self._rows = None
+        self._x, self._redo = x, redo
+
+    @property
+    def needs_settle(self):
+        return self._redo is not None
+
+    def settle(self):
+        """One read of the counts of a solve that may hold dead rows (a no-op otherwise): -2 raises, -3 rows are solved again by
+        `redo` and written into x and the counts in place.  Returns whether a row was solved again."""
+        if not self.needs_settle:
+            return False
+        rows = [int(v) for v in self.rows_tensor.tolist()]
+        if -2 in rows:
+            raise RuntimeError(_REFUSED)
+        dead = [i for i, v in enumerate(rows) if v == -3]
+        if dead:
+            xd, _, rd = self._redo(dead)
+            self._x.view(len(rows), -1)[dead] = xd.reshape(len(dead), -1)
+            for i, v in zip(dead, rd):
+                rows[i] = int(v)
+            self.rows_tensor = self.rows_tensor.new_tensor(rows)
+        self._rows = rows
+        self._x = self._redo = None         # the operands of a re-solve need not outlive the settled solve
+        return bool(dead)
 
     @property
     def rows(self):
         if self._rows is None:
-            self._rows = [int(v) for v in self._rows_dev.tolist()]
+            self._rows = [int(v) for v in self.rows_tensor.tolist()]
             if any(v == -3 for v in self._rows):
-                raise RuntimeError("efgp_hip: a cooperative CG launch could not get its workgroups resident together (another "
-                                   "kernel held the CUs); the affected systems were not solved and hold NaN -- efgp_hip.cg_solve "
-                                   "retries them through the multi-launch iteration; EFGP_NO_CG_COOP=1 avoids the cooperative path")
+                raise RuntimeError("efgp_hip: a cooperative CG launch could not get its workgroups resident together; the affected "
+                                   "systems hold NaN -- settle() re-solves them; EFGP_NO_CG_COOP=1 avoids the cooperative path")
             if any(v == -2 for v in self._rows):
-                raise RuntimeError("efgp_hip: a system given to the Hermitian CG kernel is not the transform of real data "
-                                   "(right-hand side not conjugate-even, or ws not real and even); its solution is NaN")
+                raise RuntimeError(_REFUSED)
         return self._rows
 
     def __int__(self):
@@ -445,10 +475,9 @@ class LazyIterations:
 def cg_solve_async(op, ws, sigmasq, variant, b, x0, tol, max_iter=None, early_stop=True, diag=None, batched=None,
                    hermitian=False):
     """Like cg_solve but without host synchronisation: returns (x, LazyIterations) or None when the operator's
-    grid does not fit the persistent kernel (the caller then uses cg_solve).  hermitian=True: b, x0 are Fourier
+    grid does not fit the persistent kernel (cg_solve_lazy then takes the synchronous entry).  hermitian=True: b, x0 are Fourier
     coefficients of real functions and ws is real and even (efgp_cg_solve_hermitian_async; refused with an error when
     the data say otherwise)."""
-    from .lib import EFGP_EUNSUPPORTED
     dev = op.dev
     if batched is None:
         batched = b.ndim > 1
@@ -474,9 +503,27 @@ def cg_solve_async(op, ws, sigmasq, variant, b, x0, tol, max_iter=None, early_st
     if rc == EFGP_EUNSUPPORTED:
         return None
     check(rc, "efgp_cg_solve_async")
+    redo = None
+    if op.may_hold_dead_rows:           # settle(): the rows a dead grid barrier left, from the caller's start vector
+        def redo(ix):
+            return _cg_solve_sync(op, wsd, sigmasq, variant, bb[ix], x0.reshape(-1, op.size)[ix] if x0 is not None else None,
+                                  tol, mi, early_stop, dg, batched, hermitian)
     # keep the operands alive until the stream has consumed them: torch's caching allocator only reuses a block
     # for work enqueued later on the same stream, so dropping the Python references here is safe
-    return x.reshape(b.shape), LazyIterations(rows_dev, bool(batched), mi)
+    return x.reshape(b.shape), LazyIterations(rows_dev, bool(batched), mi, x, redo)
+
+
+def cg_solve_lazy(op, ws, sigmasq, variant, b, x0, tol, max_iter=None, early_stop=True, diag=None, batched=None,
+                  hermitian=False):
+    """cg_solve_async where the grid fits its kernels, the synchronous entry otherwise: (x, LazyIterations) on every grid.
+    Settle the counts before x is used without reading them (a no-op unless the solve may hold dead rows)."""
+    res = cg_solve_async(op, ws, sigmasq, variant, b, x0, tol, max_iter=max_iter, early_stop=early_stop, diag=diag,
+                         batched=batched, hermitian=hermitian)
+    if res is not None:
+        return res
+    batched = b.ndim > 1 if batched is None else bool(batched)
+    x, _, rows = _cg_solve_sync(op, ws, sigmasq, variant, b, x0, tol, max_iter, early_stop, diag, batched, hermitian)
+    return x, LazyIterations(torch.tensor(rows, dtype=torch.int32), batched, int(max_iter) if max_iter is not None else 2 * op.size)
 
 
 def cg_solve_mean_async(op, ws, sigmasq, diag_scale, fy, tol, max_iter=None, early_stop=True):
@@ -484,7 +531,6 @@ def cg_solve_mean_async(op, ws, sigmasq, diag_scale, fy, tol, max_iter=None, ear
     synchronisation: the right-hand side ws*fy, the Jacobi diagonal diag_scale*|ws|^2 + sigmasq and the zero start
     are formed inside the kernel.  diag_scale: 0-dim float64 device tensor (may be a view, e.g. v[centre].real) or
     None for no preconditioner.  Returns (beta, LazyIterations) or None when the grid does not fit the kernel."""
-    from .lib import EFGP_EUNSUPPORTED
     dev = op.dev
     ff = _dc(fy.reshape(-1), dev, _CD)
     if ff.numel() != op.size:
@@ -504,14 +550,19 @@ def cg_solve_mean_async(op, ws, sigmasq, diag_scale, fy, tol, max_iter=None, ear
     if rc == EFGP_EUNSUPPORTED:
         return None
     check(rc, "efgp_cg_solve_mean_async")
-    return x.reshape(fy.shape), LazyIterations(rows_dev, False, mi)
+    redo = None
+    if op.may_hold_dead_rows:           # settle(): rhs and Jacobi diagonal as the kernel forms them, the synchronous entry from zero
+        def redo(_):
+            vc = ds.reshape(1).to(_CD) if ds is not None else None
+            diag, rhs = gradient_prepare(wsd, ff, vc, sigmasq, want_diag=vc is not None)
+            return _cg_solve_sync(op, wsd, sigmasq, 0, rhs, None, tol, mi, early_stop, diag, False, True)
+    return x.reshape(fy.shape), LazyIterations(rows_dev, False, mi, x, redo)
 
 
 def lanczos(op, ws, sigmasq, variant, z, steps):
     """`steps` Lanczos steps on A (variant 0: ws*T(ws*.) + sigmasq, 1: /sigmasq + 1) from every row of z (P, M), all inside
     one launch (efgp_lanczos).  Returns (alpha (P,steps), beta (P,steps), |z|^2 (P,), steps_taken (P,) int32) as DEVICE
     tensors -- nothing is read back -- or None when the grid does not fit the persistent kernel."""
-    from .lib import EFGP_EUNSUPPORTED
     dev = op.dev
     zz = _dc(z.reshape(-1, op.size), dev, _CD)
     P = zz.shape[0]
@@ -636,7 +687,6 @@ def gradient_step(xd, yd, points, *, h, mtot, kconst, lengthscale, variance, sig
     """One hyper-gradient step of the adjoint estimator in ONE library call (efgp_gradient_step; csrc/gradient_step.cpp).
     kconst = (kind, nu, c0) of utils.kernels.kernel_constants.  Returns (out_vec, beta, mean LazyIterations, trace
     LazyIterations) -- all device-resident, nothing read back -- or None when the grid's solves are not single launches."""
-    from .lib import EFGP_EUNSUPPORTED
     dev = xd.device
     npts, d = xd.shape
     M = int(mtot) ** d

@@ -31,7 +31,7 @@ from cg import ConjugateGradients
 from kernels.kernel_params import GPParams
 from utils.kernels import get_xis
 
-from efgp_hip import NufftPlan, PointSet, ToeplitzOp, lanczos, lag_sums, variance_rhs, variance_contract, cg_solve, cg_solve_async, cg_solve_mean_async, vdot_real, compute_device, rademacher_fill, gradient_prepare, gradient_assemble
+from efgp_hip import NufftPlan, PointSet, ToeplitzOp, lanczos, lag_sums, variance_rhs, variance_contract, cg_solve, cg_solve_lazy, cg_solve_mean_async, vdot_real, compute_device, rademacher_fill, gradient_prepare, gradient_assemble
 from efgp_hip.dist import PointShards
 
 TWO_PI = 2.0 * math.pi
@@ -695,12 +695,9 @@ def efgpnd_gradient_batched(
         warm = mean_cg_init is not None and tuple(mean_cg_init.shape) == tuple(rhs.shape)
         b0 = mean_cg_init.detach().to(device=dev, dtype=torch.complex128) if warm else None          # None: the solver starts from zeros it allocates itself (no copy)
         # rhs = D F*y of the real y (and a warm start from an earlier solve of the same kind): coefficients of real functions
-        res_m = cg_solve_async(top, ws, sig, 0, rhs, b0, cg_tol, early_stop=early_stopping,
-                               diag=diag if use_mean_cg_preconditioner else None, batched=False, hermitian=True)
-        if res_m is None:
-            res_m = cg_solve(top, ws, sig, 0, rhs, b0, cg_tol, early_stop=early_stopping,
-                             diag=diag if use_mean_cg_preconditioner else None, batched=False, hermitian=True)[:2]
-        beta, mean_iters = res_m
+        beta, mean_iters = cg_solve_lazy(top, ws, sig, 0, rhs, b0, cg_tol, early_stop=early_stopping,
+                                         diag=diag if use_mean_cg_preconditioner else None, batched=False, hermitian=True)
+        mean_iters.settle()
         beta_raw = beta.clone()
         beta_s = ws * beta                                        # g = D beta
         Tg = top.apply(beta_s)
@@ -821,12 +818,8 @@ def _gradient_tail_native(kernel, grid, top, Fy, v, sig, N, N_local, cg_tol, ear
     diag, rhs = gradient_prepare(ws, Fy, v.reshape(-1)[cidx:cidx + 1], sig, want_diag=use_mean_pc or use_trace_pc)
     warm = mean_cg_init is not None and tuple(mean_cg_init.shape) == tuple(rhs.shape)
     b0 = mean_cg_init.detach().to(device=dev, dtype=torch.complex128) if warm else None
-    res_m = cg_solve_async(top, ws, sig, 0, rhs, b0, cg_tol, early_stop=early_stopping, diag=diag if use_mean_pc else None,
-                           batched=False, hermitian=True)
-    if res_m is None:
-        res_m = cg_solve(top, ws, sig, 0, rhs, b0, cg_tol, early_stop=early_stopping, diag=diag if use_mean_pc else None,
-                         batched=False, hermitian=True)[:2]
-    beta, mean_iters = res_m
+    beta, mean_iters = cg_solve_lazy(top, ws, sig, 0, rhs, b0, cg_tol, early_stop=early_stopping,
+                                     diag=diag if use_mean_pc else None, batched=False, hermitian=True)
     Tg = top.apply_scaled(beta, pre=ws)                         # T (D beta)
     lap("4_solve_cg")
     lap("5_compute_term2")                                      # term 2 is part of the assemble launch below
@@ -858,6 +851,9 @@ def _gradient_tail_native(kernel, grid, top, Fy, v, sig, N, N_local, cg_tol, ear
     # 7) batched CG from zero (reference :205-236)
     Beta_all, trace_iters = _solve_batched(shards, top, ws, sig, 0, B_all, cg_tol, early_stop=early_stopping,
                                            diag=diag if use_trace_pc else None)
+    # the mean solve is settled only here, where the batched solve has made the host wait already; a re-solved beta needs T g again
+    if mean_iters.settle():
+        Tg = top.apply_scaled(beta, pre=ws)
     lap("7_batch_cg_solve")
 
     # 7.5 / 8) every inner product of terms 1 and 2 and the final algebra: two launches, nothing read back
@@ -879,20 +875,16 @@ def _rows_over_ranks(shards, top, R):
     workgroup on one CU and up to num_CU of them run side by side on a GPU: splitting pays from more rows than CUs on.  Larger
     grids take many CUs per system (cooperative launch, multi-kernel 3-D iteration) and go through the rows in slabs:
     splitting pays as soon as every rank gets a row.  opts / env EFGP_SHARD_ROWS=0 keeps every solve replicated."""
-    import os
     if shards is None or not shards.active or R < shards.world_size:
         return False
-    cells = 1
-    for f in top.fft_shape:
-        cells *= int(f)
     if os.environ.get("EFGP_SHARD_ROWS", "1") == "0":
         split = False
-    elif cells <= 4096:                                 # circulant grid of one workgroup (64 x 64, short 1-D lines)
+    elif top.one_workgroup_per_system:
         split = R > torch.cuda.get_device_properties(top.dev).multi_processor_count
     else:
         split = True
     # the decision selects the collectives that follow: it must be identical on all ranks (checked once per shape)
-    return shards.agree(("rows_over_ranks", cells, R), split, top.dev)
+    return shards.agree(("rows_over_ranks", top.fft_cells, R), split, top.dev)
 
 
 def _solve_batched(shards, top, ws, sig, variant, B_all, tol, *, early_stop, diag, max_iter=None, hermitian=False):
@@ -901,48 +893,20 @@ def _solve_batched(shards, top, ws, sig, variant, B_all, tol, *, early_stop, dia
     (X (R, M), iteration count: int-like)."""
     from efgp_hip.ops import LazyIterations
     from efgp_hip.dist import solve_rows_sharded
-    cells = 1
-    for f in top.fft_shape:
-        cells *= int(f)
 
     def solve(block):
-        res = cg_solve_async(top, ws, sig, variant, block, None, tol, max_iter=max_iter, early_stop=early_stop, diag=diag,
-                             batched=True, hermitian=hermitian)
-        if res is not None:
-            if cells <= 4096:
-                return res[0], res[1]._rows_dev          # one workgroup per system: no grid barrier, nothing to re-solve
-            # cooperative launch (128^2..512^2 grids): a grid barrier that could not get its workgroups resident together
-            # leaves -3 in the row counts and NaN in those systems.  Nobody downstream reads the counts before using the
-            # solutions (diag_sums_nd, the gradient's assemble launch), so they are read HERE (one host wait behind a
-            # solve of milliseconds) and dead systems go through the synchronous solver's multi-launch iteration.
-            X, rows_dev = res[0], res[1]._rows_dev
-            rows = [int(v) for v in rows_dev.tolist()]
-            if any(v == -2 for v in rows):
-                res[1].rows                                # raises the Hermitian refusal
-            dead = [i for i, v in enumerate(rows) if v == -3]
-            if dead:
-                ix = torch.tensor(dead, device=X.device)
-                xd, _, rd = cg_solve(top, ws, sig, variant, block.reshape(len(rows), -1)[ix], None, tol, max_iter=max_iter,
-                                     early_stop=early_stop, diag=diag, batched=True, hermitian=hermitian)
-                X.reshape(len(rows), -1)[ix] = xd.reshape(len(dead), -1)
-                for i, v in zip(dead, rd):
-                    rows[i] = int(v)
-                rows_dev = torch.tensor(rows, dtype=torch.int32, device=X.device)
-            return X, rows_dev
-        x, _, rows = cg_solve(top, ws, sig, variant, block, None, tol, max_iter=max_iter, early_stop=early_stop, diag=diag,
-                              batched=True, hermitian=hermitian)
-        return x, rows
+        x, its = cg_solve_lazy(top, ws, sig, variant, block, None, tol, max_iter=max_iter, early_stop=early_stop, diag=diag,
+                               batched=True, hermitian=hermitian)
+        its.settle()           # nobody downstream reads the counts before using the solutions (diag_sums_nd, the assemble launch)
+        return x, its.rows_tensor
 
     R = B_all.shape[0]
-    mi = int(max_iter) if max_iter is not None else 2 * top.size
     if _rows_over_ranks(shards, top, R):
         X, rows = solve_rows_sharded(shards, B_all.reshape(R, -1), solve)
-        return X.reshape(B_all.shape), LazyIterations(rows, True, mi)
-    X, rows = solve(B_all)
-    if torch.is_tensor(rows):
-        return X, LazyIterations(rows, True, mi)
-    mx = max(rows)
-    return X, (mx + 1 if mx < mi else mx)
+        X = X.reshape(B_all.shape)
+    else:
+        X, rows = solve(B_all)
+    return X, LazyIterations(rows, True, int(max_iter) if max_iter is not None else 2 * top.size)
 
 
 def vdot_m(a, b):
@@ -1346,11 +1310,8 @@ class EFGPND(nn.Module):
             cidx = _center_flat(v)
             diag, rhs = gradient_prepare(grid.ws, Fy, v.reshape(-1)[cidx:cidx + 1], sig, want_diag=use_precond)
             b0 = self._beta.detach().to(device=dev, dtype=torch.complex128) if warm else None
-            res = cg_solve_async(toeplitz._op, grid.ws, sig, 0, rhs, b0, tol, early_stop=True, diag=diag, batched=False,
-                                 hermitian=True)
-            if res is None:
-                res = cg_solve(toeplitz._op, grid.ws, sig, 0, rhs, b0, tol, early_stop=True, diag=diag, batched=False,
-                               hermitian=True)[:2]      # 3-D grids: the planes k0 >= 0 only (efgp_cg_solve_hermitian)
+            res = cg_solve_lazy(toeplitz._op, grid.ws, sig, 0, rhs, b0, tol, early_stop=True, diag=diag, batched=False,
+                                hermitian=True)         # 3-D grids: the planes k0 >= 0 only (efgp_cg_solve_hermitian)
         beta, iters = res
         self._beta = beta.to(cdtype) if cdtype != torch.complex128 else beta
         self._xis = (grid, rdtype)                 # the (M, d) node tensor is built when somebody asks for it (property below)
@@ -1361,23 +1322,10 @@ class EFGPND(nn.Module):
         self._last_fit_stats = dict(mean_cg_iters=iters, mtot=grid.mtot, feature_count=grid.M, h=grid.h)
         self._fitted = True
         self._update_param_cache()
-        if d == 2 and prod(int(f) for f in toeplitz._op.fft_shape) > 4096 and not isinstance(iters, int):
-            # cooperative launch (128^2..512^2): a grid barrier that could not get its workgroups resident together leaves -3 in the
-            # count and NaN in beta.  Nothing downstream reads the count before using beta, so it is read HERE -- last, behind the
-            # host's own bookkeeping, which thereby still overlaps the solve -- and a dead solve goes through the synchronous
-            # multi-launch iteration.
-            try:
-                iters.rows
-            except RuntimeError as err:
-                if "cooperative CG" not in str(err):
-                    raise
-                cidx = _center_flat(v)
-                diag, rhs = gradient_prepare(grid.ws, Fy, v.reshape(-1)[cidx:cidx + 1], sig, want_diag=use_precond)
-                beta, iters = cg_solve(toeplitz._op, grid.ws, sig, 0, rhs, None, tol, early_stop=True, diag=diag, batched=False,
-                                       hermitian=True)[:2]
-                self._beta = beta.to(cdtype) if cdtype != torch.complex128 else beta
-                self._fit_state["beta"] = beta
-                self._last_fit_stats["mean_cg_iters"] = iters
+        # Nothing downstream reads the count before using beta: a solve that may hold a dead system is settled HERE -- last, behind
+        # the host's own bookkeeping, which thereby still overlaps the solve.  beta and the count are repaired in place.
+        if iters.settle() and cdtype != torch.complex128:
+            self._beta = beta.to(cdtype)
 
     @property
     def _xis(self):

@@ -125,3 +125,45 @@ def test_fit_survives_a_dead_grid_barrier(monkeypatch):
     assert torch.isfinite(torch.view_as_real(beta_dead)).all()
     assert abs(it_dead - it_ok) <= 1
     assert float((beta_dead - beta_ok).abs().max()) < 1e-7 * float(beta_ok.abs().max())
+
+
+@pytest.mark.parametrize("literal", [False, True])
+def test_gradient_survives_a_dead_grid_barrier(monkeypatch, literal):
+    """compute_gradients on the 128 x 128 grid: the mean solve (reference: efgpnd.py:128-153) is an asynchronous cooperative
+    launch in the native tail (the one-call step only takes grids of F^d <= 4096) and in the literal sequence
+    (EFGP_NO_FUSED_GRADIENT); a dead grid barrier must be re-solved before beta reaches the gradient.  Same probes, same
+    gradient: the re-solves run the multi-launch iteration to the same CG tolerance (1e-8), which the fit test above holds to
+    1e-7 of beta and the variance test to 1e-6 of the batched solves; 1e-6 of the largest gradient entry covers both."""
+    import efgpnd
+    from efgpnd import EFGPND
+    from kernels.matern import Matern
+    g = torch.Generator().manual_seed(5)
+    N = 3000
+    x = torch.rand(N, 2, dtype=torch.float64, generator=g)
+    y = torch.sin(5 * x[:, 0]) * torch.cos(3 * x[:, 1]) + 0.1 * torch.randn(N, dtype=torch.float64, generator=g)
+    if literal:
+        monkeypatch.setenv("EFGP_NO_FUSED_GRADIENT", "1")
+    tails = []
+    native_tail = efgpnd._gradient_tail_native
+    monkeypatch.setattr(efgpnd, "_gradient_tail_native", lambda *a, **k: tails.append(1) or native_tail(*a, **k))
+    kern = Matern(dimension=2, nu=2.5, init_lengthscale=0.1, init_variance=1.0)
+    model = EFGPND(x.cuda(), y.cuda(), kern, sigmasq=0.1, eps=1e-3, nufft_eps=1e-8, estimate_params=False,
+                   opts={"cg_tolerance": 1e-8, "mean_cg_warm_start": False})       # no warm start: both runs solve from zero
+    model.fit()
+    assert tuple(model._toeplitz.fft_shape) == (128, 128)
+    T = 4
+    M = int(model.last_fit_stats["feature_count"])
+    probes_V = (torch.randint(0, 2, (T, M), generator=g) * 2 - 1).to(torch.float64).cuda()
+
+    def grad():
+        return model.compute_gradients(trace_samples=T, apply_gradients=False, cg_tol=1e-8, probe_seed=11,
+                                       probes_V=probes_V).clone()
+
+    g_ok = grad()
+    monkeypatch.setenv("EFGP_COOP_TEST_DEAD", "1")
+    g_dead = grad()
+    monkeypatch.delenv("EFGP_COOP_TEST_DEAD")
+    assert len(tails) == (0 if literal else 2)
+    assert torch.isfinite(g_ok).all() and torch.isfinite(g_dead).all(), g_dead
+    err = float((g_dead - g_ok).abs().max()) / float(g_ok.abs().max())
+    assert err < 1e-6, (err, g_ok, g_dead)

@@ -179,6 +179,37 @@ def test_generic_cg_matches_oracle():
         ConjugateGradients(3.0, b, b)
 
 
+def test_settle_resolves_only_the_dead_rows():
+    """LazyIterations.settle(): one read of the counts; rows a dead grid barrier left (-3) go through the re-solver and are
+    written into x in place, their counts into the counts; -2 (refused Hermitian data) raises.  No re-solver: a no-op, and
+    reading the counts keeps raising on -3."""
+    from efgp_hip.ops import LazyIterations
+    x = torch.tensor([[1.0] * 4, [float("nan")] * 4, [3.0] * 4], dtype=torch.complex128)
+    calls = []
+
+    def redo(ix):
+        calls.append(list(ix))
+        return torch.full((len(ix), 4), 2.0, dtype=torch.complex128), 6, [6] * len(ix)
+
+    its = LazyIterations(torch.tensor([5, -3, 7], dtype=torch.int32), True, 100, x=x, redo=redo)
+    buf = x.data_ptr()
+    assert its.needs_settle and its.settle() is True
+    assert calls == [[1]]
+    assert x.data_ptr() == buf and torch.equal(x, torch.tensor([[1.0] * 4, [2.0] * 4, [3.0] * 4], dtype=torch.complex128))
+    assert its.rows == [5, 6, 7] and its.rows_tensor.tolist() == [5, 6, 7] and int(its) == 8
+    assert not its.needs_settle and its.settle() is False and calls == [[1]]
+
+    refused = LazyIterations(torch.tensor([5, -2, -3], dtype=torch.int32), True, 100, x=x.clone(), redo=redo)
+    with pytest.raises(RuntimeError, match="not the transform of real data"):
+        refused.settle()
+    assert calls == [[1]]
+
+    raw = LazyIterations(torch.tensor([5, -3, 7], dtype=torch.int32), True, 100)
+    assert not raw.needs_settle and raw.settle() is False
+    with pytest.raises(RuntimeError, match="cooperative CG"):
+        raw.rows
+
+
 def test_cpu_quota_parsing(tmp_path):
     """efgp_hip.cpu_quota reads the CFS bandwidth limit (cgroup v2 cpu.max, v1 cfs files); 'max' / absent = unlimited."""
     from efgp_hip import cpu_quota
