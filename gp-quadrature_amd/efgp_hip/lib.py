@@ -84,6 +84,9 @@ _SIGNATURES = {
     "efgp_lag_sums": (_I, [_I, _I, _I64, _VP, _VP, _I, _VP, _VP]),
     "efgp_variance_rhs": (_I, [_I, _I, _I64, _D, _VP, _I64, _VP, _VP, _VP]),
     "efgp_variance_contract": (_I, [_I, _I, _I64, _D, _VP, _I64, _VP, _VP, _VP, _VP]),
+    "efgp_pg_estep_update": (_I, [_I, _I64, _I, _VP, _VP, C.c_uint64, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "efgp_pg_weight_rows": (_I, [_I, _I64, _I, _VP, C.c_uint64, _VP, _VP, _VP]),
+    "efgp_pg_mstep_terms": (_I, [_I, _I64, _I, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP]),
     "efgp_comm_unique_id": (_I, [_VP]),
     "efgp_comm_init": (_I, [C.POINTER(_VP), _I, _I, _I, _VP]),
     "efgp_comm_allreduce_sum": (_I, [_VP, _VP, C.c_size_t, _VP]),

@@ -620,6 +620,61 @@ def variance_contract(x_new, h, mtot, ws, gamma):
     return out
 
 
+def pg_estep_update(s_rows, delta, targets, rho, *, probes=None, seed=0, pg_b=None):
+    """The E-step's pass over the points (efgp_pg_estep_update): s_rows (J+1, N) float64 = [mean; S z_1..z_J]; probes (J, N) or
+    None for the counter-hash probes of `seed`; delta (N,) is updated in place.  Returns (mean, sigma_diag, residual, correct) --
+    residual (1,) float64 and correct (1,) int64 are device tensors (nothing is read back)."""
+    dev = delta.device
+    J = s_rows.shape[0] - 1
+    N = delta.numel()
+    for t_ in (s_rows, delta, targets) + tuple(t for t in (probes, pg_b) if t is not None):
+        assert t_.is_cuda and t_.device == dev and t_.dtype == _RD and t_.is_contiguous()
+    assert s_rows.shape == (J + 1, N) and targets.numel() == N
+    assert probes is None or probes.shape == (J, N)
+    assert pg_b is None or pg_b.numel() == N
+    mean = torch.empty(N, dtype=_RD, device=dev)
+    sdiag = torch.empty(N, dtype=_RD, device=dev)
+    resid = torch.empty(1, dtype=_RD, device=dev)
+    correct = torch.empty(1, dtype=torch.int64, device=dev)
+    with _on(dev):
+        check(lib().efgp_pg_estep_update(dev.index, N, J, _ptr(s_rows), _ptr(probes) if probes is not None else None,
+                                         int(seed) & (2 ** 64 - 1), _ptr(pg_b) if pg_b is not None else None, _ptr(targets), float(rho),
+                                         _ptr(delta), _ptr(mean), _ptr(sdiag), _ptr(resid), _ptr(correct), _stream(dev)),
+              "efgp_pg_estep_update")
+    return mean, sdiag, resid, correct
+
+
+def pg_weight_rows(omega, nrows, *, probes=None, seed=0):
+    """omega .* z for z = probes (nrows, N) or the counter-hash probes of `seed` (efgp_pg_weight_rows) -> (nrows, N) float64."""
+    dev = omega.device
+    N = omega.numel()
+    assert omega.dtype == _RD and omega.is_contiguous()
+    assert probes is None or (probes.dtype == _RD and probes.is_contiguous() and probes.shape == (int(nrows), N))
+    out = torch.empty((int(nrows), N), dtype=_RD, device=dev)
+    with _on(dev):
+        check(lib().efgp_pg_weight_rows(dev.index, N, int(nrows), _ptr(probes) if probes is not None else None, int(seed) & (2 ** 64 - 1),
+                                        _ptr(omega), _ptr(out), _stream(dev)), "efgp_pg_weight_rows")
+    return out
+
+
+def pg_mstep_terms(beta_x, beta_probes, r_probes, dprime):
+    """term1 | term2 | grad of the PG M-step as ONE device vector of 3 P doubles (efgp_pg_mstep_terms); dprime (M, P) real or
+    complex (real part read)."""
+    dev = beta_x.device
+    M = beta_x.numel()
+    J = beta_probes.shape[0] if beta_probes is not None else 0
+    P = dprime.shape[1]
+    for t_ in (beta_x,) + ((beta_probes, r_probes) if J else ()):
+        assert t_.is_cuda and t_.dtype == _CD and t_.is_contiguous()
+    assert dprime.is_contiguous() and dprime.dtype in (_CD, _RD) and dprime.shape == (M, P)
+    assert J == 0 or (beta_probes.numel() == J * M and r_probes.numel() == J * M)
+    out = torch.empty(3 * P, dtype=_RD, device=dev)
+    with _on(dev):
+        check(lib().efgp_pg_mstep_terms(dev.index, M, J, P, _ptr(beta_x), _ptr(beta_probes) if J else None, _ptr(r_probes) if J else None,
+                                        _ptr(dprime), int(dprime.is_complex()), _ptr(out), _stream(dev)), "efgp_pg_mstep_terms")
+    return out
+
+
 class RcclComm:
     """Sum / min / max all-reduce and broadcast over RCCL without a torch process group (C ABI: efgp_comm_*).
     `unique_id` (128 bytes) comes from `RcclComm.make_id()` on rank 0 and reaches the other ranks by the caller's channel."""

@@ -345,11 +345,13 @@ def _upload(t: torch.Tensor, dev: torch.device) -> torch.Tensor:
 class _Grid:
     """Frequency grid and weights for the current hyper-parameters (host scalars + device vectors)."""
 
-    def __init__(self, kernel, eps, L, d, dev, want_grad=False, defer_weights=False):
+    def __init__(self, kernel, eps, L, d, dev, want_grad=False, defer_weights=False, trunc_eps=None):
         """defer_weights=True: only the grid (h, mtot) is set up; the caller enqueues the N-scale pass over the points -- which
         needs nothing else -- and calls `make_weights` behind it (the gradient step waits for its result on the host every step,
-        so what the host does before the first big launch is dead time on the device: ~35 us of a 0.4-ms step)."""
-        xis_1d, h, mtot = get_xis(kernel_obj=kernel, eps=eps, L=L, use_integral=True, l2scaled=False)
+        so what the host does before the first big launch is dead time on the device: ~35 us of a 0.4-ms step).
+        trunc_eps: tolerance of the frequency truncation when it differs from `eps` (get_xis; the PG classifier passes its
+        spectral_eps and trunc_eps separately, pg_classifier.py:326-333); None keeps trunc_eps = eps."""
+        xis_1d, h, mtot = get_xis(kernel_obj=kernel, eps=eps, L=L, use_integral=True, l2scaled=False, trunc_eps=trunc_eps)
         self.h = float(h)
         self.mtot = int(mtot)
         self.d = d

@@ -367,6 +367,31 @@ int efgp_variance_rhs(int device, int dim, int64_t mtot, double h, const double*
 int efgp_variance_contract(int device, int dim, int64_t mtot, double h, const double* x_new, int64_t npts, const void* ws,
                            const void* gamma, double* out, void* stream);
 
+/* ---- Polya-Gamma classifier: the pointwise and M-scale passes around the weighted solves (pg_classifier.py) -----------------
+ * efgp_pg_estep_update: one pass over the N points after the E-step's batched solve (:552-569, :252-257, :129-138):
+ *     mean[n] = S[0, n];  sigma_diag[n] = (1/J) sum_j z[j, n] S[1 + j, n];
+ *     c = sqrt(max(sigma_diag + mean^2, 1e-12));  Lambda = c > 1e-8 ? 0.5 b tanh(c/2) / max(c, 1e-12) : 0.25 b;
+ *     delta[n] = max(delta[n] (1 - rho) + rho Lambda, 0)   (in place);
+ *     *residual_out = max_n |delta[n] - Lambda[n]|;
+ *     *correct_out  = #{n : (sigmoid(mean / sqrt(1 + pi max(sigma_diag, 0) / 8)) > 1/2) == (targets[n] != 0)}.
+ * s_rows: (J + 1, N) doubles; probes: (J, N) doubles, or NULL: z[j, n] = the counter-hash probe of efgp_rademacher_fill
+ * (seed, row j, index n); pg_b: N doubles or NULL for b = 1; residual_out (1 double) and correct_out (1 int64) are DEVICE
+ * pointers (either may be NULL).  Deterministic: a max and an integer count, partials added in a fixed order. */
+int efgp_pg_estep_update(int device, int64_t npts, int nprobes, const double* s_rows, const double* probes, uint64_t seed,
+                         const double* pg_b, const double* targets, double rho, double* delta, double* mean_out, double* sigma_diag_out,
+                         double* residual_out, int64_t* correct_out, void* stream);
+/* efgp_pg_weight_rows: out[j, n] = omega[n] z[j, n] for j < nrows (the rows whose type-1 transform is the M-step's
+ * R = F*(omega z), :616); probes (nrows, N) or NULL for the counter-hash probes of `seed` as above. */
+int efgp_pg_weight_rows(int device, int64_t npts, int nrows, const double* probes, uint64_t seed, const double* omega, double* out,
+                        void* stream);
+/* efgp_pg_mstep_terms: the M-step's feature-space estimator (:616-623), P = nhypers <= 4:
+ *     term1[p] = sum_k D'[k, p] |beta_x[k]|^2;   term2[p] = (1/J) sum_j sum_k Re(conj(R[j, k]) beta_probes[j, k]) D'[k, p];
+ *     out = term1 (P) | term2 (P) | grad = (term1 - term2) / 2 (P)   -- 3 P DEVICE doubles.
+ * beta_x (M) and beta_probes, r_probes (J, M) complex; dprime (M, P) real, or complex with only its real part read when
+ * dprime_is_complex (the layout efgp_spectral_weights writes).  Partial sums per workgroup, added in a fixed order. */
+int efgp_pg_mstep_terms(int device, int64_t nmodes, int nprobes, int nhypers, const void* beta_x, const void* beta_probes,
+                        const void* r_probes, const void* dprime, int dprime_is_complex, double* out, void* stream);
+
 /* ---- collectives of the point-sharded fit (one process per GPU, RCCL over xGMI) ------------------------------------
  * The reference has no distributed code; sharding the N observation points needs exactly these sums between the spread
  * pass and the replicated solve: the gridded partials F*y and v (efgpnd.py:118-124 / 786-790), the batched F*Z of the
