@@ -85,6 +85,8 @@ _SIGNATURES = {
     "efgp_variance_rhs": (_I, [_I, _I, _I64, _D, _VP, _I64, _VP, _VP, _VP]),
     "efgp_variance_contract": (_I, [_I, _I, _I64, _D, _VP, _I64, _VP, _VP, _VP, _VP]),
     "efgp_pg_estep_update": (_I, [_I, _I64, _I, _VP, _VP, C.c_uint64, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "efgp_pg_nb_estep_update": (_I, [_I, _I64, _I, _VP, _VP, C.c_uint64, _VP, _D, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "efgp_pg_nb_total_count_grad": (_I, [_I, _I64, _VP, _VP, _VP, _D, _I, _VP, _VP, _VP, _VP]),
     "efgp_pg_weight_rows": (_I, [_I, _I64, _I, _VP, C.c_uint64, _VP, _VP, _VP]),
     "efgp_pg_mstep_terms": (_I, [_I, _I64, _I, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP]),
     "efgp_comm_unique_id": (_I, [_VP]),

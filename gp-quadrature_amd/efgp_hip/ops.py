@@ -644,6 +644,45 @@ def pg_estep_update(s_rows, delta, targets, rho, *, probes=None, seed=0, pg_b=No
     return mean, sdiag, resid, correct
 
 
+def pg_nb_estep_update(s_rows, delta, targets, total_count, rho, *, probes=None, seed=0, out=None):
+    """The negative-binomial E-step pass (efgp_pg_nb_estep_update): as pg_estep_update with b = targets + total_count formed in
+    the kernel.  Returns (mean, sigma_diag, scalars) -- scalars (2,) float64 on the device = [residual, sum_n |r exp(mean +
+    max(sigma_diag, 0)/2) - y|] (one read-back for both); `out` may pass that (2,) buffer in."""
+    dev = delta.device
+    J = s_rows.shape[0] - 1
+    N = delta.numel()
+    for t_ in (s_rows, delta, targets) + ((probes,) if probes is not None else ()):
+        assert t_.is_cuda and t_.device == dev and t_.dtype == _RD and t_.is_contiguous()
+    assert s_rows.shape == (J + 1, N) and targets.numel() == N
+    assert probes is None or probes.shape == (J, N)
+    mean = torch.empty(N, dtype=_RD, device=dev)
+    sdiag = torch.empty(N, dtype=_RD, device=dev)
+    scalars = torch.empty(2, dtype=_RD, device=dev) if out is None else out
+    assert scalars.dtype == _RD and scalars.device == dev and scalars.numel() == 2 and scalars.is_contiguous()
+    with _on(dev):
+        check(lib().efgp_pg_nb_estep_update(dev.index, N, J, _ptr(s_rows), _ptr(probes) if probes is not None else None,
+                                            int(seed) & (2 ** 64 - 1), _ptr(targets), float(total_count), float(rho), _ptr(delta),
+                                            _ptr(mean), _ptr(sdiag), _ptr(scalars), _ptr(scalars[1:]), _stream(dev)),
+              "efgp_pg_nb_estep_update")
+    return mean, sdiag, scalars
+
+
+def pg_nb_total_count_grad(targets, mean, sigma_diag, total_count, nodes, weights, *, out=None):
+    """sum_n [digamma(y + r) - digamma(r) + sum_q w_q logsigmoid(-(mean + sqrt(max(sigma_diag, 0)) x_q))]
+    (efgp_pg_nb_total_count_grad) -> (1,) float64 on the device; nodes / weights: the (Q,) Gauss-Hermite rule, Q <= 128."""
+    dev = mean.device
+    N = mean.numel()
+    for t_ in (targets, mean, sigma_diag, nodes, weights):
+        assert t_.is_cuda and t_.device == dev and t_.dtype == _RD and t_.is_contiguous()
+    assert targets.numel() == N and sigma_diag.numel() == N and nodes.numel() == weights.numel()
+    grad = torch.empty(1, dtype=_RD, device=dev) if out is None else out
+    with _on(dev):
+        check(lib().efgp_pg_nb_total_count_grad(dev.index, N, _ptr(targets), _ptr(mean), _ptr(sigma_diag), float(total_count),
+                                                nodes.numel(), _ptr(nodes), _ptr(weights), _ptr(grad), _stream(dev)),
+              "efgp_pg_nb_total_count_grad")
+    return grad
+
+
 def pg_weight_rows(omega, nrows, *, probes=None, seed=0):
     """omega .* z for z = probes (nrows, N) or the counter-hash probes of `seed` (efgp_pg_weight_rows) -> (nrows, N) float64."""
     dev = omega.device

@@ -1,11 +1,14 @@
-"""Polya-Gamma (PG) augmented GP classifier on the HIP EFGP operators (reference: polyagamma_classification/pg_classifier.py,
-`PolyagammaGPClassifier`, Bernoulli likelihood with logistic link).
+"""Polya-Gamma (PG) augmented GP estimators on the HIP EFGP operators (reference: polyagamma_classification/pg_classifier.py):
+`PolyagammaGPClassifier` (Bernoulli likelihood with logistic link) and `PolyagammaGPNegativeBinomialRegressor` (counts,
+y ~ NB(r, sigmoid(f)), optionally with a learnt r).  Both share one fit loop; the likelihood enters only through the PG
+strength kappa, the PG shape b and the training metric.
 
 Every solve of the model is the weighted feature-space system  (I + D T_w D) u = b,  T_w the Toeplitz operator of
 F* diag(w) F for the PG weights w = delta, D = ws (E-step) or the clamped D_s (M-step, mean, prediction).  Here each of
 them is ONE batched call of the fused device solver (efgp_cg_solve, variant 1 with sigma^2 = 1), the transforms are the
 library's NUFFT plans on a per-fit point layout, and the N-scale pointwise work of the PG update and the M-step's trace
-estimator are kernels of their own (efgp_pg_estep_update, efgp_pg_weight_rows, efgp_pg_mstep_terms; csrc/pg_ops.hip).
+estimator are kernels of their own (efgp_pg_estep_update, efgp_pg_weight_rows, efgp_pg_mstep_terms; csrc/pg_ops.hip); the
+negative-binomial E-step pass and the gradient of r are efgp_pg_nb_estep_update and efgp_pg_nb_total_count_grad.
 torch carries allocations, the O(M) diagonal products around the solves and the O(#hypers) optimiser state.
 
 Scope: SE kernel, float64, predictive_variance_method="exact", a GPU device.  Anything else is refused with an error that
@@ -13,6 +16,7 @@ names the option.  The product path does not import scikit-learn.
 """
 from __future__ import annotations
 
+import functools
 import inspect
 import math
 import os
@@ -25,7 +29,8 @@ if _PKG not in sys.path:
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-__all__ = ["PolyagammaGPClassifier", "approximate_logistic_gaussian_prob", "_pg_omega_expectation"]
+__all__ = ["PolyagammaGPClassifier", "PolyagammaGPNegativeBinomialRegressor", "approximate_logistic_gaussian_prob",
+           "negative_binomial_gaussian_mean", "_gauss_hermite_normal_rule", "_pg_omega_expectation"]
 
 _SE_NAMES = ("squared_exponential", "se", "rbf")
 _EXACT_VARIANCE = "exact"
@@ -39,6 +44,23 @@ def approximate_logistic_gaussian_prob(mean: torch.Tensor, variance: torch.Tenso
         return torch.sigmoid(mean)
     scale = torch.sqrt(1.0 + (math.pi / 8.0) * variance.clamp_min(0.0))
     return torch.sigmoid(mean / scale)
+
+
+def negative_binomial_gaussian_mean(mean: torch.Tensor, variance: torch.Tensor, *, total_count: float) -> torch.Tensor:
+    """E[count] = r exp(mean + variance / 2) of y ~ NB(r, sigmoid(f)), f ~ N(mean, variance) (negative variances count as 0)."""
+    return total_count * torch.exp(mean + 0.5 * variance.clamp_min(0.0))
+
+
+@functools.lru_cache(maxsize=None)
+def _gauss_hermite_normal_rule(num_nodes: int):
+    """(nodes, weights) of the num_nodes-point Gauss-Hermite rule for E[g(X)], X ~ N(0, 1): numpy's hermgauss rule for the
+    weight exp(-x^2), nodes scaled by sqrt(2) and weights by 1/sqrt(pi).  Read-only float64 arrays."""
+    if num_nodes <= 0:
+        raise ValueError("num_nodes must be positive.")
+    x, w = np.polynomial.hermite.hermgauss(int(num_nodes))
+    nodes, weights = (x * np.sqrt(2.0)).astype(np.float64), (w / np.sqrt(np.pi)).astype(np.float64)
+    nodes.flags.writeable = weights.flags.writeable = False
+    return nodes, weights
 
 
 def _pg_omega_expectation(c: torch.Tensor, pg_b: torch.Tensor) -> torch.Tensor:
@@ -104,29 +126,14 @@ class _Spectral:
         self.plan = NufftPlan(xd, self.h, nufft_eps, xcen=None, points=points)
 
 
-class PolyagammaGPClassifier:
-    """Scikit-learn style PG-augmented GP classifier (Bernoulli likelihood, logistic link) on the HIP EFGP operators.
+class _BasePolyagammaGPEstimator:
+    """The fit loop, solves and prediction shared by the PG estimators (the reference's _BasePolyagammaGPEstimator).  A
+    subclass supplies the likelihood: `_prepare_targets` (checks, model targets), `_start_likelihood` (kappa, optimiser state),
+    `_initial_delta`, `_estep_pass` (the N-scale E-step kernel and its metric), `_refresh_likelihood` / `_step_auxiliary` /
+    `_final_record` (parameters of the likelihood learnt alongside the kernel's) and `_response_mean`."""
 
-    Constructor keywords and defaults are the reference's.  `fit` follows its loop: delta = b / 4; per outer iteration the
-    spectral state is rebuilt, one E-step (`e_step_iters` damped updates with the weighted operator built from delta as it
-    stands at the start) and one M-step gradient run, and Adam (maximize=True) steps the log hyper-parameters with the raw
-    gradient (g_l l, g_var var, 0); then a final E-step (seed random_state + 999_999) and the mean solve.
-
-    Solves: `use_exact_weighted_toeplitz_operator` True or False give the same matrix F* diag(delta) F up to `nufft_eps`, so
-    both run the fused weighted Toeplitz operator (efgp_cg_solve).
-
-    Probes: with `random_state` set, the probes are the reference's (drawn by torch.Generator on the host, seeds
-    random_state + 1000 outer + 17 (it + 1) for the E-step and + 10_000 for the M-step) and uploaded -- 2 J N doubles per
-    outer iteration (J = n_e_probes = n_m_probes = 10, N = 1e6: 160 MB of host generation and upload per iteration), so a
-    seeded fit equals the reference's.  With random_state=None the reference promises no stream: one seed per E-step /
-    M-step is drawn from torch's global generator and the +-1 probes are generated on the device by the counter hash of
-    efgp_rademacher_fill / efgp_nufft_type1_rademacher; they never exist in memory.
-
-    Supported: kernel "squared_exponential" (aliases "se", "rbf"), dtype float64, predictive_variance_method "exact", a
-    GPU device ("auto", "cuda", "cuda:k").  Others raise ValueError / NotImplementedError naming the option.
-
-    After `fit`, `last_fit_stats` lists every solve (step, outer iteration, solver entry, `fused`, CG count, rows).
-    """
+    _what = "the PG estimator"          # how option errors name the estimator
+    _history_key = _history_label = _training_attr = None
 
     def __init__(self, *, kernel: str = "squared_exponential", lengthscale_init: float = 0.3, variance_init: float = 1.0,
                  max_iter: int = 50, e_step_iters: int = 1, final_e_step_iters: int = 1, e_step_tol: float = 1e-4, rho0: float = 0.7,
@@ -190,7 +197,7 @@ class PolyagammaGPClassifier:
                              f"({', '.join(_SE_NAMES)})")
         dt = self.dtype
         if not (dt == "float64" or dt is torch.float64):
-            raise ValueError(f"dtype={dt!r} is not supported: the PG classifier runs in float64 only")
+            raise ValueError(f"dtype={dt!r} is not supported: {self._what} runs in float64 only")
         method = str(self.predictive_variance_method).lower()
         if method in _UNSUPPORTED_VARIANCE:
             raise NotImplementedError(f"predictive_variance_method={self.predictive_variance_method!r} is not implemented; "
@@ -200,7 +207,7 @@ class PolyagammaGPClassifier:
                              "{'exact', 'stochastic', 'stochastic_diag_sums', 'chebyshev'}")
         dev = str(self.device)
         if dev == "cpu" or dev.startswith("cpu:"):
-            raise ValueError(f"device={self.device!r} is not supported: the PG classifier runs on the GPU only (HIP kernels, "
+            raise ValueError(f"device={self.device!r} is not supported: {self._what} runs on the GPU only (HIP kernels, "
                              "no CPU path)")
         if dev != "auto" and not dev.startswith("cuda"):
             raise ValueError(f"device={self.device!r}: use 'auto', 'cuda' or 'cuda:<index>'")
@@ -249,7 +256,6 @@ class PolyagammaGPClassifier:
 
     # -- E-step (pg_classifier.py:507-582) ----------------------------------------------------------------------------------
     def _estep(self, spec, max_iters, seed, outer):
-        from efgp_hip.ops import pg_estep_update
         J = int(self.n_e_probes)
         N = self._N
         op = self._weighted_operator(spec, self._delta)
@@ -266,13 +272,9 @@ class PolyagammaGPClassifier:
             x, cg_iters = self._solve(op, spec.ws, fz * spec.ws, True, "estep", outer)
             S = spec.plan.type2(x, spec.shape, real_only=True, mode_scale=spec.ws, batched=True)
             rho = self.rho0 / (1.0 + self.gamma * it)
-            mean, sdiag, resid, correct = pg_estep_update(S, self._delta, self._targets, rho, probes=probes, seed=pseed)
-            self._mean, self._sigma_diag = mean, sdiag
-            residual = float(resid.item())
-            # the reference's metric is a float32 mean of the per-point hits (pg_classifier.py:129-138)
-            metric = float(np.float32(int(correct.item())) / np.float32(N))
+            self._mean, self._sigma_diag, residual, metric = self._estep_pass(S, rho, probes, pseed)
             if self.verbose > 1:
-                print(f"E-step it {it:3d} rho={rho:.3f} max|Delta-Lambda|={residual:.3e} approx_acc={metric:.4f}")
+                print(f"E-step it {it:3d} rho={rho:.3f} max|Delta-Lambda|={residual:.3e} {self._history_label}={metric:.4f}")
             if residual < self.e_step_tol:
                 break
         return {"residual": residual, "metric": metric, "cg_iters": float(cg_iters)}
@@ -304,16 +306,15 @@ class PolyagammaGPClassifier:
     # -- fit (pg_classifier.py:1254-1433) --------------------------------------------------------------------------------------
     def fit(self, X, y):
         X_arr, y_arr = _check_X_y(X, y)
-        classes = np.unique(y_arr)
-        if classes.size != 2:
-            raise ValueError("PolyagammaGPClassifier only supports binary classification.")
+        values, metadata = self._prepare_targets(y_arr)
         self._validate_options()
         from efgp_hip.ops import PointSet
         from kernels.squared_exponential import SquaredExponential
 
         dev = self._resolve_device()
         self._dev = dev
-        self.classes_ = classes
+        for key, value in metadata.items():
+            setattr(self, key, value)
         self.n_features_in_ = X_arr.shape[1]
         self._X_train_np_ = X_arr.copy()
         N, d = X_arr.shape
@@ -321,9 +322,9 @@ class PolyagammaGPClassifier:
         self.last_fit_stats = {"solves": []}
 
         xd = torch.as_tensor(X_arr).to(dev).contiguous()
-        targets = torch.as_tensor((y_arr == classes[1]).astype(np.float64)).to(dev).contiguous()
+        targets = torch.as_tensor(values).to(dev).contiguous()
         self._xd, self._targets = xd, targets
-        self._kappa = (targets - 0.5).contiguous()                      # y - 1/2 (b = 1)
+        self._start_likelihood(targets)                                 # self._kappa, and the likelihood's own state
         self._points = PointSet(xd)
         lo, hi = self._points.bounds()
         L = max(h_ - l_ for l_, h_ in zip(lo, hi))
@@ -338,7 +339,7 @@ class PolyagammaGPClassifier:
             and getattr(self, "kernel_", None) is not None and self._delta.device == dev
         if not keep:
             self.kernel_ = SquaredExponential(dimension=d, init_lengthscale=self.lengthscale_init, init_variance=self.variance_init)
-            self._delta = torch.full((N,), 0.25, dtype=torch.float64, device=dev)      # 0.25 b
+            self._delta = self._initial_delta(targets)                                  # 0.25 b
         self._mean = self._sigma_diag = None
         kernel = self.kernel_
         raw = kernel._gp_params_ref.raw
@@ -348,6 +349,7 @@ class PolyagammaGPClassifier:
         history = []
         mstep = None
         for outer in range(int(self.max_iter)):
+            self._refresh_likelihood()
             seed = None if rs is None else int(rs) + 1000 * outer
             spec = _Spectral(kernel, *spec_args)
             est = self._estep(spec, self.e_step_iters, seed, outer)
@@ -359,14 +361,18 @@ class PolyagammaGPClassifier:
                                     torch.tensor(0.0, dtype=raw.dtype)])
             optimizer.step()
             optimizer.zero_grad(set_to_none=True)
+            aux = self._step_auxiliary(outer)
             record = {"iter": float(outer), "lengthscale": float(kernel.lengthscale), "variance": float(kernel.variance),
                       "grad_lengthscale": g[0], "grad_variance": g[1], "e_residual": est["residual"], "e_cg_iters": est["cg_iters"],
-                      "m_cg_iters": float(mstep["cg_iters"]), "approx_accuracy": est["metric"]}
+                      "m_cg_iters": float(mstep["cg_iters"])}
+            record.update(aux)
+            record[self._history_key] = est["metric"]
             history.append(record)
             if self.verbose:
                 print(f"outer {outer:3d} lengthscale={record['lengthscale']:.5f} variance={record['variance']:.5f} "
-                      f"grad=({g[0]:+.3e}, {g[1]:+.3e}) approx_acc={est['metric']:.4f}")
+                      f"grad=({g[0]:+.3e}, {g[1]:+.3e}) {self._history_label}={est['metric']:.4f}")
 
+        self._refresh_likelihood()
         spec = _Spectral(kernel, *spec_args)
         self._spec = spec
         fin = self._estep(spec, self.final_e_step_iters, None if rs is None else int(rs) + 999_999, int(self.max_iter))
@@ -383,14 +389,15 @@ class PolyagammaGPClassifier:
         self.variance_ = float(kernel.variance)
         self.n_iter_ = self.max_iter
         self.training_metric_ = fin["metric"]
-        self.training_accuracy_ = fin["metric"]
+        setattr(self, self._training_attr, fin["metric"])
         self.m_step_gradient_ = mstep["grad"].detach().cpu().numpy() if mstep is not None else np.zeros(2)
         self.beta_mean_ = self._beta_mean.detach().cpu().numpy()
         self.history_ = history if self.store_history else []
         self.history_.append({"iter": float(self.max_iter), "lengthscale": self.lengthscale_, "variance": self.variance_,
                               "grad_lengthscale": float(self.m_step_gradient_[0]), "grad_variance": float(self.m_step_gradient_[1]),
-                              "e_residual": fin["residual"], "e_cg_iters": fin["cg_iters"], "m_cg_iters": float(beta_iters),
-                              "approx_accuracy": fin["metric"]})
+                              "e_residual": fin["residual"], "e_cg_iters": fin["cg_iters"], "m_cg_iters": float(beta_iters)})
+        self.history_[-1].update(self._final_record())
+        self.history_[-1][self._history_key] = fin["metric"]
         return self
 
     # -- prediction (pg_classifier.py:653-739, 1442-1508) -----------------------------------------------------------------------
@@ -451,7 +458,68 @@ class PolyagammaGPClassifier:
         else:
             xn = self._device_points(X_arr)
             mean, variance = self._latent_mean(xn), self._latent_variance(xn)
-        return approximate_logistic_gaussian_prob(mean, variance).cpu().numpy()
+        return self._response_mean(mean, variance).cpu().numpy()
+
+    # -- likelihood hooks: the ones a likelihood without parameters of its own does not need ------------------------------------
+    def _refresh_likelihood(self):
+        pass
+
+    def _step_auxiliary(self, outer):
+        return {}
+
+    def _final_record(self):
+        return {}
+
+
+class PolyagammaGPClassifier(_BasePolyagammaGPEstimator):
+    """Scikit-learn style PG-augmented GP classifier (Bernoulli likelihood, logistic link) on the HIP EFGP operators.
+
+    Constructor keywords and defaults are the reference's.  `fit` follows its loop: delta = b / 4; per outer iteration the
+    spectral state is rebuilt, one E-step (`e_step_iters` damped updates with the weighted operator built from delta as it
+    stands at the start) and one M-step gradient run, and Adam (maximize=True) steps the log hyper-parameters with the raw
+    gradient (g_l l, g_var var, 0); then a final E-step (seed random_state + 999_999) and the mean solve.
+
+    Solves: `use_exact_weighted_toeplitz_operator` True or False give the same matrix F* diag(delta) F up to `nufft_eps`, so
+    both run the fused weighted Toeplitz operator (efgp_cg_solve).
+
+    Probes: with `random_state` set, the probes are the reference's (drawn by torch.Generator on the host, seeds
+    random_state + 1000 outer + 17 (it + 1) for the E-step and + 10_000 for the M-step) and uploaded -- 2 J N doubles per
+    outer iteration (J = n_e_probes = n_m_probes = 10, N = 1e6: 160 MB of host generation and upload per iteration), so a
+    seeded fit equals the reference's.  With random_state=None the reference promises no stream: one seed per E-step /
+    M-step is drawn from torch's global generator and the +-1 probes are generated on the device by the counter hash of
+    efgp_rademacher_fill / efgp_nufft_type1_rademacher; they never exist in memory.
+
+    Supported: kernel "squared_exponential" (aliases "se", "rbf"), dtype float64, predictive_variance_method "exact", a
+    GPU device ("auto", "cuda", "cuda:k").  Others raise ValueError / NotImplementedError naming the option.
+
+    After `fit`, `last_fit_stats` lists every solve (step, outer iteration, solver entry, `fused`, CG count, rows).
+    """
+
+    _what = "the PG classifier"
+    _history_key, _history_label, _training_attr = "approx_accuracy", "approx_acc", "training_accuracy_"
+
+    def _prepare_targets(self, y_arr):
+        classes = np.unique(y_arr)
+        if classes.size != 2:
+            raise ValueError("PolyagammaGPClassifier only supports binary classification.")
+        return (y_arr == classes[1]).astype(np.float64), {"classes_": classes}
+
+    def _start_likelihood(self, targets):
+        self._kappa = (targets - 0.5).contiguous()                      # y - 1/2 (b = 1)
+
+    def _initial_delta(self, targets):
+        return torch.full((self._N,), 0.25, dtype=torch.float64, device=self._dev)
+
+    def _estep_pass(self, S, rho, probes, pseed):
+        from efgp_hip.ops import pg_estep_update
+        mean, sdiag, resid, correct = pg_estep_update(S, self._delta, self._targets, rho, probes=probes, seed=pseed)
+        residual = float(resid.item())
+        # the reference's metric is a float32 mean of the per-point hits (pg_classifier.py:129-138)
+        metric = float(np.float32(int(correct.item())) / np.float32(self._N))
+        return mean, sdiag, residual, metric
+
+    def _response_mean(self, mean, variance):
+        return approximate_logistic_gaussian_prob(mean, variance)
 
     def predict_proba(self, X):
         p1 = np.clip(self.predict_response_mean(X), 1e-8, 1.0 - 1e-8)
@@ -463,3 +531,164 @@ class PolyagammaGPClassifier:
 
     def score(self, X, y):
         return float(np.mean(self.predict(X) == np.asarray(y)))
+
+
+class PolyagammaGPNegativeBinomialRegressor(_BasePolyagammaGPEstimator):
+    """PG-augmented GP regressor for counts: y ~ NB(r, sigmoid(f)), r = `total_count`, on the HIP EFGP operators.
+
+    The fit loop is the classifier's with kappa = (y - r) / 2 and b = y + r.  With `learn_total_count=True`, log r is a float64
+    parameter kept on the host and stepped by its own Adam (maximize=True, lr `total_count_lr` or `lr`) every
+    `total_count_update_frequency`-th outer iteration, after the kernel's step, with the gradient taken from the E-step's
+    marginals at the r that E-step used:  d/dr = sum_n [digamma(y_n + r) - digamma(r) + E log sigmoid(-f_n)],  the expectation
+    by the `total_count_quadrature_nodes`-point Gauss-Hermite rule (efgp_pg_nb_total_count_grad, one scalar read back).  kappa
+    is refreshed in the strength rows only when r has changed.  The final E-step and the mean solve use the last r.
+
+    The training metric (efgp_pg_nb_estep_update) is the mean absolute error of the predicted mean count
+    r exp(mean + var / 2); `predict`, `predict_mean_count` and `predict_response_mean` return that mean count, `score` is R^2.
+    Supported options and refusals are the classifier's; at most 128 quadrature nodes when r is learnt.
+    """
+
+    _what = "the PG negative-binomial regressor"
+    _history_key, _history_label, _training_attr = "mean_count_mae", "count_mae", "training_mean_absolute_error_"
+
+    def __init__(self, *, total_count: float = 1.0, learn_total_count: bool = False, total_count_lr: float | None = None,
+                 total_count_update_frequency: int = 5, total_count_quadrature_nodes: int = 12,
+                 kernel: str = "squared_exponential", lengthscale_init: float = 0.3, variance_init: float = 1.0,
+                 max_iter: int = 50, e_step_iters: int = 1, final_e_step_iters: int = 1, e_step_tol: float = 1e-4, rho0: float = 0.7,
+                 gamma: float = 1e-3, lr: float = 0.05, n_e_probes: int = 10, n_m_probes: int = 10, cg_tol: float = 1e-6,
+                 nufft_eps: float = 1e-7, spectral_eps: float = 1e-4, trunc_eps: float = 1e-4, jitter: float = 1e-8,
+                 use_exact_weighted_toeplitz_operator: bool = True, reuse_e_probes: bool = True,
+                 prediction_batch_size: int | None = 64, predictive_variance_method: str = "exact",
+                 predictive_variance_probes: int = 16, predictive_variance_chebyshev_nodes: int = 7, warm_start: bool = False,
+                 random_state: int | None = None, device: str = "auto", dtype="float64", verbose: int = 0,
+                 store_history: bool = False):
+        super().__init__(kernel=kernel, lengthscale_init=lengthscale_init, variance_init=variance_init, max_iter=max_iter,
+                         e_step_iters=e_step_iters, final_e_step_iters=final_e_step_iters, e_step_tol=e_step_tol, rho0=rho0,
+                         gamma=gamma, lr=lr, n_e_probes=n_e_probes, n_m_probes=n_m_probes, cg_tol=cg_tol, nufft_eps=nufft_eps,
+                         spectral_eps=spectral_eps, trunc_eps=trunc_eps, jitter=jitter,
+                         use_exact_weighted_toeplitz_operator=use_exact_weighted_toeplitz_operator, reuse_e_probes=reuse_e_probes,
+                         prediction_batch_size=prediction_batch_size, predictive_variance_method=predictive_variance_method,
+                         predictive_variance_probes=predictive_variance_probes,
+                         predictive_variance_chebyshev_nodes=predictive_variance_chebyshev_nodes, warm_start=warm_start,
+                         random_state=random_state, device=device, dtype=dtype, verbose=verbose, store_history=store_history)
+        self.total_count = total_count
+        self.learn_total_count = learn_total_count
+        self.total_count_lr = total_count_lr
+        self.total_count_update_frequency = total_count_update_frequency
+        self.total_count_quadrature_nodes = total_count_quadrature_nodes
+
+    _MAX_QUADRATURE_NODES = 128          # efgp_pg_nb_total_count_grad
+
+    # -- likelihood (pg_classifier.py:142-171, 1558-1671) ------------------------------------------------------------------------
+    def _prepare_targets(self, y_arr):
+        if self.total_count <= 0:
+            raise ValueError("total_count must be positive.")
+        y = np.asarray(y_arr, dtype=np.float64)
+        if np.any(y < 0):
+            raise ValueError("Negative binomial targets must be nonnegative.")
+        if not np.isfinite(y).all() or not np.allclose(y, np.round(y)):
+            raise ValueError("Negative binomial targets must be integer-valued.")
+        if self.total_count_update_frequency <= 0:
+            raise ValueError("total_count_update_frequency must be positive.")
+        if self.total_count_quadrature_nodes <= 0:
+            raise ValueError("total_count_quadrature_nodes must be positive.")
+        if self.learn_total_count and self.total_count_quadrature_nodes > self._MAX_QUADRATURE_NODES:
+            raise ValueError(f"total_count_quadrature_nodes={self.total_count_quadrature_nodes}: at most "
+                             f"{self._MAX_QUADRATURE_NODES} nodes are supported when learn_total_count=True")
+        return np.round(y).astype(np.float64), {}
+
+    def _current_total_count(self):
+        raw = getattr(self, "_raw_total_count_", None)
+        return float(torch.exp(raw).detach().item()) if raw is not None else float(self.total_count)
+
+    def _start_likelihood(self, targets):
+        """log r as a host float64 parameter with its own Adam (kept under warm_start), the quadrature rule on the device, and
+        kappa = (y - r) / 2 at the starting r."""
+        dev = self._dev
+        if self.learn_total_count:
+            prev = getattr(self, "_raw_total_count_", None)
+            start = prev.detach().to(torch.float64) if (self.warm_start and prev is not None) \
+                else torch.tensor(math.log(float(self.total_count)), dtype=torch.float64)
+            self._raw_total_count_ = torch.nn.Parameter(start)
+            lr = self.lr if self.total_count_lr is None else self.total_count_lr
+            self._total_count_optimizer_ = torch.optim.Adam([self._raw_total_count_], lr=lr, maximize=True)
+            nodes, weights = _gauss_hermite_normal_rule(int(self.total_count_quadrature_nodes))
+            self._gh_nodes = torch.from_numpy(nodes.copy()).to(dev)
+            self._gh_weights = torch.from_numpy(weights.copy()).to(dev)
+            self._grad_r = torch.empty(1, dtype=torch.float64, device=dev)
+        else:
+            self._raw_total_count_ = self._total_count_optimizer_ = None
+        self._escalars = torch.empty(2, dtype=torch.float64, device=dev)       # [residual, sum |mean count - y|]
+        self._r = self._current_total_count()
+        self._kappa = (0.5 * (targets - self._r)).contiguous()
+        self._kappa_r = self._r
+
+    def _initial_delta(self, targets):
+        return 0.25 * (targets + self._r)
+
+    def _refresh_likelihood(self):
+        """kappa = (y - r) / 2 into _kappa and the E-step / M-step strength rows, when r has moved since they were written."""
+        if self._r == self._kappa_r:
+            return
+        torch.sub(self._targets, self._r, out=self._kappa).mul_(0.5)
+        self._zbuf_e[0].copy_(self._kappa)
+        self._zbuf_m[int(self.n_m_probes)].copy_(self._kappa)
+        self._kappa_r = self._r
+
+    def _estep_pass(self, S, rho, probes, pseed):
+        from efgp_hip.ops import pg_nb_estep_update
+        mean, sdiag, scalars = pg_nb_estep_update(S, self._delta, self._targets, self._r, rho, probes=probes, seed=pseed,
+                                                  out=self._escalars)
+        residual, abs_err = scalars.tolist()
+        return mean, sdiag, residual, abs_err / self._N
+
+    def _step_auxiliary(self, outer):
+        """The r gradient at the r of this iteration's E-step, from its marginals; an Adam step of log r on every
+        total_count_update_frequency-th iteration (pg_classifier.py:1625-1662)."""
+        record = {"total_count": self._r, "grad_total_count": 0.0, "total_count_updated": 0.0}
+        if not self.learn_total_count:
+            return record
+        from efgp_hip.ops import pg_nb_total_count_grad
+        grad = float(pg_nb_total_count_grad(self._targets, self._mean, self._sigma_diag, self._r, self._gh_nodes, self._gh_weights,
+                                            out=self._grad_r).item())
+        record["grad_total_count"] = grad
+        if (outer + 1) % int(self.total_count_update_frequency) == 0:
+            raw = self._raw_total_count_
+            raw.grad = (torch.tensor(grad, dtype=torch.float64) * torch.exp(raw)).detach()
+            self._total_count_optimizer_.step()
+            self._total_count_optimizer_.zero_grad(set_to_none=True)
+            self._r = self._current_total_count()
+            record["total_count"] = self._r
+            record["total_count_updated"] = 1.0
+        return record
+
+    def _final_record(self):
+        return {"total_count": self._r, "grad_total_count": 0.0, "total_count_updated": 0.0}
+
+    def fit(self, X, y):
+        super().fit(X, y)
+        self.total_count_ = self._r
+        self.shape_parameter_ = self._r
+        return self
+
+    # -- prediction ----------------------------------------------------------------------------------------------------------
+    def _response_mean(self, mean, variance):
+        return negative_binomial_gaussian_mean(mean, variance, total_count=self.total_count_)
+
+    def predict_mean_count(self, X):
+        return self.predict_response_mean(X)
+
+    def predict(self, X):
+        return self.predict_mean_count(X)
+
+    def score(self, X, y, sample_weight=None):
+        """R^2 of predict(X) against y (scikit-learn's RegressorMixin.score: 1.0 for a perfect fit of constant y, 0.0 for an
+        imperfect one)."""
+        y_true = np.asarray(y, dtype=np.float64).reshape(-1)
+        y_pred = np.asarray(self.predict(X), dtype=np.float64).reshape(-1)
+        w = np.ones_like(y_true) if sample_weight is None else np.asarray(sample_weight, dtype=np.float64).reshape(-1)
+        num = float(np.sum(w * (y_true - y_pred) ** 2))
+        den = float(np.sum(w * (y_true - np.average(y_true, weights=w)) ** 2))
+        if den == 0.0:
+            return 1.0 if num == 0.0 else 0.0
+        return 1.0 - num / den

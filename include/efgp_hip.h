@@ -367,7 +367,7 @@ int efgp_variance_rhs(int device, int dim, int64_t mtot, double h, const double*
 int efgp_variance_contract(int device, int dim, int64_t mtot, double h, const double* x_new, int64_t npts, const void* ws,
                            const void* gamma, double* out, void* stream);
 
-/* ---- Polya-Gamma classifier: the pointwise and M-scale passes around the weighted solves (pg_classifier.py) -----------------
+/* ---- Polya-Gamma estimators: the pointwise and M-scale passes around the weighted solves (pg_classifier.py) -----------------
  * efgp_pg_estep_update: one pass over the N points after the E-step's batched solve (:552-569, :252-257, :129-138):
  *     mean[n] = S[0, n];  sigma_diag[n] = (1/J) sum_j z[j, n] S[1 + j, n];
  *     c = sqrt(max(sigma_diag + mean^2, 1e-12));  Lambda = c > 1e-8 ? 0.5 b tanh(c/2) / max(c, 1e-12) : 0.25 b;
@@ -380,6 +380,22 @@ int efgp_variance_contract(int device, int dim, int64_t mtot, double h, const do
 int efgp_pg_estep_update(int device, int64_t npts, int nprobes, const double* s_rows, const double* probes, uint64_t seed,
                          const double* pg_b, const double* targets, double rho, double* delta, double* mean_out, double* sigma_diag_out,
                          double* residual_out, int64_t* correct_out, void* stream);
+/* efgp_pg_nb_estep_update: the same pass for the negative-binomial likelihood y ~ NB(r, sigmoid(f)) (:142-171), r = total_count > 0:
+ *     b = targets[n] + r is formed per point (no pg_b array);  mean, sigma_diag, Lambda, delta and *residual_out as above;
+ *     *abs_err_sum_out = sum_n |r exp(mean[n] + max(sigma_diag[n], 0) / 2) - targets[n]|   (the caller divides by N).
+ * residual_out and abs_err_sum_out are DEVICE pointers (either may be NULL).  The sum adds per-workgroup partials in a fixed
+ * order: deterministic. */
+int efgp_pg_nb_estep_update(int device, int64_t npts, int nprobes, const double* s_rows, const double* probes, uint64_t seed,
+                            const double* targets, double total_count, double rho, double* delta, double* mean_out,
+                            double* sigma_diag_out, double* residual_out, double* abs_err_sum_out, void* stream);
+/* efgp_pg_nb_total_count_grad: d/dr of the negative-binomial ELBO (:204-249), one DEVICE double:
+ *     *grad_out = sum_n [ digamma(targets[n] + r) - digamma(r)
+ *                         + sum_q weights[q] logsigmoid(-(mean[n] + sqrt(max(sigma_diag[n], 0)) nodes[q])) ];
+ * nodes, weights: the Gauss-Hermite rule for N(0, 1) (hermgauss(Q) scaled by sqrt(2) and 1/sqrt(pi)), 1 <= nnodes <= 128
+ * DEVICE doubles each.  Per-workgroup partials added in a fixed order: deterministic. */
+int efgp_pg_nb_total_count_grad(int device, int64_t npts, const double* targets, const double* mean, const double* sigma_diag,
+                                double total_count, int nnodes, const double* nodes, const double* weights, double* grad_out,
+                                void* stream);
 /* efgp_pg_weight_rows: out[j, n] = omega[n] z[j, n] for j < nrows (the rows whose type-1 transform is the M-step's
  * R = F*(omega z), :616); probes (nrows, N) or NULL for the counter-hash probes of `seed` as above. */
 int efgp_pg_weight_rows(int device, int64_t npts, int nrows, const double* probes, uint64_t seed, const double* omega, double* out,
