@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "spectral_weights.hpp"
 #include "toeplitz_cg.hpp"
 
 namespace efgp {
@@ -90,6 +91,15 @@ struct Args {
     double* lz_alpha;
     double* lz_beta;
     double* lz_norm2;
+    // fused mean solve (cg_herm48_kernel<0, true>, efgp_cg_solve_mean_fused): ws evaluated in the kernel from the built-in kernel's
+    // parameters (spectral_weights.hpp) and written to ws_out; the 48 x 48 spectrum made from the Toeplitz vector vsrc (L0 x L1)
+    // in the prologue and written to vhat_out
+    int wk_kind, wk_mtot;
+    double wk_nu, wk_ell, wk_c0, wk_h;
+    double2* ws_out;
+    const double2* vsrc;
+    int vL0, vL1;
+    double2* vhat_out;
 #ifdef EFGP_CG_STAMPS
     long long* stamps;       // diagnostic build only: cycles per phase class, accumulated by block 0
 #endif
@@ -1321,9 +1331,101 @@ __device__ __forceinline__ void exchange_6to8(double2 (&u)[6], double2 (&v)[8], 
     s64::load8_all<9>(rd, v);
     h64::dft8_out4(v);
 }
+
+// vhat[f0][f1] = factor * sum_l v[l] w48^(f0 l0 + f1 l1), natural order: the spectrum of the Toeplitz vector on this grid.  Lines in
+// the "8x6" layout (radix 6 on eight lanes, radix 8 on six), rows then columns, NT / 8 line slots, as many passes per dimension as
+// 48 lines need (512 threads: one; 256: two -- the same arithmetic per line either way).  LDS: [48][49] grid + [NT / 8][72] scratch.
+// KEEP: the result also stays in the grid, lds2[f0 * 49 + f1] (the fused mean solve loads its spectrum registers from there).
+template <int NT, bool KEEP>
+__device__ __forceinline__ void vhat48_lines(const double2* __restrict__ v, int L0, int L1, double factor, double2* __restrict__ vhat,
+                                             double2* lds2) {
+    constexpr int LD = 49, SLOTS = NT / 8, PASSES = (F + SLOTS - 1) / SLOTS, PER = (F * F + NT - 1) / NT;
+    double2* const buf = lds2;                       // [48][LD]
+    double2* const scr = lds2 + F * LD;              // [SLOTS lines][writer 9 j + value]
+    const int tid = threadIdx.x;
+    // every load of v in flight at once (one L2 round trip, not PER of them: 9 on 256 threads), the twiddles computed meanwhile
+    double2 xs[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int t = tid + k * NT, i0 = t / F, i1 = t - i0 * F;
+        xs[k] = (t < F * F && i0 < L0 && i1 < L1) ? v[i0 * L1 + i1] : make_double2(0.0, 0.0);
+    }
+    const int slot = tid >> 3, j = tid & 7;
+    double2 tw[5];
+#pragma unroll
+    for (int t = 1; t < 6; ++t) {
+        double sn, cs;
+        sincospi(-(double)(j * t) / 24.0, &sn, &cs);      // exp(-2 pi i j t / 48)
+        tw[t - 1] = make_double2(cs, sn);
+    }
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int t = tid + k * NT, i0 = t / F, i1 = t - i0 * F;
+        double2 x = xs[k];
+        if (i0 < L0 && i1 < L1) {
+            x.x *= factor;
+            x.y *= factor;
+        }
+        if (t < F * F) buf[i0 * LD + i1] = x;
+    }
+    double2* const wr = scr + slot * LX + 9 * j;
+    const double2* const rd = scr + slot * LX + j;
+    double2 u6[6], x8[8];
+    __syncthreads();
+    // dimension 1 (contiguous): line = row
+#pragma unroll
+    for (int ps = 0; ps < PASSES; ++ps) {
+        const int line = slot + ps * SLOTS;
+        const bool act = line < F;
+#pragma unroll
+        for (int t = 0; t < 6; ++t) u6[t] = act ? buf[line * LD + j + 8 * t] : make_double2(0.0, 0.0);
+        dft6(u6);
+#pragma unroll
+        for (int t = 1; t < 6; ++t) u6[t] = cmulp(u6[t], tw[t - 1]);
+        wave_sync();
+#pragma unroll
+        for (int t = 0; t < 6; ++t) wr[t] = u6[t];
+        wave_sync();
+        s64::load8_all<9>(rd, x8);
+        dft_fwd<8>(x8);
+        if (act && j < 6) {
+#pragma unroll
+            for (int t = 0; t < 8; ++t) buf[line * LD + j + 6 * t] = x8[t];
+        }
+    }
+    __syncthreads();
+    // dimension 0: line = column (a line reads and rewrites its own column only)
+#pragma unroll
+    for (int ps = 0; ps < PASSES; ++ps) {
+        const int line = slot + ps * SLOTS;
+        const bool act = line < F;
+#pragma unroll
+        for (int t = 0; t < 6; ++t) u6[t] = act ? buf[(j + 8 * t) * LD + line] : make_double2(0.0, 0.0);
+        dft6(u6);
+#pragma unroll
+        for (int t = 1; t < 6; ++t) u6[t] = cmulp(u6[t], tw[t - 1]);
+        wave_sync();
+#pragma unroll
+        for (int t = 0; t < 6; ++t) wr[t] = u6[t];
+        wave_sync();
+        s64::load8_all<9>(rd, x8);
+        dft_fwd<8>(x8);
+        if (act && j < 6) {
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                vhat[(j + 6 * t) * F + line] = x8[t];
+                if (KEEP) buf[(j + 6 * t) * LD + line] = x8[t];
+            }
+        }
+    }
+}
 }  // namespace h48
 
-template <int VARIANT>
+// FUSED (the fit's cold-start mean solve, efgp_cg_solve_mean_fused): the 48 x 48 spectrum is made in the prologue from the Toeplitz
+// vector (vhat48_lines on the 256 threads, in LDS the iteration reuses afterwards) and ws is evaluated from the built-in kernel's
+// parameters (spectral_weights.hpp) by the row lanes that hold the modes; both are written out for later users.  The iteration is
+// the same code.
+template <int VARIANT, bool FUSED = false>
 __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
     using namespace h48;
     using h64::block_sum_h;
@@ -1363,15 +1465,22 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
         twc[t - 1] = a.g.tw[0][jc * t];
     }
     // real spectrum of the centred lags, halved (the unpacking of D averages two terms): vhat = w^((n-1)(f0+f1)) S
+    if (FUSED) {
+        vhat48_lines<kThreadsH, true>(a.vsrc, a.vL0, a.vL1, 1.0 / 2304.0, a.vhat_out, lds2);
+        __syncthreads();
+    }
+    const double2* const vh = FUSED ? lds2 : a.vhat;
+    constexpr int LV = FUSED ? 49 : F;                    // pitch of vh: the prologue's grid, or the operator's spectrum
     double sa[6], sb[6];
 #pragma unroll
     for (int t = 0; t < 6; ++t) {
         const int f0 = jc + 8 * t;
-        const double2 va = a.vhat[f0 * F + qs], vb = a.vhat[f0 * F + qs + HF];
+        const double2 va = vh[f0 * LV + qs], vb = vh[f0 * LV + qs + HF];
         const double2 wa = a.g.tw[0][((n - 1) * (f0 + qs)) % F], wb = a.g.tw[0][((n - 1) * (f0 + qs + HF)) % F];
         sa[t] = 0.5 * (va.x * wa.x + va.y * wa.y);
         sb[t] = -0.5 * (vb.x * wb.x + vb.y * wb.y);      // sign: conjugation in front of the inverse transform
     }
+    if (FUSED) __syncthreads();                           // the iteration's G / T / scratch alias the prologue's grid
     const bool z6_ok = jc > 0;                            // row 12 - jc exists
     const int jr = col6 ? jc : 0;                         // rows this lane packs in B (the lanes jc >= 6 only take part in the radix-6 stages)
 
@@ -1389,7 +1498,15 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
         ok[s] = vec_role && k0 <= h && k1 <= h && -k1 <= h;
         idx[s] = ok[s] ? (k0 + h) * n + (k1 + h) : 0;
         double ws_im = 0.0;
-        if (ok[s]) {
+        if (ok[s] && FUSED) {
+            // ws = sqrt(S h^d) is real and even by construction: node idx and its mirror M - 1 - idx get the same value
+            xv[s] = make_double2(0.0, 0.0);
+            const double2 w = make_double2(spectral_weight_at(a.wk_kind, a.g.d, a.wk_nu, a.wk_ell, a.wk_c0, a.wk_h, a.wk_mtot, idx[s]), 0.0);
+            a.ws_out[idx[s]] = w;
+            a.ws_out[M - 1 - idx[s]] = w;
+            wsr[s] = w.x;
+            dg[s] = jacobi_entry(a, w, idx[s]);
+        } else if (ok[s]) {
             xv[s] = a.zero_x0 ? make_double2(0.0, 0.0) : a.x0[base + idx[s]];
             const double2 w = a.ws[idx[s]], wm = a.ws[M - 1 - idx[s]];
             wsr[s] = w.x;
@@ -1838,70 +1955,10 @@ __global__ __launch_bounds__(kThreads) void toeplitz_vhat_2d64_kernel(const doub
     toeplitz_vhat_2d64_body(v, L0, L1, factor, vhat, lds2);
 }
 
-// The same for the 48 x 48 circulant grid of cg_herm48_kernel (round 4): vhat[f0][f1] = factor * sum_l v[l] w48^(f0 l0 + f1 l1).
-// Lines as in that kernel: 8 adjacent lanes, "8x6" (radix 6 on eight lanes, radix 8 on six), rows then columns, 64 line slots.
+// The same for the 48 x 48 circulant grid of cg_herm48_kernel (round 4): vhat48_lines above on 512 threads (64 line slots, one pass).
 __device__ __forceinline__ void toeplitz_vhat_2d48_body(const double2* __restrict__ v, int L0, int L1, double factor,
                                                         double2* __restrict__ vhat, double2* lds2) {
-    constexpr int F = 48, LD = 49, LX = 72;
-    double2* const buf = lds2;                       // [48][LD]
-    double2* const scr = lds2 + F * LD;              // [64 lines][writer 9 j + value]
-    const int tid = threadIdx.x;
-    for (int t = tid; t < F * F; t += kThreads) {
-        const int i0 = t / F, i1 = t - i0 * F;
-        double2 x = make_double2(0.0, 0.0);
-        if (i0 < L0 && i1 < L1) {
-            x = v[i0 * L1 + i1];
-            x.x *= factor;
-            x.y *= factor;
-        }
-        buf[i0 * LD + i1] = x;
-    }
-    const int line = tid >> 3, j = tid & 7;
-    const bool act = line < F;
-    double2 tw[5];
-#pragma unroll
-    for (int t = 1; t < 6; ++t) {
-        double sn, cs;
-        sincospi(-(double)(j * t) / 24.0, &sn, &cs);      // exp(-2 pi i j t / 48)
-        tw[t - 1] = make_double2(cs, sn);
-    }
-    double2* const wr = scr + line * LX + 9 * j;
-    const double2* const rd = scr + line * LX + j;
-    double2 u6[6], x8[8];
-    __syncthreads();
-    // dimension 1 (contiguous): line = row
-#pragma unroll
-    for (int t = 0; t < 6; ++t) u6[t] = act ? buf[line * LD + j + 8 * t] : make_double2(0.0, 0.0);
-    h48::dft6(u6);
-#pragma unroll
-    for (int t = 1; t < 6; ++t) u6[t] = cmulp(u6[t], tw[t - 1]);
-    h48::wave_sync();
-#pragma unroll
-    for (int t = 0; t < 6; ++t) wr[t] = u6[t];
-    h48::wave_sync();
-    s64::load8_all<9>(rd, x8);
-    dft_fwd<8>(x8);
-    if (act && j < 6) {
-#pragma unroll
-        for (int t = 0; t < 8; ++t) buf[line * LD + j + 6 * t] = x8[t];
-    }
-    __syncthreads();
-    // dimension 0: line = column
-#pragma unroll
-    for (int t = 0; t < 6; ++t) u6[t] = act ? buf[(j + 8 * t) * LD + line] : make_double2(0.0, 0.0);
-    h48::dft6(u6);
-#pragma unroll
-    for (int t = 1; t < 6; ++t) u6[t] = cmulp(u6[t], tw[t - 1]);
-    h48::wave_sync();
-#pragma unroll
-    for (int t = 0; t < 6; ++t) wr[t] = u6[t];
-    h48::wave_sync();
-    s64::load8_all<9>(rd, x8);
-    dft_fwd<8>(x8);
-    if (act && j < 6) {
-#pragma unroll
-        for (int t = 0; t < 8; ++t) vhat[(j + 6 * t) * F + line] = x8[t];
-    }
+    h48::vhat48_lines<kThreads, false>(v, L0, L1, factor, vhat, lds2);
 }
 // both spectra of an operator in ONE launch (two workgroups on two CUs): a dependent launch costs more than either transform
 __global__ __launch_bounds__(kThreads) void toeplitz_vhat_pair_kernel(const double2* __restrict__ v, int L0, int L1, double factor64,
@@ -2264,9 +2321,12 @@ int persistent_cg_launch(const ToepGeom& tg, const double2* const* twiddles, con
                          const double* diag, double sigmasq, int variant, double tol, int early_stop, int batched,
                          int max_iter, const double2* b, double2* x, int rows, int* d_iters, hipStream_t stream,
                          const double* diag_scale, int b_times_ws, int zero_x0, const LanczosOut* lz, int hermitian,
-                         const Herm48Operands* h48, const double2* x0) {
+                         const Herm48Operands* h48, const double2* x0, const MeanFusedOperands* fuse) {
     using namespace pcg;
     Args a;
+    a.ws_out = nullptr;
+    a.vsrc = nullptr;
+    a.vhat_out = nullptr;
     Geom& g = a.g;
     g.d = tg.d;
     for (int i = 0; i < 3; ++i) {
@@ -2461,7 +2521,41 @@ int persistent_cg_launch(const ToepGeom& tg, const double2* const* twiddles, con
     const bool herm64 = fast64 && hermitian && !lz && (g.n[0] & 1) && g.n[0] <= 31 && std::getenv("EFGP_NO_CG_HERM") == nullptr;
     // blocks of up to 23 x 23 modes: the smallest circulant grid, 48 x 48 (the operator holds a second spectrum for it)
     const bool herm48 = herm64 && h48 != nullptr && h48->vhat != nullptr && g.n[0] <= 23 && std::getenv("EFGP_NO_CG48") == nullptr;
-    if (herm48) {
+    if (fuse != nullptr && !(herm48 && variant == 0 && rows == 1 && zero_x0 && b_times_ws && !diag)) {
+        set_error("fused mean solve: the system is not a cold-start 48 x 48 Hermitian mean solve");
+        return EFGP_EUNSUPPORTED;
+    }
+    if (herm48 && fuse != nullptr) {
+        // the prologue's grid + 32 line slots of scratch outgrow the iteration's 53 KB; one workgroup, so the extra LDS costs nothing
+        constexpr size_t lds_f = (size_t)(48 * 49 + (h48::kThreadsH / 8) * h48::LX) * sizeof(double2);
+        static_assert(48 * 49 + (h48::kThreadsH / 8) * h48::LX >= h48::kLdsElems, "the fused prologue's LDS covers the iteration's");
+        bool& attr_f = per_device_flag("cg_herm48_fused");
+        if (!attr_f) {
+            hipError_t e2 = hipFuncSetAttribute((const void*)cg_herm48_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f);
+            if (e2 != hipSuccess) {
+                set_error("fused mean solve (48x48): hipFuncSetAttribute failed: %s", hipGetErrorString(e2));
+                return EFGP_EHIP;
+            }
+            attr_f = true;
+        }
+        a.vhat = nullptr;
+        a.ws = nullptr;
+        a.wk_kind = fuse->kind;
+        a.wk_mtot = fuse->mtot;
+        a.wk_nu = fuse->nu;
+        a.wk_ell = fuse->ell;
+        a.wk_c0 = fuse->c0;
+        a.wk_h = fuse->h;
+        a.ws_out = fuse->ws_out;
+        a.vsrc = fuse->v;
+        a.vL0 = fuse->L0;
+        a.vL1 = fuse->L1;
+        a.vhat_out = fuse->vhat48_out;
+        g.F[0] = g.F[1] = 48;
+        g.tw[0] = g.tw[1] = h48->tw;
+        KernelTimer timer("cg_solve", stream);
+        hipLaunchKernelGGL((cg_herm48_kernel<0, true>), dim3(1), dim3(h48::kThreadsH), lds_f, stream, a);
+    } else if (herm48) {
         bool& attr_h = per_device_flag("cg_herm48");
         const size_t lds_h = (size_t)h48::kLdsElems * sizeof(double2);
         if (!attr_h) {

@@ -2427,6 +2427,13 @@ struct efgp_toeplitz_s {
     // circulant grid, 48 x 48 (cg_herm48_kernel, round 4), from a third spectrum made in the same launch as the 64 x 64 one
     double2* vhat48 = nullptr;
     Herm48Operands h48 = {nullptr, nullptr};
+    // deferred spectra (efgp_toeplitz_create_ex with EFGP_TOEPLITZ_DEFER_SPECTRA): creation launches nothing.  The fused mean solve
+    // (efgp_cg_solve_mean_fused) makes vhat48 in its prologue; the first other use makes what is still missing (ensure_deferred_spectra)
+    // from the caller's Toeplitz vector, which is not copied: the caller keeps it alive and unchanged while the operator lives
+    bool pair_pending = false;   // the 64 x 64 spectrum (pair_target: vhat, or vhat_cg of the embedding) is still to be made
+    bool vhat48_ready = true;
+    const double2* v_ref = nullptr;
+    double2* pair_target = nullptr;
 };
 
 // exp(-2 pi i q / n), q < n, on the device (cached per context)
@@ -2451,8 +2458,25 @@ static double2* twiddle_table_for(DeviceCtx* ctx, int64_t n, hipStream_t stream)
     return dtw;
 }
 
-// geometry, twiddles and spectrum the single-launch CG kernels use for this operator
-static void cg_operands(const efgp_toeplitz_s* op, const ToepGeom** g, const double2* const** tw, const double2** vhat) {
+// a deferred operator's spectra, made on first use by any entry other than the fused mean solve: the 64 x 64 one, and the 48 x 48
+// one in the same launch unless the fused solve has made it.  On the caller's stream: its DeviceGuard has handed the context over
+// from the stream the operator was made on (stream_handover), as for the deferred reference-grid spectrum below.
+static int ensure_deferred_spectra(efgp_toeplitz_s* op, hipStream_t stream) {
+    if (!op->pair_pending) return EFGP_OK;
+    const int L0 = (int)op->Ls[0], L1 = (int)op->Ls[1];
+    const int rc = op->vhat48_ready ? toeplitz_vhat_fused_launch(op->v_ref, L0, L1, 1.0 / 4096.0, op->pair_target, stream)
+                                    : toeplitz_vhat_pair_launch(op->v_ref, L0, L1, op->pair_target, op->vhat48, stream);
+    if (rc != EFGP_OK) return rc;
+    op->pair_pending = false;
+    op->vhat48_ready = true;
+    op->v_ref = nullptr;
+    return EFGP_OK;
+}
+
+// geometry, twiddles and spectrum the single-launch CG kernels use for this operator (made first if it was deferred)
+static int cg_operands(efgp_toeplitz_s* op, hipStream_t stream, const ToepGeom** g, const double2* const** tw, const double2** vhat) {
+    const int rc = ensure_deferred_spectra(op, stream);
+    if (rc != EFGP_OK) return rc;
     if (op->cg64) {
         *g = &op->g_cg;
         *tw = (const double2* const*)op->tw_cg;
@@ -2462,6 +2486,7 @@ static void cg_operands(const efgp_toeplitz_s* op, const ToepGeom** g, const dou
         *tw = (const double2* const*)op->tw;
         *vhat = op->vhat;
     }
+    return EFGP_OK;
 }
 
 namespace efgp {
@@ -2474,6 +2499,8 @@ static dim3 grid_for(int64_t work, int rows, int threads, int cap = 1024) {
 // vhat = FFT(zero-padded v) / Ftot on the reference's grid, made on first use when the operator was created with a smaller
 // cooperative grid (efgp_toeplitz_create)
 static int ensure_reference_spectrum(efgp_toeplitz_s* op, hipStream_t stream) {
+    const int rcd = ensure_deferred_spectra(op, stream);
+    if (rcd != EFGP_OK) return rcd;
     if (op->vhat_ready) return EFGP_OK;
     ToepGeom gv = op->g;
     gv.M = 1;
@@ -2535,7 +2562,13 @@ extern "C" {
 
 int efgp_toeplitz_create(efgp_toeplitz_t** op_out, int device, int dim, const int64_t* Ls, const void* v,
                          int force_pow2, void* stream_) {
+    return efgp_toeplitz_create_ex(op_out, device, dim, Ls, v, force_pow2, 0, stream_);
+}
+
+int efgp_toeplitz_create_ex(efgp_toeplitz_t** op_out, int device, int dim, const int64_t* Ls, const void* v, int force_pow2, int flags,
+                            void* stream_) {
     EFGP_REQUIRE(op_out && Ls && v, "efgp_toeplitz_create: null argument");
+    EFGP_REQUIRE((flags & ~EFGP_TOEPLITZ_DEFER_SPECTRA) == 0, "efgp_toeplitz_create_ex: unknown flags %d", flags);
     EFGP_REQUIRE(dim >= 1 && dim <= 3, "efgp_toeplitz_create: dim must be 1, 2 or 3 (got %d)", dim);
     for (int a = 0; a < dim; ++a) EFGP_REQUIRE(Ls[a] >= 1, "efgp_toeplitz_create: Ls[%d] < 1", a);
     DeviceCtx* ctx = device_ctx(device);
@@ -2579,6 +2612,8 @@ int efgp_toeplitz_create(efgp_toeplitz_t** op_out, int device, int dim, const in
         if (op->vhat48) op->h48.tw = tw48;
     }
     bool made48 = false;
+    // deferred: the launch that would make the 64 x 64 and 48 x 48 spectra together is left to the fused mean solve and to first use
+    const bool defer_pair = (flags & EFGP_TOEPLITZ_DEFER_SPECTRA) && op->vhat48 != nullptr && std::getenv("EFGP_NO_DEFER_SPECTRA") == nullptr;
     // 2-D grids of the cooperative solve (128..512 per axis): when a smaller cooperative grid exists (made below) nothing on the
     // fit path reads the reference grid's spectrum -- keep a copy of v and make it on first use
     bool defer_ref = dim == 2 && std::getenv("EFGP_NO_COOP_SMALL") == nullptr && std::getenv("EFGP_EAGER_REF_SPECTRUM") == nullptr;
@@ -2600,7 +2635,11 @@ int efgp_toeplitz_create(efgp_toeplitz_t** op_out, int device, int dim, const in
     if (defer_ref) {
         // nothing now
     } else if (toeplitz_vhat_fused_eligible(op->g)) {
-        if (op->vhat48) {
+        if (op->vhat48 && defer_pair) {
+            op->pair_pending = true;
+            op->pair_target = op->vhat;
+            made48 = true;
+        } else if (op->vhat48) {
             rc = toeplitz_vhat_pair_launch((const double2*)v, (int)op->Ls[0], (int)op->Ls[1], op->vhat, op->vhat48, stream);
             made48 = rc == EFGP_OK;
         } else {
@@ -2742,7 +2781,11 @@ int efgp_toeplitz_create(efgp_toeplitz_t** op_out, int device, int dim, const in
             if (ok) op->tw_cg[0] = op->tw_cg[1] = (double2*)ctx->twiddles[64];
         }
         if (ok) {
-            if (op->vhat48 && !made48) {
+            if (op->vhat48 && !made48 && defer_pair) {
+                op->pair_pending = true;
+                op->pair_target = op->vhat_cg;
+                made48 = true;
+            } else if (op->vhat48 && !made48) {
                 ok = toeplitz_vhat_pair_launch((const double2*)v, (int)op->Ls[0], (int)op->Ls[1], op->vhat_cg, op->vhat48, stream) == EFGP_OK;
                 made48 = ok;
             } else {
@@ -2756,6 +2799,10 @@ int efgp_toeplitz_create(efgp_toeplitz_t** op_out, int device, int dim, const in
             if (op->vhat_cg) pool_free(ctx, op->vhat_cg, (size_t)4096 * sizeof(double2));
             op->vhat_cg = nullptr;
         }
+    }
+    if (op->pair_pending) {
+        op->v_ref = (const double2*)v;
+        op->vhat48_ready = false;
     }
     if (op->vhat48 && made48) {
         op->h48.vhat = op->vhat48;
@@ -2840,7 +2887,7 @@ int efgp_toeplitz_apply_scaled(efgp_toeplitz_t* op, const void* x, int x_is_real
     const ToepGeom* gq;
     const double2* const* twq;
     const double2* vq;
-    cg_operands(op, &gq, &twq, &vq);
+    if (const int rc_ops = cg_operands(op, stream, &gq, &twq, &vq)) return rc_ops;
     if (toeplitz_apply_fused_eligible(*gq))
         return toeplitz_apply_fused_launch(*gq, twq[0], vq, (const double2*)pre, (const double2*)post, x, x_is_real, (double2*)y, nbatch,
                                            stream);
@@ -2873,7 +2920,7 @@ int efgp_internal_apply_scaled(efgp_toeplitz_s* op, const void* x, int x_is_real
     const ToepGeom* gq;
     const double2* const* twq;
     const double2* vq;
-    cg_operands(op, &gq, &twq, &vq);
+    if (const int rc_ops = cg_operands(op, stream, &gq, &twq, &vq)) return rc_ops;
     if (!toeplitz_apply_fused_eligible(*gq)) return EFGP_EUNSUPPORTED;
     return toeplitz_apply_fused_launch(*gq, twq[0], vq, (const double2*)pre, (const double2*)post, x, x_is_real, (double2*)y, nbatch, stream,
                                        pre_stride);
@@ -2892,7 +2939,7 @@ int efgp_internal_cg_single_launch(efgp_toeplitz_s* op, const void* ws, double s
     const ToepGeom* gq;
     const double2* const* twq;
     const double2* vq;
-    cg_operands(op, &gq, &twq, &vq);
+    if (const int rc_ops = cg_operands(op, stream, &gq, &twq, &vq)) return rc_ops;
     return persistent_cg_launch(*gq, twq, vq, (const double2*)ws, diag, sigmasq, variant, tol, early_stop, batched_semantics, max_iter,
                                 (const double2*)b, (double2*)x, nbatch, row_iters_dev, stream, diag ? nullptr : diag_scale, b_times_ws, zero_x0,
                                 nullptr, hermitian, op->h48.vhat ? &op->h48 : nullptr, (const double2*)x0);
@@ -3151,7 +3198,7 @@ static int cg_solve_impl(efgp_toeplitz_t* op, const void* ws, double sigmasq, in
             const ToepGeom* gq;
             const double2* const* twq;
             const double2* vq;
-            cg_operands(op, &gq, &twq, &vq);
+            if (const int rc_ops = cg_operands(op, stream, &gq, &twq, &vq)) return rc_ops;
             rc = persistent_cg_launch(*gq, twq, vq, (const double2*)ws, precond_diag, sigmasq,
                                       variant, tol, early_stop, batched_semantics, max_iter, (const double2*)b, (double2*)x,
                                       nbatch, d_iters, stream);
@@ -3662,7 +3709,7 @@ static int cg_solve_async_impl(efgp_toeplitz_t* op, const void* ws, double sigma
     const ToepGeom* gq;
     const double2* const* twq;
     const double2* vq;
-    cg_operands(op, &gq, &twq, &vq);
+    if (const int rc_ops = cg_operands(op, stream, &gq, &twq, &vq)) return rc_ops;
     return persistent_cg_launch(*gq, twq, vq, (const double2*)ws, precond_diag, sigmasq,
                                 variant, tol, early_stop, batched_semantics, max_iter, (const double2*)b, (double2*)x, nbatch,
                                 row_iters_dev, stream, nullptr, 0, zero_x0, nullptr, hermitian, op->h48.vhat ? &op->h48 : nullptr);
@@ -3684,7 +3731,7 @@ int efgp_lanczos(efgp_toeplitz_t* op, const void* ws, double sigmasq, int varian
     const ToepGeom* gq;
     const double2* const* twq;
     const double2* vq;
-    cg_operands(op, &gq, &twq, &vq);
+    if (const int rc_ops = cg_operands(op, stream, &gq, &twq, &vq)) return rc_ops;
     return persistent_cg_launch(*gq, twq, vq, (const double2*)ws, nullptr, sigmasq, variant, 0.0, 0,
                                 1, steps, (const double2*)z, nullptr, nprobes, steps_taken_dev, stream, nullptr, 0, 1, &lz);
 }
@@ -3711,11 +3758,36 @@ int efgp_cg_solve_mean_async(efgp_toeplitz_t* op, const void* ws, double sigmasq
     const ToepGeom* gq;
     const double2* const* twq;
     const double2* vq;
-    cg_operands(op, &gq, &twq, &vq);
+    if (const int rc_ops = cg_operands(op, stream, &gq, &twq, &vq)) return rc_ops;
     return persistent_cg_launch(*gq, twq, vq, (const double2*)ws, nullptr, sigmasq, 0, tol,
                                 early_stop, 0, max_iter, (const double2*)fy, (double2*)x, 1, iters_dev, stream, diag_scale_dev,
                                 1, 1, nullptr, /*hermitian: F*y of a real y, Toeplitz vector of real weights*/ 1,
                                 op->h48.vhat ? &op->h48 : nullptr);
+}
+
+int efgp_cg_solve_mean_fused(efgp_toeplitz_t* op, int kind, double nu, double lengthscale, double c0, double h, int mtot, void* ws_out,
+                             double sigmasq, const double* diag_scale_dev, const void* fy, void* x, double tol, int max_iter, int early_stop,
+                             int* iters_dev, void* stream_) {
+    EFGP_REQUIRE(op && ws_out && fy && x && iters_dev, "efgp_cg_solve_mean_fused: null argument");
+    EFGP_REQUIRE(kind == 0 || kind == 1, "efgp_cg_solve_mean_fused: kernel kind %d not built in", kind);
+    // only an operator whose 48 x 48 spectrum is still to be made (efgp_toeplitz_create_ex, deferred) on a block of mtot^2 modes
+    if (!op->pair_pending || op->vhat48_ready || op->h48.vhat == nullptr || !op->persistent_ok || op->g.d != 2 || op->g.n[0] != mtot ||
+        op->g.n[1] != mtot || std::getenv("EFGP_NO_PERSISTENT_CG") != nullptr || std::getenv("EFGP_NO_CG_FUSED_MEAN") != nullptr) {
+        set_error("efgp_cg_solve_mean_fused: the operator is not a deferred 48 x 48 Hermitian one of this grid");
+        return EFGP_EUNSUPPORTED;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    DeviceGuard guard(op->device, (hipStream_t)stream_);
+    if (max_iter <= 0) max_iter = (int)std::min<int64_t>(2 * op->g.M, 2000000000);
+    KernelTimer timer("cg_persistent", stream);
+    const ToepGeom* gq = op->cg64 ? &op->g_cg : &op->g;
+    const double2* const* twq = (const double2* const*)(op->cg64 ? op->tw_cg : op->tw);
+    const MeanFusedOperands fuse{kind, mtot, nu, lengthscale, c0, h, (double2*)ws_out, op->v_ref, (int)op->Ls[0], (int)op->Ls[1], op->vhat48};
+    const int rc = persistent_cg_launch(*gq, twq, nullptr, (const double2*)ws_out, nullptr, sigmasq, 0, tol, early_stop, 0, max_iter,
+                                        (const double2*)fy, (double2*)x, 1, iters_dev, stream, diag_scale_dev, 1, 1, nullptr, 1, &op->h48,
+                                        nullptr, &fuse);
+    if (rc == EFGP_OK) op->vhat48_ready = true;        // the 64 x 64 spectrum stays deferred: nothing on the fit path reads it
+    return rc;
 }
 
 int efgp_vdot_real(int device, const void* a, int a_is_complex, const void* b, int b_is_complex, int64_t count,

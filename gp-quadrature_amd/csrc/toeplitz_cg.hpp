@@ -29,6 +29,18 @@ struct Herm48Operands {
     const double2* tw;
 };
 
+// the fit's cold-start mean solve with its set-up folded in (efgp_cg_solve_mean_fused): the built-in kernel's parameters for the
+// weights (kind 0 SE, 1 Matern; spectral_weights.hpp) and where they go, the Toeplitz vector (L0 x L1) whose 48 x 48 spectrum the
+// kernel makes and where that goes
+struct MeanFusedOperands {
+    int kind, mtot;
+    double nu, ell, c0, h;
+    double2* ws_out;
+    const double2* v;
+    int L0, L1;
+    double2* vhat48_out;
+};
+
 // single-launch CG with the FFT in LDS (cg_persistent.hip)
 bool persistent_cg_eligible(const ToepGeom& g);
 int persistent_cg_launch(const ToepGeom& g, const double2* const* twiddles, const double2* vhat, const double2* ws,
@@ -37,7 +49,8 @@ int persistent_cg_launch(const ToepGeom& g, const double2* const* twiddles, cons
                          const double* diag_scale = nullptr, int b_times_ws = 0, int zero_x0 = 0, const LanczosOut* lz = nullptr,
                          int hermitian = 0 /* b, x0 and the Toeplitz vector are coefficient arrays of real functions */,
                          const Herm48Operands* h48 = nullptr /* 2-D blocks <= 23 x 23: Hermitian solves run on the 48 x 48 grid */,
-                         const double2* x0 = nullptr /* start vectors when they are not in x (read before x is written) */);
+                         const double2* x0 = nullptr /* start vectors when they are not in x (read before x is written) */,
+                         const MeanFusedOperands* fuse = nullptr /* 48 x 48 Hermitian mean solve only: ws and the spectrum made in the kernel */);
 
 // spectrum of the Toeplitz vector on the 64 x 64 circulant grid in one launch (cg_persistent.hip)
 bool toeplitz_vhat_fused_eligible(const ToepGeom& g);

@@ -10,6 +10,7 @@
 
 #include "common.hpp"
 #include "line_fft.hpp"
+#include "spectral_weights.hpp"
 #include "toeplitz_cg.hpp"
 
 namespace efgp {
@@ -142,28 +143,18 @@ __global__ __launch_bounds__(256) void spectral_weights_kernel(int kind, int dim
                                                                int mtot, int64_t M, double2* __restrict__ ws, double2* __restrict__ dprime) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= M) return;
-    const int m = (mtot - 1) / 2;
-    int64_t rem = t;
-    double q = 0.0;
-    for (int a = dim - 1; a >= 0; --a) {
-        const double xa = (double)((int)(rem % mtot) - m) * h;
-        rem /= mtot;
-        q += xa * xa;
-    }
-    const double two_pi = 6.283185307179586476925286766559, pi = 3.14159265358979323846264338327950288;
-    double hd = h;
-    for (int a = 1; a < dim; ++a) hd *= h;
-    double S, d_ell;
-    if (kind == 0) {
-        S = c0 * exp(-(two_pi * two_pi) * (ell * ell) * q / 2);
-        d_ell = S * (dim / ell - (two_pi * two_pi) * ell * q);
-    } else {
-        const double den = 2 * nu / (ell * ell) + (4 * pi * pi) * q;
-        S = c0 * pow(den, -(nu + dim / 2.0));
-        d_ell = S * (-2 * nu / ell + (-(nu + dim / 2.0)) * (-4 * nu / (ell * ell * ell)) / den);
-    }
+    double S, q, hd;
+    spectral_density_at(kind, dim, nu, ell, c0, h, mtot, t, S, q, hd);      // spectral_weights.hpp (shared with the fused mean solve)
     ws[t] = make_double2(sqrt(S * hd), 0.0);
     if (dprime) {
+        const double two_pi = 6.283185307179586476925286766559, pi = 3.14159265358979323846264338327950288;
+        double d_ell;
+        if (kind == 0) {
+            d_ell = S * (dim / ell - (two_pi * two_pi) * ell * q);
+        } else {
+            const double den = 2 * nu / (ell * ell) + (4 * pi * pi) * q;
+            d_ell = S * (-2 * nu / ell + (-(nu + dim / 2.0)) * (-4 * nu / (ell * ell * ell)) / den);
+        }
         dprime[2 * t] = make_double2(hd * d_ell, 0.0);
         dprime[2 * t + 1] = make_double2(hd * (S / var), 0.0);
     }

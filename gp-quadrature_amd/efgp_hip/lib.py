@@ -59,6 +59,7 @@ _SIGNATURES = {
     "efgp_nufft_type2": (_I, [_VP, _VP, _I, _PI64, _I, _I, _VP, _I, _VP]),
     "efgp_nufft_type2_scaled": (_I, [_VP, _VP, _VP, _I, _PI64, _I, _I, _VP, _I, _VP]),
     "efgp_toeplitz_create": (_I, [C.POINTER(_VP), _I, _I, _PI64, _VP, _I, _VP]),
+    "efgp_toeplitz_create_ex": (_I, [C.POINTER(_VP), _I, _I, _PI64, _VP, _I, _I, _VP]),
     "efgp_toeplitz_destroy": (_I, [_VP]),
     "efgp_toeplitz_apply": (_I, [_VP, _VP, _I, _VP, _VP]),
     "efgp_toeplitz_apply_scaled": (_I, [_VP, _VP, _I, _I, _VP, _VP, _VP, _VP]),
@@ -79,6 +80,7 @@ _SIGNATURES = {
     "efgp_cg_solve_hermitian_async": (_I, [_VP, _VP, _D, _I, _VP, _VP, _VP, _I, _D, _I, _I, _I, _VP, _VP]),
     "efgp_cg_solve_from_zero_async": (_I, [_VP, _VP, _D, _I, _VP, _VP, _VP, _I, _D, _I, _I, _I, _I, _VP, _VP]),
     "efgp_cg_solve_mean_async": (_I, [_VP, _VP, _D, _VP, _VP, _VP, _D, _I, _I, _VP, _VP]),
+    "efgp_cg_solve_mean_fused": (_I, [_VP, _I, _D, _D, _D, _D, _I, _VP, _D, _VP, _VP, _VP, _D, _I, _I, _VP, _VP]),
     "efgp_cg_record_history": (_I, [_VP, _I]),
     "efgp_lanczos": (_I, [_VP, _VP, _D, _I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "efgp_lag_sums": (_I, [_I, _I, _I64, _VP, _VP, _I, _VP, _VP]),

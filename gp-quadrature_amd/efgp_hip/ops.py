@@ -241,7 +241,10 @@ class NufftPlan:
 class ToeplitzOp:
     """d-dimensional Toeplitz mat-vec (C ABI: efgp_toeplitz_*)."""
 
-    def __init__(self, v, force_pow2=True):
+    def __init__(self, v, force_pow2=True, defer_spectra=False):
+        """defer_spectra: on the 48 x 48 Hermitian grids (2-D blocks of up to 23 x 23 modes) launch nothing now -- the fused mean
+        solve (cg_solve_mean_fused) makes the spectrum it needs, any other use the rest (efgp_toeplitz_create_ex).  The library
+        then reads `self.v` later: it must not be changed in place while the operator lives."""
         assert v.is_cuda
         self.dev = v.device
         self.v = v.to(_CD).contiguous()
@@ -253,8 +256,9 @@ class ToeplitzOp:
             self.size *= n
         self._h = C.c_void_p()
         with _on(self.dev):
-            check(lib().efgp_toeplitz_create(C.byref(self._h), self.dev.index, self.d, _i64(self.Ls), _ptr(self.v),
-                                             int(bool(force_pow2)), _stream(self.dev)), "efgp_toeplitz_create")
+            check(lib().efgp_toeplitz_create_ex(C.byref(self._h), self.dev.index, self.d, _i64(self.Ls), _ptr(self.v),
+                                                int(bool(force_pow2)), 1 if defer_spectra else 0, _stream(self.dev)),
+                  "efgp_toeplitz_create")
         shp = (C.c_int64 * 3)()
         check(lib().efgp_toeplitz_fft_shape(self._h, shp), "efgp_toeplitz_fft_shape")
         self.fft_shape = [int(shp[a]) for a in range(self.d)]
@@ -524,6 +528,34 @@ def cg_solve_lazy(op, ws, sigmasq, variant, b, x0, tol, max_iter=None, early_sto
     batched = b.ndim > 1 if batched is None else bool(batched)
     x, _, rows = _cg_solve_sync(op, ws, sigmasq, variant, b, x0, tol, max_iter, early_stop, diag, batched, hermitian)
     return x, LazyIterations(torch.tensor(rows, dtype=torch.int32), batched, int(max_iter) if max_iter is not None else 2 * op.size)
+
+
+def cg_solve_mean_fused(op, kind, nu, c0, lengthscale, h, mtot, sigmasq, diag_scale, fy, tol, max_iter=None, early_stop=True):
+    """cg_solve_mean_async with its set-up in the same launch (efgp_cg_solve_mean_fused), for an operator made with
+    defer_spectra=True on a 48 x 48 Hermitian grid: ws of the built-in kernel (kind 0 SE, 1 Matern nu; c0 as
+    utils.kernels.kernel_constants forms it) is evaluated in the kernel, and so is the operator's 48 x 48 spectrum.
+    Returns (beta, ws (M,) complex128, LazyIterations), or None (nothing enqueued) for any other operator."""
+    dev = op.dev
+    ff = _dc(fy.reshape(-1), dev, _CD)
+    if ff.numel() != op.size or op.size != int(mtot) ** op.d:
+        raise ValueError(f"fy has {ff.numel()} entries, the operator has {op.size} (mtot {mtot})")
+    ws = torch.empty(op.size, dtype=_CD, device=dev)
+    x = torch.empty(op.size, dtype=_CD, device=dev)
+    ds = None
+    if diag_scale is not None:
+        ds = diag_scale.to(device=dev, dtype=_RD)        # no copy for a float64 view on the device
+        if ds.numel() != 1:
+            raise ValueError("diag_scale must hold one value")
+    mi = int(max_iter) if max_iter is not None else 2 * op.size
+    rows_dev = torch.empty(1, dtype=torch.int32, device=dev)
+    with _on(dev):
+        rc = lib().efgp_cg_solve_mean_fused(op._h, int(kind), float(nu), float(lengthscale), float(c0), float(h), int(mtot), _ptr(ws),
+                                            float(sigmasq), _ptr(ds) if ds is not None else None, _ptr(ff), _ptr(x), float(tol), mi,
+                                            int(bool(early_stop)), _ptr(rows_dev), _stream(dev))
+    if rc == EFGP_EUNSUPPORTED:
+        return None
+    check(rc, "efgp_cg_solve_mean_fused")
+    return x.reshape(fy.shape), ws, LazyIterations(rows_dev, False, mi, x, None)
 
 
 def cg_solve_mean_async(op, ws, sigmasq, diag_scale, fy, tol, max_iter=None, early_stop=True):

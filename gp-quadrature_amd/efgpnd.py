@@ -31,7 +31,7 @@ from cg import ConjugateGradients
 from kernels.kernel_params import GPParams
 from utils.kernels import get_xis
 
-from efgp_hip import NufftPlan, PointSet, ToeplitzOp, lanczos, lag_sums, variance_rhs, variance_contract, cg_solve, cg_solve_lazy, cg_solve_mean_async, vdot_real, compute_device, rademacher_fill, gradient_prepare, gradient_assemble
+from efgp_hip import NufftPlan, PointSet, ToeplitzOp, lanczos, lag_sums, variance_rhs, variance_contract, cg_solve, cg_solve_lazy, cg_solve_mean_async, cg_solve_mean_fused, vdot_real, compute_device, rademacher_fill, gradient_prepare, gradient_assemble
 from efgp_hip.dist import PointShards
 
 TWO_PI = 2.0 * math.pi
@@ -197,7 +197,7 @@ class ToeplitzND:
     libefgp_hip.  ``precompute_fft`` is accepted for compatibility; the transform of v is always cached.
     """
 
-    def __init__(self, v: torch.Tensor, *, force_pow2: bool = True, precompute_fft: bool = True):
+    def __init__(self, v: torch.Tensor, *, force_pow2: bool = True, precompute_fft: bool = True, defer_spectra: bool = False):
         if not torch.is_complex(v):
             v = v.to(torch.complex128 if v.dtype == torch.float64 else torch.complex64)
         self.Ls = list(v.shape)
@@ -207,7 +207,7 @@ class ToeplitzND:
         self.device = v.device
         self.dtype = v.dtype
         self._dev = compute_device(v)
-        self._op = ToeplitzOp(v.detach().to(self._dev), force_pow2=force_pow2)
+        self._op = ToeplitzOp(v.detach().to(self._dev), force_pow2=force_pow2, defer_spectra=defer_spectra)
         self.fft_shape = list(self._op.fft_shape)
         self.starts = [n - 1 for n in self.ns]
         self.ends = [s + n for s, n in zip(self.starts, self.ns)]
@@ -1291,19 +1291,34 @@ class EFGPND(nn.Module):
         rdtype = self.x.dtype
         cdtype = _cmplx(rdtype)
 
-        grid = _Grid(self.kernel, self.eps, dd["L"], d, dev)
+        grid = _Grid(self.kernel, self.eps, dd["L"], d, dev, defer_weights=True)
+        warm = self.opts.get("mean_cg_warm_start", True) and self._beta is not None and tuple(self._beta.shape) == (grid.M,)
+        # Cold start of a built-in kernel on a 2-D grid: the weights may be made inside the mean solve (below); elsewhere they are
+        # made now, ahead of the pass over the points
+        bk = _builtin_kernel_constants(self.kernel) if (d == 2 and not warm and dev.type == "cuda" and
+                                                        not os.environ.get("EFGP_NO_NATIVE_GRID")) else None
+        if bk is None:
+            grid.make_weights()
         plan = NufftPlan(xd, grid.h, min(float(nufft_eps), _CONV_TOL), points=self._layout())
         Fy, v = _normal_equations(plan, yd, grid, self._shards)
-        toeplitz = ToeplitzND(v, force_pow2=True)
+        # deferred: on the 48 x 48 Hermitian grids the operator launches nothing; the fused solve makes its spectrum
+        toeplitz = ToeplitzND(v, force_pow2=True, defer_spectra=bk is not None)
         use_precond = self.opts.get("mean_cg_preconditioner", True)
         tol = self.opts.get("cg_tolerance", 1e-4)
-        warm = self.opts.get("mean_cg_warm_start", True) and self._beta is not None and \
-            tuple(self._beta.shape) == tuple(Fy.shape)
         # Cold start on a grid that fits the single-launch kernel: rhs = ws*F*y (:792), the Jacobi diagonal
         # v[0]|ws|^2 + sigma^2 (:795-799) and beta_0 = 0 are formed inside the solve kernel -- one launch, no host
-        # synchronisation (the iteration count stays on the device until somebody reads last_fit_stats).
+        # synchronisation (the iteration count stays on the device until somebody reads last_fit_stats).  On the 48 x 48 grids
+        # of a built-in kernel that launch also evaluates ws and makes the operator's spectrum (efgp_cg_solve_mean_fused).
         res = None
-        if not warm:
+        if bk is not None:
+            (kind, nu, c0), ell, _var = bk
+            fused = cg_solve_mean_fused(toeplitz._op, kind, nu, c0, ell, grid.h, grid.mtot, sig,
+                                        _center_value(v) if use_precond else None, Fy, tol, early_stop=True)
+            if fused is not None:
+                beta_f, grid.ws, iters_f = fused
+                res = (beta_f, iters_f)
+        grid.make_weights()                        # no-op when the fused solve made them
+        if res is None and not warm:
             res = cg_solve_mean_async(toeplitz._op, grid.ws, sig, _center_value(v) if use_precond else None, Fy, tol,
                                       early_stop=True)
         if res is None:

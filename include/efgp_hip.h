@@ -160,6 +160,13 @@ int efgp_nufft_type2_scaled(efgp_nufft_t* plan, const void* f, const void* mode_
  * is next_pow2(L_a) when force_pow2 (efgpnd.py:1269) else the next 2^a3^b5^c size >= L_a. */
 int efgp_toeplitz_create(efgp_toeplitz_t** op_out, int device, int dim, const int64_t* Ls,
                          const void* v, int force_pow2, void* stream);
+/* efgp_toeplitz_create with flags.  EFGP_TOEPLITZ_DEFER_SPECTRA: where the Hermitian solves run on the 48 x 48 grid (2-D blocks
+ * of up to 23 x 23 modes), creation launches nothing; efgp_cg_solve_mean_fused makes the 48 x 48 spectrum in its own kernel and
+ * the first use by any other entry makes the spectra still missing.  v is then NOT copied: the caller keeps it alive and unchanged
+ * for the operator's lifetime.  Elsewhere the flag has no effect. */
+#define EFGP_TOEPLITZ_DEFER_SPECTRA 1
+int efgp_toeplitz_create_ex(efgp_toeplitz_t** op_out, int device, int dim, const int64_t* Ls,
+                            const void* v, int force_pow2, int flags, void* stream);
 int efgp_toeplitz_destroy(efgp_toeplitz_t* op);
 /* y[b] = T x[b]; x, y (nbatch, prod n_a) complex, may alias.  (ToeplitzND.__call__, :1331-1393) */
 int efgp_toeplitz_apply(efgp_toeplitz_t* op, const void* x, int nbatch, void* y, void* stream);
@@ -325,6 +332,14 @@ int efgp_fft_c2c(int device, int rank, const long long* n, long long batch, void
  * when its grid barrier could not get the workgroups resident together: solve again through efgp_cg_solve). */
 int efgp_cg_solve_mean_async(efgp_toeplitz_t* op, const void* ws, double sigmasq, const double* diag_scale_dev, const void* fy,
                              void* x, double tol, int max_iter, int early_stop, int* iters_dev, void* stream);
+/* efgp_cg_solve_mean_async with its set-up in the same kernel, for an operator made with EFGP_TOEPLITZ_DEFER_SPECTRA whose solves
+ * run on the 48 x 48 grid: ws (M = mtot^2 complex, written to ws_out) is evaluated from the built-in kernel's parameters as
+ * efgp_spectral_weights does (kind 0 SE, 1 Matern nu; c0, lengthscale, grid spacing h), the 48 x 48 spectrum of the Toeplitz
+ * vector is made in the prologue; the iteration, beta and the count are those of efgp_cg_solve_mean_async.  EFGP_EUNSUPPORTED
+ * (nothing enqueued) for any other operator: the caller makes ws itself and uses efgp_cg_solve_mean_async. */
+int efgp_cg_solve_mean_fused(efgp_toeplitz_t* op, int kind, double nu, double lengthscale, double c0, double h, int mtot, void* ws_out,
+                             double sigmasq, const double* diag_scale_dev, const void* fy, void* x, double tol, int max_iter,
+                             int early_stop, int* iters_dev, void* stream);
 
 /* Lanczos three-term recurrence on A (variant as in efgp_cg_solve), the inner loop of the reference's stochastic
  * Lanczos quadrature log-determinant (logdet_slq, efgpnd.py:1716-1738):
