@@ -77,7 +77,8 @@ __device__ __forceinline__ void lds_add_raw(double* cell, double a_scaled, doubl
 }
 __device__ __forceinline__ long long sext48(long long v) { return (v << 16) >> 16; }
 
-template <int D, int W, bool USE_LDS>
+// GEN: the strengths are standard normals generated in the kernel (STR_NORMAL / STR_NORMAL_PAIR, see fetch_strength)
+template <int D, int W, bool USE_LDS, bool GEN = false>
 __global__ __launch_bounds__(kSpreadThreads) void spread_kernel(SpreadArgs a) {
     extern __shared__ double lds[];
     const int batch = blockIdx.y;
@@ -99,7 +100,7 @@ __global__ __launch_bounds__(kSpreadThreads) void spread_kernel(SpreadArgs a) {
 
     for (int64_t n = lo + threadIdx.x; n < hi; n += kSpreadThreads) {
         double c0, c1;
-        fetch_strength(a.src, batch, n, c0, c1);
+        fetch_strength<GEN>(a.src, batch, n, c0, c1);
         c0 *= S;
         c1 *= S1;
         double v0[W], v1[W], v2[W];
@@ -241,7 +242,7 @@ __global__ __launch_bounds__(kSpreadThreads) void class_order_kernel(GridGeom g,
     }
 }
 
-template <int D, int W, bool RAW48>
+template <int D, int W, bool RAW48, bool GEN = false>
 __global__ __launch_bounds__(kSpreadThreads) void spread_pad_kernel(SpreadArgs a) {
     extern __shared__ double lds[];
     const int batch = blockIdx.y;
@@ -328,7 +329,7 @@ __global__ __launch_bounds__(kSpreadThreads) void spread_pad_kernel(SpreadArgs a
         if (src < 0) continue;
         const int64_t n = n_ord >= 0 ? n_ord : cbase + src;
         double c0, c1;
-        fetch_strength(a.src, batch, n, c0, c1);
+        fetch_strength<GEN>(a.src, batch, n, c0, c1);
         c0 *= S;
         c1 *= S1;
         double v0[W], v1[W], v2[W];
@@ -396,6 +397,19 @@ __global__ void rademacher_fill_kernel(unsigned long long seed, int64_t npts, in
     const int row = blockIdx.y;
     for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < npts; n += (int64_t)gridDim.x * blockDim.x)
         out[(int64_t)row * npts + n] = efgp_rademacher(seed, row, (long long)((unsigned long long)n + (unsigned long long)index_offset));
+}
+
+// out[b][n] = the standard normal the spread kernels generate for (seed, row b, point n + index_offset): one Box-Muller
+// evaluation serves rows 2p and 2p + 1 (blockIdx.y = p); an odd row count leaves the last pair half used
+__global__ void normal_fill_kernel(unsigned long long seed, int64_t npts, int64_t index_offset, int pair0, int nrows,
+                                   double* __restrict__ out) {
+    const int pair = pair0 + blockIdx.y;
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < npts; n += (int64_t)gridDim.x * blockDim.x) {
+        double z0, z1;
+        efgp_normal_pair(seed, pair, (long long)((unsigned long long)n + (unsigned long long)index_offset), z0, z1);
+        out[(int64_t)(2 * pair) * npts + n] = z0;
+        if (2 * pair + 1 < nrows) out[(int64_t)(2 * pair + 1) * npts + n] = z1;
+    }
 }
 
 // Fixed-point scales, one per channel: scale[0] = S0 (channel 0), [1] = 1/S0, [2] = S1 (channel 1), [3] = 1/S1,
@@ -789,7 +803,7 @@ struct TileSpreadArgs {
     const double* scale;
 };
 
-template <int D, int W>
+template <int D, int W, bool GEN = false>
 __global__ __launch_bounds__(kSpreadThreads) void spread_tile_kernel(TileSpreadArgs a) {
     extern __shared__ double lds[];
     __shared__ int s_bin;
@@ -829,7 +843,7 @@ __global__ __launch_bounds__(kSpreadThreads) void spread_tile_kernel(TileSpreadA
         __syncthreads();
         for (int64_t n = cur + threadIdx.x; n < seg_hi; n += kSpreadThreads) {
             double c0, c1;
-            fetch_strength(a.src, batch, a.src.mode == STR_ONES ? 0 : (int64_t)a.order[n], c0, c1);
+            fetch_strength<GEN>(a.src, batch, a.src.mode == STR_ONES ? 0 : (int64_t)a.order[n], c0, c1);
             c0 *= S;
             c1 *= S1;
             double v0[W], v1[W], v2[W];
@@ -2159,24 +2173,24 @@ static ModeGeom make_modes(const efgp_nufft_s* plan, const WindowSet* w, const i
     return m;
 }
 
-template <int D, int W>
+template <int D, int W, bool GEN>
 static hipError_t launch_spread_dw(bool use_lds, dim3 grid, size_t lds_bytes, hipStream_t s, const SpreadArgs& a) {
     if (use_lds) {
-        auto k = spread_kernel<D, W, true>;
+        auto k = spread_kernel<D, W, true, GEN>;
         if (lds_bytes > 65536) {
             hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
             if (e != hipSuccess) return e;
         }
         hipLaunchKernelGGL(k, grid, dim3(kSpreadThreads), lds_bytes, s, a);
     } else {
-        hipLaunchKernelGGL((spread_kernel<D, W, false>), grid, dim3(kSpreadThreads), 0, s, a);
+        hipLaunchKernelGGL((spread_kernel<D, W, false, GEN>), grid, dim3(kSpreadThreads), 0, s, a);
     }
     return hipGetLastError();
 }
 
-template <int D, int W, bool RAW48>
+template <int D, int W, bool RAW48, bool GEN = false>
 static hipError_t launch_spread_pad_dwr(dim3 grid, size_t lds_bytes, hipStream_t s, const SpreadArgs& a) {
-    auto k = spread_pad_kernel<D, W, RAW48>;
+    auto k = spread_pad_kernel<D, W, RAW48, GEN>;
     if (lds_bytes > 65536) {
         hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return e;
@@ -2190,6 +2204,7 @@ static hipError_t launch_spread_pad_d(int W, bool raw48, dim3 grid, size_t lds_b
     switch (W) {
 #define EFGP_CASE(w_)                                                                          \
     case w_:                                                                                   \
+        if (strength_is_normal(a.src.mode)) return launch_spread_pad_dwr<D, w_, false, true>(grid, lds_bytes, s, a); \
         return raw48 ? launch_spread_pad_dwr<D, w_, true>(grid, lds_bytes, s, a)               \
                      : launch_spread_pad_dwr<D, w_, false>(grid, lds_bytes, s, a);
         EFGP_CASE(2) EFGP_CASE(3) EFGP_CASE(4) EFGP_CASE(5) EFGP_CASE(6) EFGP_CASE(7) EFGP_CASE(8) EFGP_CASE(9)
@@ -2202,7 +2217,10 @@ static hipError_t launch_spread_pad_d(int W, bool raw48, dim3 grid, size_t lds_b
 template <int D>
 static hipError_t launch_spread_d(int W, bool use_lds, dim3 grid, size_t lds_bytes, hipStream_t s, const SpreadArgs& a) {
     switch (W) {
-#define EFGP_CASE(w_) case w_: return launch_spread_dw<D, w_>(use_lds, grid, lds_bytes, s, a);
+#define EFGP_CASE(w_)                                                                                   \
+    case w_:                                                                                            \
+        return strength_is_normal(a.src.mode) ? launch_spread_dw<D, w_, true>(use_lds, grid, lds_bytes, s, a) \
+                                              : launch_spread_dw<D, w_, false>(use_lds, grid, lds_bytes, s, a);
         EFGP_CASE(2) EFGP_CASE(3) EFGP_CASE(4) EFGP_CASE(5) EFGP_CASE(6) EFGP_CASE(7) EFGP_CASE(8) EFGP_CASE(9)
         EFGP_CASE(10) EFGP_CASE(11) EFGP_CASE(12) EFGP_CASE(13) EFGP_CASE(14) EFGP_CASE(15) EFGP_CASE(16)
 #undef EFGP_CASE
@@ -2597,7 +2615,7 @@ static hipError_t launch_tile_d(int W, dim3 grid, size_t lds_bytes, hipStream_t 
     switch (W) {
 #define EFGP_CASE(w_)                                                                                               \
     case w_: {                                                                                                      \
-        auto k = spread_tile_kernel<D, w_>;                                                                         \
+        auto k = strength_is_normal(a.src.mode) ? spread_tile_kernel<D, w_, true> : spread_tile_kernel<D, w_, false>; \
         if (lds_bytes > 65536) {                                                                                    \
             hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
             if (e != hipSuccess) return e;                                                                          \
@@ -2883,10 +2901,13 @@ static int spread_and_fft(efgp_nufft_s* plan, WindowSet* w, const double* c, int
     DeviceCtx* ctx = plan->ctx;
     const GridGeom g = make_geom(plan, w);
     if (scale_out) *scale_out = nullptr;
-    const int channels = (mode == STR_COMPLEX || mode == STR_REAL_AND_ONES || mode == STR_REAL_PAIR || mode == STR_RNG_PAIR) ? 2 : 1;
+    const int channels = (mode == STR_COMPLEX || mode == STR_REAL_AND_ONES || mode == STR_REAL_PAIR || mode == STR_RNG_PAIR ||
+                          mode == STR_NORMAL_PAIR) ? 2 : 1;
     // strengths read from memory need a max|c| pass for the fixed-point scale; generated / implicit ones are +-1
     const bool need_max = (mode == STR_REAL || mode == STR_COMPLEX || mode == STR_REAL_AND_ONES || mode == STR_REAL_PAIR);
-    const double floor_bound = (mode == STR_REAL_AND_ONES || mode == STR_ONES || mode == STR_RNG || mode == STR_RNG_PAIR) ? 1.0 : 0.0;
+    // generated normals are bounded by construction (kNormalBound): the scale is sized for that bound, no pass over data
+    const double floor_bound = strength_is_normal(mode) ? kNormalBound
+                               : (mode == STR_REAL_AND_ONES || mode == STR_ONES || mode == STR_RNG || mode == STR_RNG_PAIR) ? 1.0 : 0.0;
     const int64_t nvals = (mode == STR_REAL_AND_ONES) ? plan->npts
                           : (int64_t)nbatch * plan->npts * ((mode == STR_COMPLEX || mode == STR_REAL_PAIR) ? 2 : 1);
     StrengthSrc src;
@@ -2975,7 +2996,7 @@ static int spread_and_fft(efgp_nufft_s* plan, WindowSet* w, const double* c, int
         // per cell, but the per-plan counting sort it needs (0.15 ms at N=1e6, 0.6 ms at N=1e7) only pays off after
         // several passes over the same plan; see LABNOTES.md section 4.1.
         const char* force = std::getenv("EFGP_CELLSORT");
-        const bool use_cells = force && force[0] == '1' && plan->dim == 2 && w->p.w <= kCellMaxW &&
+        const bool use_cells = force && force[0] == '1' && !strength_is_normal(mode) && plan->dim == 2 && w->p.w <= kCellMaxW &&
                                w->p.degree <= w->p.w + 4 && g.cells <= 16384 && plan->npts > 0;
         TileGeom cg;
         if (use_cells && make_tile_geom(plan, w, channels, (size_t)ctx->max_lds - 4096, &cg, 1)) {
@@ -3113,7 +3134,8 @@ static int spread_and_fft(efgp_nufft_s* plan, WindowSet* w, const double* c, int
     const int64_t nlast = g.nf[plan->dim - 1];
     const size_t pad_bytes = (size_t)channels * (size_t)(g.cells / nlast) * (size_t)(nlast + w->p.w - 1) * sizeof(double);
     const bool use_pad = use_lds && pad_bytes + 4608 <= (size_t)ctx->max_lds && std::getenv("EFGP_NO_PAD") == nullptr;   // + class lists
-    const bool raw48 = use_pad && (double)per * std::ldexp(1.0, -47) <= 0.01 * plan->tol && std::getenv("EFGP_NO_RAW48") == nullptr;
+    const bool raw48 = use_pad && (double)per * std::ldexp(1.0, -47) <= 0.01 * plan->tol && std::getenv("EFGP_NO_RAW48") == nullptr &&
+                       !strength_is_normal(mode);     // normals: max|c| is 8.6 typical magnitudes, the raw floor would be that much coarser
     if (plan->npts > 0) {      // (both forms: LDS tiles per workgroup, or one global int64 grid)
         if (scale_out) *scale_out = d_scale;
         // fixed-point scale from max |c| (device side, no host round trip)
@@ -3267,7 +3289,8 @@ int efgp_nufft_destroy(efgp_nufft_t* plan) {
 
 // shared by the strengths-from-memory and the generated-probe entry points: real rows are processed two
 // per fine grid (re/im channels, separated after the FFT by Hermitian symmetry), an odd last row alone
-static int type1_real_rows(efgp_nufft_s* plan, WindowSet* w, const double* c, bool rng, unsigned long long seed,
+enum RowSource { ROWS_MEMORY = 0, ROWS_RADEMACHER = 1, ROWS_NORMAL = 2 };
+static int type1_real_rows(efgp_nufft_s* plan, WindowSet* w, const double* c, RowSource rows, unsigned long long seed,
                            int64_t index_offset, int nbatch, const int64_t* n_modes, int isign, int modeord, void* out,
                            hipStream_t stream) {
     int64_t total = 1;
@@ -3275,6 +3298,7 @@ static int type1_real_rows(efgp_nufft_s* plan, WindowSet* w, const double* c, bo
     // Generated probes, odd count, 2-D: the last row rides as the real part of one more pair grid whose imaginary row (index nbatch)
     // is generated and dropped -- one pass and one transform chain instead of two (6 launches; the 2-D spread costs the same per
     // grid with one channel or two).  Rows read from memory have no row `nbatch` to read, and the 1-D / 3-D passes pay per channel.
+    const bool rng = rows != ROWS_MEMORY;
     const bool pad_odd = rng && (nbatch & 1) && nbatch > 1 && plan->dim == 2;
     const int npair = pad_odd ? (nbatch + 1) / 2 : nbatch / 2;
     double2* fine = nullptr;
@@ -3284,7 +3308,7 @@ static int type1_real_rows(efgp_nufft_s* plan, WindowSet* w, const double* c, bo
         req.rows_limit = nbatch;
         req.ma = make_modes(plan, w, n_modes, modeord);
         req.out_a = out;
-        int rc = spread_and_fft(plan, w, c, rng ? STR_RNG_PAIR : STR_REAL_PAIR, npair, isign, stream, &fine, seed, index_offset, nullptr,
+        int rc = spread_and_fft(plan, w, c, rows == ROWS_NORMAL ? STR_NORMAL_PAIR : (rng ? STR_RNG_PAIR : STR_REAL_PAIR), npair, isign, stream, &fine, seed, index_offset, nullptr,
                                 &req);
         if (rc != EFGP_OK) return rc;
         // for isign = +1 the roles of k and -k swap in the Hermitian split; conjugating H handles both signs:
@@ -3299,7 +3323,12 @@ static int type1_real_rows(efgp_nufft_s* plan, WindowSet* w, const double* c, bo
         req.part = 0;
         req.ma = make_modes(plan, w, n_modes, modeord);
         req.out_a = (double2*)out + (int64_t)last * total;
-        if (rng) {
+        if (rows == ROWS_NORMAL) {
+            // row `last` (even) is element 0 of pair last / 2: pair 0 at the point index shifted by (last / 2) * kRowStride
+            rc = spread_and_fft(plan, w, nullptr, STR_NORMAL, 1, isign, stream, &fine, seed,
+                                (int64_t)((unsigned long long)index_offset + (unsigned long long)(last >> 1) * kRademacherRowStride), nullptr,
+                                &req);
+        } else if (rng) {
             // STR_RNG takes the fine-grid index (0 here) as the row: row `last` of the same seed is row 0 at the point index shifted
             // by last * kRowStride (efgp_rademacher hashes row * kRowStride + index in wrapping 64-bit arithmetic)
             rc = spread_and_fft(plan, w, nullptr, STR_RNG, 1, isign, stream, &fine, seed,
@@ -3328,7 +3357,7 @@ int efgp_nufft_type1(efgp_nufft_t* plan, const void* c, int c_is_complex, int nb
     int rc = get_window(plan, n_modes, stream, &w);
     if (rc != EFGP_OK) return rc;
     if (!c_is_complex && isign == -1 && plan->npts > 0)
-        return type1_real_rows(plan, w, (const double*)c, false, 0, 0, nbatch, n_modes, isign, modeord, out, stream);
+        return type1_real_rows(plan, w, (const double*)c, ROWS_MEMORY, 0, 0, nbatch, n_modes, isign, modeord, out, stream);
     double2* fine = nullptr;
     G2MRequest req;
     req.part = 0;
@@ -3356,8 +3385,45 @@ int efgp_nufft_type1_rademacher(efgp_nufft_t* plan, uint64_t seed, int64_t index
         EFGP_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)nbatch * total * sizeof(double2), stream));
         return EFGP_OK;
     }
-    return type1_real_rows(plan, w, nullptr, true, (unsigned long long)seed, index_offset, nbatch, n_modes, -1, modeord, out,
+    return type1_real_rows(plan, w, nullptr, ROWS_RADEMACHER, (unsigned long long)seed, index_offset, nbatch, n_modes, -1, modeord, out,
                            stream);
+}
+
+int efgp_nufft_type1_normal(efgp_nufft_t* plan, uint64_t seed, int64_t index_offset, int nbatch,
+                            const int64_t* n_modes, int modeord, void* out, void* stream_) {
+    EFGP_REQUIRE(plan && n_modes && out, "efgp_nufft_type1_normal: null argument");
+    EFGP_REQUIRE(nbatch >= 1, "efgp_nufft_type1_normal: nbatch must be >= 1");
+    for (int a = 0; a < plan->dim; ++a) EFGP_REQUIRE(n_modes[a] >= 1, "efgp_nufft_type1_normal: n_modes[%d] < 1", a);
+    hipStream_t stream = (hipStream_t)stream_;
+    DeviceGuard guard(plan->device, (hipStream_t)stream_);
+    WindowSet* w = nullptr;
+    int rc = get_window(plan, n_modes, stream, &w);
+    if (rc != EFGP_OK) return rc;
+    if (plan->npts == 0) {
+        int64_t total = 1;
+        for (int a = 0; a < plan->dim; ++a) total *= n_modes[a];
+        EFGP_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)nbatch * total * sizeof(double2), stream));
+        return EFGP_OK;
+    }
+    return type1_real_rows(plan, w, nullptr, ROWS_NORMAL, (unsigned long long)seed, index_offset, nbatch, n_modes, -1, modeord, out,
+                           stream);
+}
+
+int efgp_normal_fill(int device, uint64_t seed, int64_t index_offset, int nbatch, int64_t npts, double* out, void* stream_) {
+    EFGP_REQUIRE(out || npts == 0, "efgp_normal_fill: null out");
+    EFGP_REQUIRE(nbatch >= 1 && npts >= 0, "efgp_normal_fill: bad sizes");
+    if (npts == 0) return EFGP_OK;
+    if (!device_ctx(device)) return EFGP_EHIP;
+    DeviceGuard guard(device, (hipStream_t)stream_);
+    hipStream_t stream = (hipStream_t)stream_;
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((npts + 255) / 256, 4096));
+    const int npairs = (nbatch + 1) / 2;
+    for (int p0 = 0; p0 < npairs; p0 += 65535) {       // gridDim.y holds at most 65535 pairs
+        hipLaunchKernelGGL(normal_fill_kernel, dim3(blocks, std::min(65535, npairs - p0)), dim3(256), 0, stream, (unsigned long long)seed, npts,
+                           index_offset, p0, nbatch, out);
+    }
+    EFGP_HIP_CHECK(hipGetLastError());
+    return EFGP_OK;
 }
 
 int efgp_rademacher_fill(int device, uint64_t seed, int64_t index_offset, int nbatch, int64_t npts, double* out,

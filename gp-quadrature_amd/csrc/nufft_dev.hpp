@@ -21,8 +21,11 @@ enum StrengthMode {
     STR_ONES = 3,
     STR_REAL_PAIR = 4,       // two real rows (2g, 2g+1) share one complex fine grid
     STR_RNG = 5,             // one Rademacher row generated in the kernel
-    STR_RNG_PAIR = 6         // two Rademacher rows
+    STR_RNG_PAIR = 6,        // two Rademacher rows
+    STR_NORMAL = 7,          // one standard-normal row generated in the kernel (kernels instantiated with GEN = true only)
+    STR_NORMAL_PAIR = 8      // two standard-normal rows: both outputs of one Box-Muller evaluation per point
 };
+__host__ __device__ constexpr bool strength_is_normal(int mode) { return mode == STR_NORMAL || mode == STR_NORMAL_PAIR; }
 
 // counter-based Rademacher probe: sign(seed, row, point index) -- splitmix64 finaliser
 __host__ __device__ __forceinline__ unsigned long long efgp_mix64(unsigned long long z) {
@@ -40,6 +43,27 @@ __host__ __device__ __forceinline__ double efgp_rademacher(unsigned long long se
     return (r >> 63) ? 1.0 : -1.0;
 }
 
+// counter-based standard normals: Box-Muller on two hashed words of the counter (seed, pair, n).  Keyed like efgp_rademacher
+// (pair * kRademacherRowStride + n in wrapping arithmetic, so pair p at index n is pair 0 at index n + p * stride and index_offset
+// keeps its meaning), with a domain constant in the seed: Rademacher probes of the same seed see unrelated bits.
+//   u1 = ((r1 >> 11) + 1) 2^-53 in (0, 1],  u2 = (r2 >> 11) 2^-53 in [0, 1),  z0 + i z1 = sqrt(-2 ln u1) exp(2 pi i u2)
+// Row r of a block is element r & 1 of pair r >> 1.  u1 >= 2^-53 bounds the radius: |z| <= sqrt(2 * 53 * ln 2), which the
+// fixed-point spreaders take as the floor of their scale.
+constexpr unsigned long long kNormalDomain = 0x6A09E667F3BCC908ull;      // frac(sqrt 2) and frac(sqrt 3) in 64 bits: one per word
+constexpr unsigned long long kNormalDomain2 = 0xBB67AE8584CAA73Bull;
+constexpr double kNormalBound = 8.5717;                                   // >= sqrt(106 ln 2) = 8.57162...
+__device__ __forceinline__ void efgp_normal_pair(unsigned long long seed, long long pair, long long n, double& z0, double& z1) {
+    const unsigned long long h = efgp_mix64((unsigned long long)pair * kRademacherRowStride + (unsigned long long)n);
+    const unsigned long long r1 = efgp_mix64((seed ^ kNormalDomain) ^ h);
+    const unsigned long long r2 = efgp_mix64((seed ^ kNormalDomain2) ^ h);
+    const double u1 = (double)((r1 >> 11) + 1ull) * 0x1.0p-53, u2 = (double)(r2 >> 11) * 0x1.0p-53;
+    const double rad = sqrt(-2.0 * log(u1));
+    double sn, cs;
+    sincospi(2.0 * u2, &sn, &cs);
+    z0 = rad * cs;
+    z1 = rad * sn;
+}
+
 struct StrengthSrc {
     const double* c;          // base pointer of all rows (layout by mode)
     int64_t npts;             // row length
@@ -48,10 +72,21 @@ struct StrengthSrc {
     int64_t index_offset;     // added to the point index for the RNG (global index of this shard's first point)
 };
 
-// strengths (c0, c1) of point `n` (original index) for fine grid `g`
+// strengths (c0, c1) of point `n` (original index) for fine grid `g`.  GEN = true serves the two normal modes and nothing else:
+// the spread kernels carry them as instantiations of their own, so the logarithm and the sincos cost the other modes nothing.
+template <bool GEN = false>
 __device__ __forceinline__ void fetch_strength(const StrengthSrc& s, int g, int64_t n, double& c0, double& c1) {
     c0 = 1.0;
     c1 = 1.0;
+    if (GEN) {
+        // STR_NORMAL: grid g is row g = element g & 1 of pair g >> 1; STR_NORMAL_PAIR: grid g is pair g, rows 2g and 2g + 1
+        const bool pairs = s.mode == STR_NORMAL_PAIR;
+        double z0, z1;
+        efgp_normal_pair(s.seed, pairs ? g : (g >> 1), (long long)((unsigned long long)n + (unsigned long long)s.index_offset), z0, z1);
+        c0 = (pairs || !(g & 1)) ? z0 : z1;
+        c1 = z1;
+        return;
+    }
     switch (s.mode) {
         case STR_REAL: c0 = s.c[(int64_t)g * s.npts + n]; break;
         case STR_COMPLEX: {

@@ -198,19 +198,26 @@ __device__ __forceinline__ void flush_tile_small(double acc0, double acc1, int c
 struct PointIn {
     double2 xy;
     double c0, c1;
+    int idx;         // GEN only: the point's original index (the normals are generated when the point is used)
 };
 
 // SORTED: strengths come from the level-ordered copy (the fit-time (y, 1) pair or y alone): two coalesced loads and
 // no strength-mode dispatch in the hot loop.
-template <bool SORTED>
+template <bool SORTED, bool GEN>
 __device__ __forceinline__ PointIn load_point(const MfmaSpreadArgs& a, int batch, int p) {
     PointIn r;
     r.xy = reinterpret_cast<const double2*>(a.xs)[p];
-    if (SORTED) {
+    r.idx = 0;
+    if (GEN) {
+        // prefetch the index only: generating here would keep the logarithm's and the sincos' registers live across the MFMA phase
+        // of the batch before (the kernel sits at its register bound already)
+        r.idx = a.perm[p];
+        r.c0 = r.c1 = 0.0;
+    } else if (SORTED) {
         r.c0 = a.ys[p];
         r.c1 = 1.0;
     } else {
-        fetch_strength(a.src, batch, a.perm[p], r.c0, r.c1);
+        fetch_strength<GEN>(a.src, batch, a.perm[p], r.c0, r.c1);
     }
     return r;
 }
@@ -221,8 +228,12 @@ __device__ __forceinline__ PointIn load_point(const MfmaSpreadArgs& a, int batch
 #define EFGP_DIAG(bit_) false
 #endif
 
-template <int W, int DEG, bool SORTED, int HB>
-__global__ __launch_bounds__(64 * kMfmaMaxWaves, HB == 1 ? 3 : 2) void spread_mfma_kernel(MfmaSpreadArgs a) {
+// GEN: standard-normal strengths generated per point (STR_NORMAL / STR_NORMAL_PAIR), an instantiation of its own so that the
+// generator's registers stay out of the kernels the fit and the probe transforms run.  Its one-cell-band form runs two
+// workgroups per CU, not three: under the 168-VGPR bound of three the logarithm and the sincos spill (104-184 bytes of scratch
+// per lane at W = 7, 8), under 256 nothing does.
+template <int W, int DEG, bool SORTED, int HB, bool GEN = false>
+__global__ __launch_bounds__(64 * kMfmaMaxWaves, (HB == 1 && !GEN) ? 3 : 2) void spread_mfma_kernel(MfmaSpreadArgs a) {
     extern __shared__ double lds_raw[];
     constexpr int BR = W + HB;                    // B rows = tile columns in use
     constexpr int kWaveDoubles = mfma_rows(W, HB) * kMfmaRow;
@@ -268,16 +279,20 @@ __global__ __launch_bounds__(64 * kMfmaMaxWaves, HB == 1 ? 3 : 2) void spread_mf
         d4 acc = {0.0, 0.0, 0.0, 0.0};
         double sa0 = 0.0, sa1 = 0.0;                                          // SMALL: the two 4 x 4 x 4 accumulators
         int cur_bx = 0;
-        PointIn nxt = load_point<SORTED>(a, batch, start + (lane < count ? lane : count - 1));
+        PointIn nxt = load_point<SORTED, GEN>(a, batch, start + (lane < count ? lane : count - 1));
         for (int b0 = 0; b0 < count; b0 += 64) {
             const int rem = count - b0;                                       // wave-uniform
             const bool valid = lane < rem;
             const PointIn cur = nxt;
             if (rem > 64) {                                                   // next batch's loads fly during this one
                 const int r2 = rem - 64;
-                nxt = load_point<SORTED>(a, batch, start + b0 + 64 + (lane < r2 ? lane : r2 - 1));
+                nxt = load_point<SORTED, GEN>(a, batch, start + b0 + 64 + (lane < r2 ? lane : r2 - 1));
             }
             double c0 = cur.c0, c1 = a.channels == 1 ? 0.0 : cur.c1;
+            if (GEN) {
+                fetch_strength<true>(a.src, batch, cur.idx, c0, c1);
+                if (a.channels == 1) c1 = 0.0;
+            }
             if (!valid) {                                                     // tail lanes repeat the last point with zero strength
                 c0 = 0.0;
                 c1 = 0.0;
@@ -404,7 +419,12 @@ static hipError_t launch_w(dim3 grid, int waves, hipStream_t s, const MfmaSpread
         }                                                                                                            \
         hipLaunchKernelGGL(k, grid, block, lds, s, a);                                                               \
     } while (0)
-    if (fixed == 1 && sorted) EFGP_GO((spread_mfma_kernel<W, W + 1, true, HB>));
+    if (strength_is_normal(a.src.mode)) {
+        if (sorted) return hipErrorInvalidValue;          // generated strengths have no level-ordered copy
+        if (fixed == 1) EFGP_GO((spread_mfma_kernel<W, W + 1, false, HB, true>));
+        else if (fixed == 2) EFGP_GO((spread_mfma_kernel<W, W + 2, false, HB, true>));
+        else EFGP_GO((spread_mfma_kernel<W, 0, false, HB, true>));
+    } else if (fixed == 1 && sorted) EFGP_GO((spread_mfma_kernel<W, W + 1, true, HB>));
     else if (fixed == 1) EFGP_GO((spread_mfma_kernel<W, W + 1, false, HB>));
     else if (fixed == 2 && sorted) EFGP_GO((spread_mfma_kernel<W, W + 2, true, HB>));
     else if (fixed == 2) EFGP_GO((spread_mfma_kernel<W, W + 2, false, HB>));
@@ -449,7 +469,7 @@ int spread_mfma_launch(DeviceCtx* ctx, const SortedLevel* lvl, int band_cells, c
     // s_waitcnt vmcnt(0) at the merge of its two paths exposes the HBM latency of the prefetched points.)
     // Round 3, bands at most ONE cell high (band_cells = 1; pick_level chooses it for dense point sets): 13.2 KB of rows per
     // wave and 168 VGPRs -> three workgroups of four waves per CU.
-    int waves = 4, per_cu = band_cells == 1 ? 3 : 2;
+    int waves = 4, per_cu = (band_cells == 1 && !strength_is_normal(src.mode)) ? 3 : 2;
     if (const char* e1 = std::getenv("EFGP_MFMA_WAVES")) waves = std::max(1, std::min(kMfmaMaxWaves, std::atoi(e1)));
     if (const char* e2 = std::getenv("EFGP_MFMA_BLOCKS_PER_CU")) per_cu = std::max(1, std::atoi(e2));
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)lvl->nchunks + waves - 1) / waves, (int64_t)ctx->num_cu * per_cu));

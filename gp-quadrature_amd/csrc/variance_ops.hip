@@ -2,6 +2,7 @@
 //   efgp_lag_sums          Hutchinson lag sums  c[r] = mean_j sum_{k-l=r} gamma_j[k] eta_j[l]   (efgpnd.py:1660-1664)
 //   efgp_variance_rhs      right-hand sides ws .* conj(f(x*)) of the 'regular' variance          (efgpnd.py:1805-1812)
 //   efgp_variance_contract s^2(x*) = max(0, Re sum_k f_k(x*) ws_k gamma_k)                        (efgpnd.py:1817-1820)
+//   efgp_hermitian_normal_rows  right-hand sides / prior weights of the path sampler: a ws .* fz + b e, e a conjugate-even normal row
 // The reference does these with torch.fft / dense torch ops; here they are hipFFT transforms plus three small kernels,
 // so a caller that binds only include/efgp_hip.h can compute a variance end to end.
 #include <algorithm>
@@ -10,6 +11,7 @@
 
 #include "common.hpp"
 #include "line_fft.hpp"
+#include "nufft_dev.hpp"
 #include "spectral_weights.hpp"
 #include "toeplitz_cg.hpp"
 
@@ -160,6 +162,32 @@ __global__ __launch_bounds__(256) void spectral_weights_kernel(int kind, int dim
     }
 }
 
+// out[s, j] = a ws[j] fz[s, j] + b e[s, j] on the symmetric mode box (flat index j, negated frequency at M - 1 - j), with
+// e[s, j] = (z0 + i z1) / sqrt 2 of Box-Muller pair s at index j + index_offset below the centre, z0 at the centre (real), and the
+// upper half WRITTEN as the conjugate of the lower: the row is conjugate-even bit for bit.  fz (a transform of real rows) is
+// conjugate-even up to rounding; only its lower half is read.  ws / fz null: the first term is absent.
+__global__ __launch_bounds__(256) void hermitian_normal_rows_kernel(unsigned long long seed, int64_t index_offset, int row0, int64_t M,
+                                                                    double a, const double2* __restrict__ ws,
+                                                                    const double2* __restrict__ fz, double b, double2* __restrict__ out) {
+    const int s = row0 + blockIdx.y;
+    const int64_t centre = (M - 1) / 2;
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j <= centre; j += (int64_t)gridDim.x * blockDim.x) {
+        double z0, z1;
+        efgp_normal_pair(seed, s, (long long)((unsigned long long)j + (unsigned long long)index_offset), z0, z1);
+        double re = j == centre ? z0 : z0 * 0.70710678118654752440, im = j == centre ? 0.0 : z1 * 0.70710678118654752440;
+        re *= b;
+        im *= b;
+        if (ws) {
+            const double2 w = ws[j], f = fz[(int64_t)s * M + j];
+            const double pr = w.x * f.x - w.y * f.y, pi = w.x * f.y + w.y * f.x;
+            re = fma(a, pr, re);
+            im = j == centre ? 0.0 : fma(a, pi, im);
+        }
+        out[(int64_t)s * M + j] = make_double2(re, im);
+        if (j != centre) out[(int64_t)s * M + (M - 1 - j)] = make_double2(re, -im);
+    }
+}
+
 }  // namespace efgp
 
 using namespace efgp;
@@ -239,6 +267,24 @@ int efgp_lag_sums(int device, int dim, int64_t mtot, const void* gamma, const do
     const int oblocks = (int)std::max<int64_t>(1, std::min<int64_t>((g.S + 255) / 256, 1024));
     hipLaunchKernelGGL(lag_scale_kernel, dim3(oblocks), dim3(256), 0, stream, g, 1.0 / ((double)g.P * (double)nprobes), (const double2*)acc,
                        (double2*)out);
+    EFGP_HIP_CHECK(hipGetLastError());
+    return EFGP_OK;
+}
+
+int efgp_hermitian_normal_rows(int device, uint64_t seed, int64_t index_offset, int nrows, int64_t nmodes, double a, const void* ws,
+                               const void* fz, double b, void* out, void* stream_) {
+    EFGP_REQUIRE(nrows >= 1 && nmodes >= 1 && (nmodes & 1), "efgp_hermitian_normal_rows: nrows >= 1 and an odd mode count are required");
+    EFGP_REQUIRE(out, "efgp_hermitian_normal_rows: null out");
+    EFGP_REQUIRE((ws == nullptr) == (fz == nullptr), "efgp_hermitian_normal_rows: ws and fz go together (both or neither)");
+    if (!device_ctx(device)) return EFGP_EHIP;
+    DeviceGuard guard(device, (hipStream_t)stream_);
+    const int64_t half = (nmodes + 1) / 2;
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((half + 255) / 256, 1024));
+    for (int r0 = 0; r0 < nrows; r0 += 65535) {
+        const int nr = std::min(65535, nrows - r0);
+        hipLaunchKernelGGL(hermitian_normal_rows_kernel, dim3(blocks, nr), dim3(256), 0, (hipStream_t)stream_, (unsigned long long)seed,
+                           index_offset, r0, nmodes, a, (const double2*)ws, (const double2*)fz, b, (double2*)out);
+    }
     EFGP_HIP_CHECK(hipGetLastError());
     return EFGP_OK;
 }

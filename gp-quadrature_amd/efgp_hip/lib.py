@@ -55,6 +55,8 @@ _SIGNATURES = {
     "efgp_nufft_type1": (_I, [_VP, _VP, _I, _I, _PI64, _I, _I, _VP, _VP]),
     "efgp_nufft_type1_rademacher": (_I, [_VP, C.c_uint64, _I64, _I, _PI64, _I, _VP, _VP]),
     "efgp_rademacher_fill": (_I, [_I, C.c_uint64, _I64, _I, _I64, _VP, _VP]),
+    "efgp_nufft_type1_normal": (_I, [_VP, C.c_uint64, _I64, _I, _PI64, _I, _VP, _VP]),
+    "efgp_normal_fill": (_I, [_I, C.c_uint64, _I64, _I, _I64, _VP, _VP]),
     "efgp_nufft_type1_pair": (_I, [_VP, _VP, _PI64, _VP, _PI64, _VP, _VP]),
     "efgp_nufft_type2": (_I, [_VP, _VP, _I, _PI64, _I, _I, _VP, _I, _VP]),
     "efgp_nufft_type2_scaled": (_I, [_VP, _VP, _VP, _I, _PI64, _I, _I, _VP, _I, _VP]),
@@ -86,6 +88,7 @@ _SIGNATURES = {
     "efgp_lag_sums": (_I, [_I, _I, _I64, _VP, _VP, _I, _VP, _VP]),
     "efgp_variance_rhs": (_I, [_I, _I, _I64, _D, _VP, _I64, _VP, _VP, _VP]),
     "efgp_variance_contract": (_I, [_I, _I, _I64, _D, _VP, _I64, _VP, _VP, _VP, _VP]),
+    "efgp_hermitian_normal_rows": (_I, [_I, C.c_uint64, _I64, _I, _I64, _D, _VP, _VP, _D, _VP, _VP]),
     "efgp_pg_estep_update": (_I, [_I, _I64, _I, _VP, _VP, C.c_uint64, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
     "efgp_pg_nb_estep_update": (_I, [_I, _I64, _I, _VP, _VP, C.c_uint64, _VP, _D, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
     "efgp_pg_nb_total_count_grad": (_I, [_I, _I64, _VP, _VP, _VP, _D, _I, _VP, _VP, _VP, _VP]),

@@ -84,6 +84,22 @@ def _dc(t, dev, dtype):
     return t.to(device=dev, dtype=dtype).contiguous()
 
 
+NORMAL_ROW_STRIDE = 0xD1342543DE82EF95      # csrc/nufft_dev.hpp: pair p at index n is pair 0 at index n + p * stride (mod 2^64)
+
+
+def _wrap_i64(v):
+    """An index offset in wrapping 64-bit arithmetic as the signed value the C ABI takes."""
+    v = int(v) & (2 ** 64 - 1)
+    return v - 2 ** 64 if v >= 2 ** 63 else v
+
+
+def normal_row_offset(first_row, index_offset=0):
+    """index_offset that makes row r of a generated-normal call the global row first_row + r (first_row even)."""
+    if first_row % 2:
+        raise ValueError("normal rows are generated in pairs: the first row of a block must be even")
+    return _wrap_i64(int(index_offset) + (int(first_row) // 2) * NORMAL_ROW_STRIDE)
+
+
 def _i64(vals):
     return (C.c_int64 * len(vals))(*[int(v) for v in vals])
 
@@ -186,6 +202,16 @@ class NufftPlan:
             check(lib().efgp_nufft_type1_rademacher(self._h, int(seed) & (2 ** 64 - 1), int(index_offset), int(nbatch),
                                                     _i64(n_modes), int(modeord), _ptr(out), _stream(self.dev)),
                   "efgp_nufft_type1_rademacher")
+        return out
+
+    def type1_normal(self, seed, nbatch, n_modes, index_offset=0, modeord=0):
+        """F* Z for Z[b,n] ~ N(0, 1) generated in the kernel from (seed, b, n + index_offset) -> (B, *n_modes); `normal_fill`
+        materialises the same Z."""
+        out = torch.empty((int(nbatch),) + tuple(int(m) for m in n_modes), dtype=_CD, device=self.dev)
+        with _on(self.dev):
+            check(lib().efgp_nufft_type1_normal(self._h, int(seed) & (2 ** 64 - 1), _wrap_i64(index_offset), int(nbatch),
+                                                _i64(n_modes), int(modeord), _ptr(out), _stream(self.dev)),
+                  "efgp_nufft_type1_normal")
         return out
 
     def type1_pair(self, y, n_modes_y, n_modes_one):
@@ -835,6 +861,38 @@ def gradient_step(xd, yd, points, *, h, mtot, kconst, lengthscale, variance, sig
         return None
     check(rc, "efgp_gradient_step")
     return out, beta, LazyIterations(its[:1], False, 2 * M), LazyIterations(its[1:], True, 2 * M)
+
+
+def normal_fill(dev, seed, nbatch, npts, index_offset=0):
+    """The standard normals `NufftPlan.type1_normal` uses, materialised as a (nbatch, npts) float64 tensor."""
+    out = torch.empty((int(nbatch), int(npts)), dtype=_RD, device=dev)
+    with _on(dev):
+        check(lib().efgp_normal_fill(dev.index, int(seed) & (2 ** 64 - 1), _wrap_i64(index_offset), int(nbatch), int(npts),
+                                     _ptr(out), _stream(dev)), "efgp_normal_fill")
+    return out
+
+
+def hermitian_normal_rows(dev, seed, nrows, nmodes, a=0.0, ws=None, fz=None, b=1.0, index_offset=0):
+    """(nrows, nmodes) complex128: a * ws * fz + b * e with e a conjugate-even standard complex normal row generated in the
+    kernel (efgp_hermitian_normal_rows; e is defined through `normal_fill(dev, seed, 2 * nrows, nmodes, index_offset)`).
+    ws (nmodes,) and fz (nrows, nmodes) go together or are both None (then the result is b * e).  ws and the rows of fz must be
+    conjugate-even (real, even spectral weights; transforms of real rows): the kernel reads their lower halves only and writes
+    the upper half of the result as the conjugate of the lower."""
+    nrows, nmodes = int(nrows), int(nmodes)
+    if (ws is None) != (fz is None):
+        raise ValueError("hermitian_normal_rows: ws and fz go together (both or neither)")
+    out = torch.empty((nrows, nmodes), dtype=_CD, device=dev)
+    wsc = fzc = None
+    if ws is not None:
+        wsc = _dc(ws.reshape(-1), dev, _CD)
+        fzc = _dc(fz.reshape(nrows, -1), dev, _CD)
+        if wsc.numel() != nmodes or fzc.shape[1] != nmodes:
+            raise ValueError(f"hermitian_normal_rows: ws has {wsc.numel()} and fz {fzc.shape[1]} entries per row, expected {nmodes}")
+    with _on(dev):
+        check(lib().efgp_hermitian_normal_rows(dev.index, int(seed) & (2 ** 64 - 1), _wrap_i64(index_offset), nrows, nmodes, float(a),
+                                               _ptr(wsc) if wsc is not None else None, _ptr(fzc) if fzc is not None else None,
+                                               float(b), _ptr(out), _stream(dev)), "efgp_hermitian_normal_rows")
+    return out
 
 
 def rademacher_fill(dev, seed, nbatch, npts, index_offset=0):

@@ -19,6 +19,7 @@ from __future__ import annotations
 import math
 import os
 import time
+import warnings
 from math import prod
 from typing import Dict, Optional, Tuple, Union
 
@@ -31,7 +32,7 @@ from cg import ConjugateGradients
 from kernels.kernel_params import GPParams
 from utils.kernels import get_xis
 
-from efgp_hip import NufftPlan, PointSet, ToeplitzOp, lanczos, lag_sums, variance_rhs, variance_contract, cg_solve, cg_solve_lazy, cg_solve_mean_async, cg_solve_mean_fused, vdot_real, compute_device, rademacher_fill, gradient_prepare, gradient_assemble
+from efgp_hip import NufftPlan, PointSet, ToeplitzOp, lanczos, lag_sums, variance_rhs, variance_contract, cg_solve, cg_solve_lazy, cg_solve_mean_async, cg_solve_mean_fused, vdot_real, compute_device, rademacher_fill, gradient_prepare, gradient_assemble, hermitian_normal_rows, normal_row_offset
 from efgp_hip.dist import PointShards
 
 TWO_PI = 2.0 * math.pi
@@ -1051,6 +1052,20 @@ def compute_prediction_variance(x_new, xis, ws, A_var, cg_tol, max_cg_iter, vari
 # ======================================================================================
 # the model (reference: efgpnd.py:336-1226)
 # ======================================================================================
+# Rows per batched pass of EFGPND.sample_paths (even: normals come in pairs).  A pass holds one complex fine grid and one int64
+# accumulator pair per TWO rows plus the CG vectors of every row: 64 rows keep that below ~100 MB on the 2-D grids (up to
+# 512 x 512 fine cells) and fill the batched CG; the 3-D fine grids (128^3 and beyond) are 100x larger per row.
+_SAMPLE_BLOCK = {1: 64, 2: 64, 3: 8}
+
+
+def _derive_seed(seed: int, stream: int) -> int:
+    """Seed of noise stream `stream` of a draw: the splitmix64 finaliser of (seed, stream) -- e1 and e2 never share a counter."""
+    z = (int(seed) + 0x9E3779B97F4A7C15 * (int(stream) + 1)) & (2 ** 64 - 1)
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & (2 ** 64 - 1)
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & (2 ** 64 - 1)
+    return z ^ (z >> 31)
+
+
 class EFGPND(nn.Module):
     """Equispaced-Fourier GP regression in d dimensions.
 
@@ -1126,6 +1141,8 @@ class EFGPND(nn.Module):
         self._devdata = None
         self._fit_state = None
         self._predict_plan = None
+        self._sample_plan = None
+        self._last_sample_stats = {}
         self._nan_scalar = None
         # shard_points: True = torch.distributed default group; an efgp_hip.RcclComm = the library's own RCCL communicator
         sp = self.opts.get("shard_points", False)
@@ -1428,8 +1445,145 @@ class EFGPND(nn.Module):
             return out_mean, var, lm
         return out_mean, var
 
-    def sample_posterior(self, x_new: torch.Tensor, nsamples: int):
-        """Dense O(N^3) posterior samples at x_new (small N only; reference: efgpnd.py:974-1022)."""
+    # -- function draws ----------------------------------------------------------------------------------
+    @property
+    def last_sample_stats(self) -> Dict:
+        """Seed, row count and per-row CG iteration counts of the last `sample_paths` call (reading them waits for its solves);
+        `cg_capped` lists the rows that reached `cg_max_iterations` without meeting the tolerance."""
+        st = dict(self._last_sample_stats)
+        if "cg_iters" in st:
+            st["cg_iters"] = [int(v) for its in st["cg_iters"] for v in its.rows]
+            st["cg_capped"] = [i for i, v in enumerate(st["cg_iters"]) if v >= st["cg_max_iterations"]]
+        return st
+
+    def sample_paths(self, x_new: torch.Tensor, nsamples: int, *, prior: bool = False, seed: Optional[int] = None,
+                     cg_tolerance: Optional[float] = None, return_state: bool = False):
+        """Draws of the latent function at x_new -> (nsamples, B), from the posterior (default) or the prior, in the weight space
+        of the equispaced features: with D = diag(ws), A = D F*F D + sigma^2 I and the weights' prior N(0, I),
+
+            w = beta + A^-1 (sigma D F* e1 + sigma^2 e2),   f(x*) = Re F_new (ws * w),
+
+        e1 ~ N(0, I_N) real and e2 a conjugate-even standard complex normal on the mode grid (the bracket has covariance
+        sigma^2 A, so w ~ N(beta, sigma^2 A^-1), the posterior of the weights).  One draw costs one type-1 transform of a noise
+        row generated inside the spreader (e1 never exists in memory), one Hermitian CG solve with the fit's operator and one
+        type-2 transform, all batched over blocks of `_SAMPLE_BLOCK` rows.  prior=True draws w = e2 alone: no pass over the
+        training points, no solve.
+
+        seed=None takes a 63-bit seed from torch's default generator (`torch.manual_seed` governs reproducibility); an integer
+        makes the call a pure function of (model, x_new, nsamples, seed).  Rows are numbered across blocks: the first k rows of a
+        larger call are the draws of a k-row call (to rounding).  return_state=True also returns a dict with `seed`, `weights`
+        (nsamples, M), `delta`, `rhs`, `cg_iters`, `cg_max_iterations` and `cg_capped` (posterior; None for the prior).
+
+        The noise right-hand sides excite every mode, not only the smooth ones of the data term, so their solves take about
+        sqrt(cond A) ln(2 / tol) / 2 iterations at worst (785-1104 measured at N = 1e6, tolerance 1e-4, where the fit takes 15):
+        opts["max_cg_iterations"] (default 1000) caps them.  Rows that reach the cap are returned as they stand; their indices
+        are in `last_sample_stats["cg_capped"]` (read on request: no synchronisation in the call) and in the state, and a
+        return_state=True call, which reads the counts anyway, warns about them.  The pass over the training points counts as
+        one for opts["point_layout"] = "auto": a first sample_paths call after a single fit builds the sorted layout."""
+        nsamples = int(nsamples)
+        if nsamples < 1:
+            raise ValueError(f"nsamples must be at least 1 (got {nsamples})")
+        if self.opts.get("shard_points", False):
+            raise NotImplementedError("sample_paths does not support opts['shard_points']: the sharded sampler needs an all-reduce "
+                                      "of the noise transform F* e1 over the ranks")
+        if x_new is None:
+            raise ValueError("x_new must be provided for sampling")
+        d_model = 1 if self.x.ndim == 1 else self.x.shape[1]
+        d_new = 1 if x_new.ndim == 1 else x_new.shape[1]
+        if d_new != d_model:
+            raise ValueError(f"x_new has {d_new} columns, the model was built on {d_model}")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        seed = int(seed)
+        self._compute_common_parameters()
+        st = self._fit_state
+        rdtype = self.x.dtype
+        dev = self._devdata["dev"]
+        xn = _dev_points(x_new, dev)
+        d, M = st["d"], st["ws"].numel()
+        shape = (st["mtot"],) * d
+        pkey = (xn.data_ptr(), tuple(xn.shape), xn._version, st["h"], float(self.nufft_eps))
+        if self._predict_plan is not None and self._predict_plan[0] == pkey:
+            plan_new = self._predict_plan[1]
+        else:
+            plan_new = NufftPlan(xn, st["h"], float(self.nufft_eps))
+            self._predict_plan = (pkey, plan_new)
+        seed_e1, seed_e2 = _derive_seed(seed, 1), _derive_seed(seed, 2)
+        block = _SAMPLE_BLOCK[d]
+        sig = st["sig"]
+        sols = []
+        if not prior:
+            tol = float(cg_tolerance) if cg_tolerance is not None else self.opts.get("cg_tolerance", 1e-4)
+            points = self._layout()
+            # kept while the grid spacing, the tolerance and the layout object stay what the plan was made with (a refit
+            # replaces _fit_state; what the plan depends on is h)
+            tol1 = min(float(self.nufft_eps), _CONV_TOL)
+            sp = self._sample_plan
+            if sp is None or sp[0] != (st["h"], tol1) or sp[2] is not points:
+                self._sample_plan = sp = ((st["h"], tol1), NufftPlan(self._devdata["x"], st["h"], tol1, points=points), points)
+            plan_x = sp[1]
+            max_iter = int(self.opts.get("max_cg_iterations", 1000))
+            diag = None
+            if self.opts.get("mean_cg_preconditioner", True):
+                cidx = _center_flat(st["v"])
+                diag, _ = gradient_prepare(st["ws"], None, st["v"].reshape(-1)[cidx:cidx + 1], sig, want_diag=True, want_rhs=False)
+            sroot = math.sqrt(sig)
+        outs = []
+        keep = dict(weights=[], delta=[], rhs=[]) if return_state else None
+        for r0 in range(0, nsamples, block):
+            nb = min(block, nsamples - r0)
+            if prior:
+                w = hermitian_normal_rows(dev, seed_e2, nb, M, a=0.0, b=1.0, index_offset=normal_row_offset(2 * r0))
+            else:
+                fz = plan_x.type1_normal(seed_e1, nb, shape, index_offset=normal_row_offset(r0)).reshape(nb, M)
+                rhs = hermitian_normal_rows(dev, seed_e2, nb, M, a=sroot, ws=st["ws"], fz=fz, b=sig,
+                                            index_offset=normal_row_offset(2 * r0))
+                delta, its = cg_solve_lazy(self._toeplitz._op, st["ws"], sig, 0, rhs, None, tol,
+                                           max_iter=max_iter, early_stop=True, diag=diag,
+                                           batched=True, hermitian=True)
+                its.settle()                         # reads the counts only where the solve may hold dead rows
+                sols.append(its)
+                # The solution of a conjugate-even system is conjugate-even.  The Hermitian kernels iterate on the full vector
+                # and control only its even part: over the ~1000 iterations these broad-spectrum right-hand sides take at
+                # N = 1e6 the odd part grows from rounding to 1e-5..1e-3 of the solution (the fit's 10-300 iterations never
+                # show it).  It drops out of Re F(ws w) anyway; projecting it out makes delta and the weights what they mean.
+                delta = delta.reshape(nb, M)
+                delta = 0.5 * (delta + delta.flip(1).conj())
+                w = delta + st["beta"].reshape(1, M)
+                if keep is not None:
+                    keep["delta"].append(delta)
+                    keep["rhs"].append(rhs)
+            if keep is not None:
+                keep["weights"].append(w)
+            outs.append(plan_new.type2(w, shape, real_only=True, batched=True, mode_scale=st["ws"]))
+        out = outs[0] if len(outs) == 1 else torch.cat(outs)       # one block: the transform's own output, no copy
+        self._last_sample_stats = dict(seed=seed, nsamples=nsamples, prior=bool(prior), blocks=-(-nsamples // block))
+        if not prior:
+            self._last_sample_stats["cg_iters"] = sols
+            self._last_sample_stats["cg_max_iterations"] = max_iter
+        res = out.to(device=self.device, dtype=rdtype)
+        if not return_state:
+            return res
+        state = dict(seed=seed, weights=torch.cat(keep["weights"]),
+                     delta=torch.cat(keep["delta"]) if not prior else None,
+                     rhs=torch.cat(keep["rhs"]) if not prior else None,
+                     cg_iters=None, cg_max_iterations=None, cg_capped=None)
+        if not prior:
+            stats = self.last_sample_stats
+            state.update(cg_iters=stats["cg_iters"], cg_max_iterations=max_iter, cg_capped=stats["cg_capped"])
+            if stats["cg_capped"]:
+                warnings.warn(f"sample_paths: {len(stats['cg_capped'])} of {nsamples} solves reached max_cg_iterations = {max_iter} "
+                              f"without meeting the tolerance {tol:g}; raise opts['max_cg_iterations']", RuntimeWarning, stacklevel=2)
+        return res, state
+
+    def sample_posterior(self, x_new: torch.Tensor, nsamples: int, method: str = "dense", seed: Optional[int] = None):
+        """Posterior samples at x_new as a numpy array (B, nsamples).  method="dense": the O(N^3) sampler of the reference
+        (small N only; efgpnd.py:974-1022), drawing from torch's default generator; method="efgp": `sample_paths`, which
+        scales like the fit (`seed` as there)."""
+        if method == "efgp":
+            return self.sample_paths(x_new, nsamples, seed=seed).T.detach().cpu().numpy()
+        if method != "dense":
+            raise ValueError(f"unknown sampling method {method!r}: 'dense' or 'efgp'")
         x = _as2d(self.x)
         xn = _as2d(x_new)
         k = self.kernel.kernel

@@ -134,6 +134,21 @@ int efgp_nufft_type1_rademacher(efgp_nufft_t* plan, uint64_t seed, int64_t index
 int efgp_rademacher_fill(int device, uint64_t seed, int64_t index_offset, int nbatch, int64_t npts, double* out,
                          void* stream);
 
+/* type 1 of standard-normal rows generated inside the spread kernel (the e1 ~ N(0, I_N) of a posterior draw never exists in
+ * memory):
+ *     out[b, k] = sum_n Z[b, n] exp(-i k . phi_n),   Z[2p, n] + i Z[2p + 1, n] = sqrt(-2 ln u1) exp(2 pi i u2),
+ *     u1 in (0, 1] and u2 in [0, 1) the 53-bit fractions of two hashed words of the counter (seed, pair p, n + index_offset):
+ * one Box-Muller evaluation per point serves two rows.  |Z| <= sqrt(106 ln 2) < 8.5717 by construction.  Row b does not depend on
+ * nbatch; pair p at index n is pair 0 at index n + p * 0xD1342543DE82EF95 in wrapping 64-bit arithmetic, so a caller that numbers
+ * rows across several calls passes index_offset + (first_row / 2) * that stride (first_row even).  The bits are unrelated to the
+ * Rademacher probes of the same seed.  Argument checks and the empty-plan result (zeros) are those of
+ * efgp_nufft_type1_rademacher.  efgp_normal_fill writes the very same Z[b, n] to memory (nbatch x npts doubles): the oracle of
+ * the fused transform (device log / sincos differ from a host's in the last bits; compare against this, not against host normals). */
+int efgp_nufft_type1_normal(efgp_nufft_t* plan, uint64_t seed, int64_t index_offset, int nbatch,
+                            const int64_t* n_modes, int modeord, void* out, void* stream);
+int efgp_normal_fill(int device, uint64_t seed, int64_t index_offset, int nbatch, int64_t npts, double* out,
+                     void* stream);
+
 /* Fused fit-time pass over the same points (efgpnd.py:786 and :789-790 / :1395-1421):
  *     out_y[k]    = sum_n y_n exp(-i k . phi_n),  k in the n_modes_y   box (CMCL order)
  *     out_ones[k] = sum_n     exp(-i k . phi_n),  k in the n_modes_one box (CMCL order)
@@ -381,6 +396,19 @@ int efgp_variance_rhs(int device, int dim, int64_t mtot, double h, const double*
                       void* stream);
 int efgp_variance_contract(int device, int dim, int64_t mtot, double h, const double* x_new, int64_t npts, const void* ws,
                            const void* gamma, double* out, void* stream);
+/* Rows on the symmetric mode box of nmodes = mtot^d entries (odd; flat index j, the negated frequency at nmodes - 1 - j) for the
+ * path sampler, one launch for all rows:
+ *     out[s, j] = a * ws[j] * fz[s, j] + b * e[s, j],
+ * e[s, .] a conjugate-even standard complex normal (E e e^H = I) defined through efgp_normal_fill: with p / q = rows 2s / 2s + 1
+ * of efgp_normal_fill(seed, index_offset, 2 nrows, nmodes), e[s, j] = (p[j] + i q[j]) / sqrt 2 for j below the centre,
+ * e[s, centre] = p[centre], and every entry above the centre is written as the conjugate of its mirror: the row is conjugate-even
+ * bit for bit (what efgp_cg_solve_hermitian expects).  fz: (nrows, nmodes) complex transforms of real rows (conjugate-even up to
+ * rounding: only the lower half and the real part of the centre are read); ws: (nmodes) complex and itself conjugate-even
+ * (ws[nmodes - 1 - j] = conj(ws[j]): the real, even spectral weights of a stationary kernel are) -- it too is read on the lower
+ * half only, so for any other ws the upper half is NOT a * ws * fz + b * e.  ws and fz may both be NULL:
+ * out = b * e (a = 0, b = 1 draws the weights of a prior sample). */
+int efgp_hermitian_normal_rows(int device, uint64_t seed, int64_t index_offset, int nrows, int64_t nmodes, double a, const void* ws,
+                               const void* fz, double b, void* out, void* stream);
 
 /* ---- Polya-Gamma estimators: the pointwise and M-scale passes around the weighted solves (pg_classifier.py) -----------------
  * efgp_pg_estep_update: one pass over the N points after the E-step's batched solve (:552-569, :252-257, :129-138):
