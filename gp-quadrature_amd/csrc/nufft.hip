@@ -433,6 +433,7 @@ struct ScaleJob {            // what fixed_scale_write needs besides max|c|
     int64_t per;
     double* scale;
     int sum_bits;
+    double cmax_mult = 1.0;  // the strengths are bounded by cmax_mult * max|c| (scaled generated normals: c = the per-point scale)
 };
 __device__ __forceinline__ void fixed_scale_write(double cmax, double floor_bound, int ones_channel, int64_t per,
                                                   double* __restrict__ scale, int sum_bits) {
@@ -516,7 +517,7 @@ __global__ __launch_bounds__(1024) void maxabs_kernel(const double* __restrict__
             __threadfence();
             const double cmax = __longlong_as_double((long long)atomicExch(out, 0ull));
             *ticket = 0u;
-            fixed_scale_write(cmax, job.floor_bound, job.ones_channel, job.per, job.scale, job.sum_bits);
+            fixed_scale_write(cmax * job.cmax_mult, job.floor_bound, job.ones_channel, job.per, job.scale, job.sum_bits);
         }
     }
 }
@@ -2897,18 +2898,23 @@ static int transform_fine(efgp_nufft_s* plan, const GridGeom& g, double2* fine, 
 // spread + reduce + FFT; leaves the transformed fine grids in SLOT_FINE
 static int spread_and_fft(efgp_nufft_s* plan, WindowSet* w, const double* c, int mode, int nbatch, int isign,
                           hipStream_t stream, double2** fine_out, unsigned long long seed = 0, int64_t index_offset = 0,
-                          const double** scale_out = nullptr, G2MRequest* req = nullptr) {
+                          const double** scale_out = nullptr, G2MRequest* req = nullptr, const double* point_scale = nullptr) {
     DeviceCtx* ctx = plan->ctx;
     const GridGeom g = make_geom(plan, w);
     if (scale_out) *scale_out = nullptr;
+    // generated normals times a per-point factor (point_scale, npts doubles by original index): |c| <= kNormalBound * max(point_scale),
+    // so the max pass runs over the N factors and its result is multiplied by the normals' bound on the device
+    const bool scaled = point_scale != nullptr && strength_is_normal(mode);
     const int channels = (mode == STR_COMPLEX || mode == STR_REAL_AND_ONES || mode == STR_REAL_PAIR || mode == STR_RNG_PAIR ||
                           mode == STR_NORMAL_PAIR) ? 2 : 1;
     // strengths read from memory need a max|c| pass for the fixed-point scale; generated / implicit ones are +-1
-    const bool need_max = (mode == STR_REAL || mode == STR_COMPLEX || mode == STR_REAL_AND_ONES || mode == STR_REAL_PAIR);
+    const bool need_max = (mode == STR_REAL || mode == STR_COMPLEX || mode == STR_REAL_AND_ONES || mode == STR_REAL_PAIR) || scaled;
     // generated normals are bounded by construction (kNormalBound): the scale is sized for that bound, no pass over data
-    const double floor_bound = strength_is_normal(mode) ? kNormalBound
+    const double floor_bound = scaled ? 0.0 : strength_is_normal(mode) ? kNormalBound
                                : (mode == STR_REAL_AND_ONES || mode == STR_ONES || mode == STR_RNG || mode == STR_RNG_PAIR) ? 1.0 : 0.0;
-    const int64_t nvals = (mode == STR_REAL_AND_ONES) ? plan->npts
+    const double* max_src = scaled ? point_scale : c;
+    const double max_mult = scaled ? kNormalBound : 1.0;
+    const int64_t nvals = (mode == STR_REAL_AND_ONES || scaled) ? plan->npts
                           : (int64_t)nbatch * plan->npts * ((mode == STR_COMPLEX || mode == STR_REAL_PAIR) ? 2 : 1);
     StrengthSrc src;
     src.c = c;
@@ -2916,6 +2922,7 @@ static int spread_and_fft(efgp_nufft_s* plan, WindowSet* w, const double* c, int
     src.mode = mode;
     src.seed = seed;
     src.index_offset = index_offset;
+    src.scale = scaled ? point_scale : nullptr;
     const size_t lds_bytes = (size_t)channels * (size_t)g.cells * sizeof(double);
     const bool use_lds = lds_bytes <= (size_t)ctx->max_lds && plan->npts > 0;
     // 2-D plans made on a per-model point layout (efgp_nufft_create_on): MFMA register accumulation over
@@ -2941,7 +2948,7 @@ static int spread_and_fft(efgp_nufft_s* plan, WindowSet* w, const double* c, int
         // the converting kernel below zeroes what it reads: back-to-back passes of this path need no memset launch
         if (known_zero < acc_bytes || slabs_before != (const void*)gacc) EFGP_HIP_CHECK(hipMemsetAsync(gacc, 0, acc_bytes, stream));
         // the global int64 grid sums over ALL points: the scale is bounded with N
-        ScaleJob job{floor_bound, mode == STR_REAL_AND_ONES ? 1 : 0, plan->npts, d_scale, 61};
+        ScaleJob job{floor_bound, mode == STR_REAL_AND_ONES ? 1 : 0, plan->npts, d_scale, 61, max_mult};
         if (need_max && ys && plan->points->d_values_max && mode == STR_REAL_AND_ONES) {
             // the fit-time pair on the attached targets: max|y|, N and the bit budget are fixed per model, so the scale block is
             // computed once per attach and kept with the layout (one launch less per fit)
@@ -2958,7 +2965,7 @@ static int spread_and_fft(efgp_nufft_s* plan, WindowSet* w, const double* c, int
                                (const unsigned long long*)plan->points->d_values_max, job);
         } else if (need_max) {
             const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((nvals + 8191) / 8192, 256));
-            hipLaunchKernelGGL(maxabs_kernel, dim3(blocks), dim3(1024), 0, stream, c, nvals, d_cmax,
+            hipLaunchKernelGGL(maxabs_kernel, dim3(blocks), dim3(1024), 0, stream, max_src, nvals, d_cmax,
                                (unsigned int*)(misc + 48), job);
         } else {
             // generated +-1 probes / implicit ones: the block depends on (floor, N, bit budget) only -- constant for the layout
@@ -3064,10 +3071,10 @@ static int spread_and_fft(efgp_nufft_s* plan, WindowSet* w, const double* c, int
         // the kernel that converts the accumulator clears what it reads: back-to-back passes need no memset launch
         if (known_zero < acc_bytes || slabs_before != (const void*)gacc) EFGP_HIP_CHECK(hipMemsetAsync(gacc, 0, acc_bytes, stream));
         // the global int64 grid sums over ALL points: bound the scale with N instead of points per workgroup
-        const ScaleJob job{floor_bound, mode == STR_REAL_AND_ONES ? 1 : 0, plan->npts, d_scale, 61};
+        const ScaleJob job{floor_bound, mode == STR_REAL_AND_ONES ? 1 : 0, plan->npts, d_scale, 61, max_mult};
         if (need_max) {
             const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((nvals + 8191) / 8192, 256));
-            hipLaunchKernelGGL(maxabs_kernel, dim3(blocks), dim3(1024), 0, stream, c, nvals, d_cmax,
+            hipLaunchKernelGGL(maxabs_kernel, dim3(blocks), dim3(1024), 0, stream, max_src, nvals, d_cmax,
                                (unsigned int*)(misc + 48), job);
         } else {
             hipLaunchKernelGGL(fixed_scale_kernel, dim3(1), dim3(64), 0, stream, job.floor_bound, job.ones_channel, job.per,
@@ -3143,10 +3150,10 @@ static int spread_and_fft(efgp_nufft_s* plan, WindowSet* w, const double* c, int
         // Otherwise the bound must hold for the SUM OVER ALL SLABS (reduce_slabs_kernel adds them in plain int64):
         // bounding only one workgroup's share let same-sign strengths (the all-ones channel, clustered points) wrap
         // the total, e.g. 1-D, N = 1e6, tol <= 1e-9: 512 slabs x 2^61 / 1954 points each.
-        const ScaleJob job{floor_bound, mode == STR_REAL_AND_ONES ? 1 : 0, raw48 ? per : plan->npts, d_scale, raw48 ? 46 : 61};
+        const ScaleJob job{floor_bound, mode == STR_REAL_AND_ONES ? 1 : 0, raw48 ? per : plan->npts, d_scale, raw48 ? 46 : 61, max_mult};
         if (need_max) {
             const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((nvals + 8191) / 8192, 256));
-            hipLaunchKernelGGL(maxabs_kernel, dim3(blocks), dim3(1024), 0, stream, c, nvals, d_cmax,
+            hipLaunchKernelGGL(maxabs_kernel, dim3(blocks), dim3(1024), 0, stream, max_src, nvals, d_cmax,
                                (unsigned int*)(misc + 48), job);
         } else {
             hipLaunchKernelGGL(fixed_scale_kernel, dim3(1), dim3(64), 0, stream, job.floor_bound, job.ones_channel, job.per,
@@ -3292,7 +3299,7 @@ int efgp_nufft_destroy(efgp_nufft_t* plan) {
 enum RowSource { ROWS_MEMORY = 0, ROWS_RADEMACHER = 1, ROWS_NORMAL = 2 };
 static int type1_real_rows(efgp_nufft_s* plan, WindowSet* w, const double* c, RowSource rows, unsigned long long seed,
                            int64_t index_offset, int nbatch, const int64_t* n_modes, int isign, int modeord, void* out,
-                           hipStream_t stream) {
+                           hipStream_t stream, const double* point_scale = nullptr) {
     int64_t total = 1;
     for (int a = 0; a < plan->dim; ++a) total *= n_modes[a];
     // Generated probes, odd count, 2-D: the last row rides as the real part of one more pair grid whose imaginary row (index nbatch)
@@ -3309,7 +3316,7 @@ static int type1_real_rows(efgp_nufft_s* plan, WindowSet* w, const double* c, Ro
         req.ma = make_modes(plan, w, n_modes, modeord);
         req.out_a = out;
         int rc = spread_and_fft(plan, w, c, rows == ROWS_NORMAL ? STR_NORMAL_PAIR : (rng ? STR_RNG_PAIR : STR_REAL_PAIR), npair, isign, stream, &fine, seed, index_offset, nullptr,
-                                &req);
+                                &req, point_scale);
         if (rc != EFGP_OK) return rc;
         // for isign = +1 the roles of k and -k swap in the Hermitian split; conjugating H handles both signs:
         // the split below assumes the forward (isign = -1) transform, which is what the reference uses for type 1
@@ -3327,7 +3334,7 @@ static int type1_real_rows(efgp_nufft_s* plan, WindowSet* w, const double* c, Ro
             // row `last` (even) is element 0 of pair last / 2: pair 0 at the point index shifted by (last / 2) * kRowStride
             rc = spread_and_fft(plan, w, nullptr, STR_NORMAL, 1, isign, stream, &fine, seed,
                                 (int64_t)((unsigned long long)index_offset + (unsigned long long)(last >> 1) * kRademacherRowStride), nullptr,
-                                &req);
+                                &req, point_scale);
         } else if (rng) {
             // STR_RNG takes the fine-grid index (0 here) as the row: row `last` of the same seed is row 0 at the point index shifted
             // by last * kRowStride (efgp_rademacher hashes row * kRowStride + index in wrapping 64-bit arithmetic)
@@ -3407,6 +3414,28 @@ int efgp_nufft_type1_normal(efgp_nufft_t* plan, uint64_t seed, int64_t index_off
     }
     return type1_real_rows(plan, w, nullptr, ROWS_NORMAL, (unsigned long long)seed, index_offset, nbatch, n_modes, -1, modeord, out,
                            stream);
+}
+
+int efgp_nufft_type1_normal_scaled(efgp_nufft_t* plan, uint64_t seed, int64_t index_offset, int nbatch, const double* point_scale,
+                                   const int64_t* n_modes, int modeord, void* out, void* stream_) {
+    EFGP_REQUIRE(plan && n_modes && out, "efgp_nufft_type1_normal_scaled: null argument");
+    EFGP_REQUIRE(nbatch >= 1, "efgp_nufft_type1_normal_scaled: nbatch must be >= 1");
+    for (int a = 0; a < plan->dim; ++a) EFGP_REQUIRE(n_modes[a] >= 1, "efgp_nufft_type1_normal_scaled: n_modes[%d] < 1", a);
+    EFGP_REQUIRE(plan->npts == 0 || point_scale, "efgp_nufft_type1_normal_scaled: null point_scale");
+    hipStream_t stream = (hipStream_t)stream_;
+    DeviceGuard guard(plan->device, (hipStream_t)stream_);
+    WindowSet* w = nullptr;
+    int rc = get_window(plan, n_modes, stream, &w);
+    if (rc != EFGP_OK) return rc;
+    if (plan->npts == 0) {
+        int64_t total = 1;
+        for (int a = 0; a < plan->dim; ++a) total *= n_modes[a];
+        EFGP_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)nbatch * total * sizeof(double2), stream));
+        return EFGP_OK;
+    }
+    // an all-zero scale: max = 0 sizes the accumulators as for |c| <= 1, every contribution is an exact zero
+    return type1_real_rows(plan, w, nullptr, ROWS_NORMAL, (unsigned long long)seed, index_offset, nbatch, n_modes, -1, modeord, out,
+                           stream, point_scale);
 }
 
 int efgp_normal_fill(int device, uint64_t seed, int64_t index_offset, int nbatch, int64_t npts, double* out, void* stream_) {

@@ -70,11 +70,14 @@ struct StrengthSrc {
     int mode;
     unsigned long long seed;
     int64_t index_offset;     // added to the point index for the RNG (global index of this shard's first point)
+    const double* scale = nullptr;   // normal modes only: per-point factor of the generated normals (original index), null = none
 };
 
 // strengths (c0, c1) of point `n` (original index) for fine grid `g`.  GEN = true serves the two normal modes and nothing else:
 // the spread kernels carry them as instantiations of their own, so the logarithm and the sincos cost the other modes nothing.
-template <bool GEN = false>
+// A set s.scale multiplies both normals of the point by s.scale[n] (one pointer test per wave; the unscaled modes skip the load and
+// the products).  APPLY_SCALE = false leaves that to a caller that has fetched the factor itself (spread_mfma.hip prefetches it).
+template <bool GEN = false, bool APPLY_SCALE = true>
 __device__ __forceinline__ void fetch_strength(const StrengthSrc& s, int g, int64_t n, double& c0, double& c1) {
     c0 = 1.0;
     c1 = 1.0;
@@ -85,6 +88,11 @@ __device__ __forceinline__ void fetch_strength(const StrengthSrc& s, int g, int6
         efgp_normal_pair(s.seed, pairs ? g : (g >> 1), (long long)((unsigned long long)n + (unsigned long long)s.index_offset), z0, z1);
         c0 = (pairs || !(g & 1)) ? z0 : z1;
         c1 = z1;
+        if (APPLY_SCALE && s.scale != nullptr) {
+            const double f = s.scale[n];
+            c0 *= f;
+            c1 *= f;
+        }
         return;
     }
     switch (s.mode) {

@@ -213,6 +213,9 @@ __device__ __forceinline__ PointIn load_point(const MfmaSpreadArgs& a, int batch
         // of the batch before (the kernel sits at its register bound already)
         r.idx = a.perm[p];
         r.c0 = r.c1 = 0.0;
+        // the per-point factor of scaled normals is gathered through the permutation here, one batch ahead like the index: 8 bytes
+        // that fly during the MFMA phase of the batch before (two more live VGPRs; this instantiation has 256 to spend)
+        if (a.src.scale != nullptr) r.c0 = a.src.scale[r.idx];
     } else if (SORTED) {
         r.c0 = a.ys[p];
         r.c1 = 1.0;
@@ -290,7 +293,11 @@ __global__ __launch_bounds__(64 * kMfmaMaxWaves, (HB == 1 && !GEN) ? 3 : 2) void
             }
             double c0 = cur.c0, c1 = a.channels == 1 ? 0.0 : cur.c1;
             if (GEN) {
-                fetch_strength<true>(a.src, batch, cur.idx, c0, c1);
+                fetch_strength<true, false>(a.src, batch, cur.idx, c0, c1);
+                if (a.src.scale != nullptr) {                                 // wave-uniform
+                    c0 *= cur.c0;
+                    c1 *= cur.c0;
+                }
                 if (a.channels == 1) c1 = 0.0;
             }
             if (!valid) {                                                     // tail lanes repeat the last point with zero strength

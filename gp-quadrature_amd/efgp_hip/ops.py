@@ -214,6 +214,19 @@ class NufftPlan:
                   "efgp_nufft_type1_normal")
         return out
 
+    def type1_normal_scaled(self, seed, nbatch, n_modes, scale, index_offset=0, modeord=0):
+        """F* (scale .* Z[b]) for the normals of `type1_normal` and a per-point factor `scale` ((N,) float64, finite, >= 0, in the
+        order of x) -> (B, *n_modes); the scaled rows are never materialised (efgp_nufft_type1_normal_scaled)."""
+        sc = _dc(scale, self.dev, _RD).reshape(-1)
+        if sc.numel() != self.npts:
+            raise ValueError(f"type1_normal_scaled: scale has {sc.numel()} entries, the plan has {self.npts} points")
+        out = torch.empty((int(nbatch),) + tuple(int(m) for m in n_modes), dtype=_CD, device=self.dev)
+        with _on(self.dev):
+            check(lib().efgp_nufft_type1_normal_scaled(self._h, int(seed) & (2 ** 64 - 1), _wrap_i64(index_offset), int(nbatch),
+                                                       _ptr(sc), _i64(n_modes), int(modeord), _ptr(out), _stream(self.dev)),
+                  "efgp_nufft_type1_normal_scaled")
+        return out
+
     def type1_pair(self, y, n_modes_y, n_modes_one):
         """One pass over the points: (F* y on n_modes_y, F* 1 on n_modes_one)."""
         yy = _dc(y, self.dev, _RD)

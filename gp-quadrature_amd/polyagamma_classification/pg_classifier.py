@@ -21,6 +21,7 @@ import inspect
 import math
 import os
 import sys
+import warnings
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if _PKG not in sys.path:
@@ -460,6 +461,104 @@ class _BasePolyagammaGPEstimator:
             mean, variance = self._latent_mean(xn), self._latent_variance(xn)
         return self._response_mean(mean, variance).cpu().numpy()
 
+    # -- function draws ----------------------------------------------------------------------------------------------------
+    @property
+    def last_sample_stats(self):
+        """Seed, row count and per-row CG iteration counts of the last `sample_latent` call (reading them waits for its solves);
+        `cg_capped` lists the rows that reached `cg_max_iterations` without meeting the tolerance."""
+        st = dict(getattr(self, "_last_sample_stats", None) or {})
+        if "cg_iters" in st:
+            st["cg_iters"] = [int(v) for its in st["cg_iters"] for v in its.rows]
+            st["cg_capped"] = [i for i, v in enumerate(st["cg_iters"]) if v >= st["cg_max_iterations"]]
+        return st
+
+    def sample_latent(self, X, n_samples, *, seed=None, cg_tolerance=None, max_cg_iterations=2000, return_state=False):
+        """Joint draws of the latent function at the rows of X from the fitted variational posterior -> float64 array
+        (n_samples, n).  The weights' posterior is N(m, A^-1), A = I + D T_w D with D = diag(ws) and T_w the Toeplitz operator of
+        F* diag(delta) F for the fitted PG expectation delta, so
+
+            u = A^-1 (D F*(sqrt(delta) .* e1) + e2),   f(x*) = Re F_new(ws .* (ws .* beta_mean + u)),
+
+        e1 ~ N(0, I_N) real and e2 a conjugate-even standard complex normal on the mode grid: the bracket has covariance A,
+        u ~ N(0, A^-1), and the draws have mean `_latent_mean` and covariance Phi_new D A^-1 D Phi_new^H.  The draws use the
+        E-step's scaling D = ws; the exact `predictive_variance` solves with the clamped D_s, which differs from D only on modes
+        with ws^2 < 1e-14 mean(ws^2), far below the draws' own solve tolerance.
+
+        Per call: sqrt(delta) once and one plan over X.  Per block of `efgpnd._SAMPLE_BLOCK[d]` rows: one type-1 transform of
+        normals generated and scaled inside the spreader (`NufftPlan.type1_normal_scaled`; neither e1 nor sqrt(delta) .* e1
+        exists in memory), one right-hand-side kernel (`hermitian_normal_rows`), one batched Hermitian CG solve from zero with
+        the fit's operator `_op_pred` (no Jacobi diagonal: the E-step solves the same system without one) and one batched
+        type 2.  The solutions are projected onto their conjugate-even part, as `EFGPND.sample_paths` does.
+
+        seed=None takes a 63-bit seed from torch's default generator (`torch.manual_seed` governs reproducibility); an integer
+        makes the call a pure function of (fit, X, n_samples, seed).  Rows are numbered across blocks: the first k rows of a
+        larger call are the draws of a k-row call (to rounding).  cg_tolerance defaults to the estimator's `cg_tol`.  Rows that
+        reach max_cg_iterations are returned as they stand; their indices are in `last_sample_stats["cg_capped"]` (read on
+        request) and in the state, and a return_state=True call warns about them.  return_state=True also returns a dict of
+        device tensors and counts: `seed`, `weights` (ws .* beta_mean + u), `delta` (u), `rhs`, `cg_iters`, `cg_max_iterations`,
+        `cg_capped`.
+
+        Training inputs get no special case: `decision_function` returns the E-step's stochastic `posterior_mean_` there, while
+        the draws always go through `beta_mean` (their mean on the training inputs is the predictive latent mean).  No fitted
+        attribute changes and nothing is refitted."""
+        n_samples = int(n_samples)
+        if n_samples < 1:
+            raise ValueError(f"n_samples must be at least 1 (got {n_samples})")
+        max_iter = int(max_cg_iterations)
+        if max_iter < 1:
+            raise ValueError(f"max_cg_iterations must be at least 1 (got {max_iter})")
+        self._check_fitted()
+        X_arr = _check_array(X, self.n_features_in_)
+        import efgpnd
+        from efgp_hip.ops import NufftPlan, cg_solve_lazy, hermitian_normal_rows, normal_row_offset
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        seed = int(seed)
+        spec, dev = self._spec, self._dev
+        M, shape = spec.M, spec.shape
+        tol = float(self.cg_tol if cg_tolerance is None else cg_tolerance)
+        xn = self._device_points(X_arr)
+        n = xn.shape[0]
+        plan_new = NufftPlan(xn, spec.h, self.nufft_eps) if n else None
+        root = torch.sqrt(self._delta)
+        mean_w = (spec.ws * self._beta_mean).reshape(1, M)
+        seed_e1, seed_e2 = efgpnd._derive_seed(seed, 1), efgpnd._derive_seed(seed, 2)
+        block = efgpnd._SAMPLE_BLOCK[spec.d]
+        outs, sols = [], []
+        keep = dict(weights=[], delta=[], rhs=[]) if return_state else None
+        for r0 in range(0, n_samples, block):
+            nb = min(block, n_samples - r0)
+            fz = spec.plan.type1_normal_scaled(seed_e1, nb, shape, root, index_offset=normal_row_offset(r0)).reshape(nb, M)
+            rhs = hermitian_normal_rows(dev, seed_e2, nb, M, a=1.0, ws=spec.ws, fz=fz, b=1.0, index_offset=normal_row_offset(2 * r0))
+            u, its = cg_solve_lazy(self._op_pred, spec.ws, 1.0, 1, rhs, None, tol, max_iter=max_iter, early_stop=True, batched=True,
+                                   hermitian=True)
+            its.settle()                             # reads the counts only where the solve may hold dead rows
+            sols.append(its)
+            # the Hermitian kernels control only the even part of the iterate; the odd part that rounding grows over a long solve
+            # drops out of Re F(ws w) anyway, projecting it out makes delta and the weights what they mean (EFGPND.sample_paths)
+            u = u.reshape(nb, M)
+            u = 0.5 * (u + u.flip(1).conj())
+            w = u + mean_w
+            if keep is not None:
+                keep["weights"].append(w)
+                keep["delta"].append(u)
+                keep["rhs"].append(rhs)
+            outs.append(plan_new.type2(w, shape, real_only=True, batched=True, mode_scale=spec.ws) if n
+                        else torch.empty((nb, 0), dtype=torch.float64, device=dev))
+        out = outs[0] if len(outs) == 1 else torch.cat(outs)
+        self._last_sample_stats = dict(seed=seed, n_samples=n_samples, blocks=-(-n_samples // block), cg_iters=sols,
+                                       cg_max_iterations=max_iter)
+        res = out.reshape(n_samples, n).cpu().numpy()
+        if not return_state:
+            return res
+        stats = self.last_sample_stats
+        state = dict(seed=seed, weights=torch.cat(keep["weights"]), delta=torch.cat(keep["delta"]), rhs=torch.cat(keep["rhs"]),
+                     cg_iters=stats["cg_iters"], cg_max_iterations=max_iter, cg_capped=stats["cg_capped"])
+        if stats["cg_capped"]:
+            warnings.warn(f"sample_latent: {len(stats['cg_capped'])} of {n_samples} solves reached max_cg_iterations = {max_iter} "
+                          f"without meeting the tolerance {tol:g}; raise max_cg_iterations", RuntimeWarning, stacklevel=2)
+        return res, state
+
     # -- likelihood hooks: the ones a likelihood without parameters of its own does not need ------------------------------------
     def _refresh_likelihood(self):
         pass
@@ -524,6 +623,12 @@ class PolyagammaGPClassifier(_BasePolyagammaGPEstimator):
     def predict_proba(self, X):
         p1 = np.clip(self.predict_response_mean(X), 1e-8, 1.0 - 1e-8)
         return np.column_stack([1.0 - p1, p1])
+
+    def sample_proba(self, X, n_samples, *, seed=None):
+        """sigmoid(f) of every draw of `sample_latent(X, n_samples, seed=seed)` -> (n_samples, n): joint draws of the probability
+        of `classes_[1]`."""
+        f = torch.from_numpy(self.sample_latent(X, n_samples, seed=seed))
+        return torch.sigmoid(f).numpy()
 
     def predict(self, X):
         self._check_fitted()
@@ -677,6 +782,12 @@ class PolyagammaGPNegativeBinomialRegressor(_BasePolyagammaGPEstimator):
 
     def predict_mean_count(self, X):
         return self.predict_response_mean(X)
+
+    def sample_mean_count(self, X, n_samples, *, seed=None):
+        """r exp(f) of every draw of `sample_latent(X, n_samples, seed=seed)` with the fitted total count r -> (n_samples, n): joint
+        draws of the mean count, whose Gaussian expectation is `negative_binomial_gaussian_mean`."""
+        f = torch.from_numpy(self.sample_latent(X, n_samples, seed=seed))
+        return (self.total_count_ * torch.exp(f)).numpy()
 
     def predict(self, X):
         return self.predict_mean_count(X)

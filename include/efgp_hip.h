@@ -149,6 +149,18 @@ int efgp_nufft_type1_normal(efgp_nufft_t* plan, uint64_t seed, int64_t index_off
 int efgp_normal_fill(int device, uint64_t seed, int64_t index_offset, int nbatch, int64_t npts, double* out,
                      void* stream);
 
+/* efgp_nufft_type1_normal with a per-point factor on the generated normals (the data-side noise F* diag(sqrt(delta)) e1 of a
+ * Polya-Gamma posterior draw, without the row sqrt(delta) .* e1 ever existing in memory):
+ *     out[b, k] = sum_n point_scale[n] Z[b, n] exp(-i k . phi_n),
+ * Z[b, n] exactly the normal of efgp_nufft_type1_normal / efgp_normal_fill for the same (seed, index_offset): pairing, row numbering
+ * across calls and index_offset keep their meaning.  point_scale: npts device doubles indexed by the ORIGINAL point index (the order
+ * of x), finite and >= 0, 16-byte aligned (the max pass reads it in pairs, as it reads the strength rows of efgp_nufft_type1).  The fixed-point accumulators are sized for
+ * |c| <= 8.5717 max_n point_scale[n]; the maximum is taken on the device (one pass over npts values, no host read-back).  An all-zero
+ * scale and an empty plan give zeros.  Argument checks are those of efgp_nufft_type1_normal; a null point_scale on a non-empty plan
+ * is refused by name. */
+int efgp_nufft_type1_normal_scaled(efgp_nufft_t* plan, uint64_t seed, int64_t index_offset, int nbatch, const double* point_scale,
+                                   const int64_t* n_modes, int modeord, void* out, void* stream);
+
 /* Fused fit-time pass over the same points (efgpnd.py:786 and :789-790 / :1395-1421):
  *     out_y[k]    = sum_n y_n exp(-i k . phi_n),  k in the n_modes_y   box (CMCL order)
  *     out_ones[k] = sum_n     exp(-i k . phi_n),  k in the n_modes_one box (CMCL order)
