@@ -2317,11 +2317,8 @@ bool persistent_cg_eligible(const ToepGeom& tg) {
     return true;
 }
 
-int persistent_cg_launch(const ToepGeom& tg, const double2* const* twiddles, const double2* vhat, const double2* ws,
-                         const double* diag, double sigmasq, int variant, double tol, int early_stop, int batched,
-                         int max_iter, const double2* b, double2* x, int rows, int* d_iters, hipStream_t stream,
-                         const double* diag_scale, int b_times_ws, int zero_x0, const LanczosOut* lz, int hermitian,
-                         const Herm48Operands* h48, const double2* x0, const MeanFusedOperands* fuse) {
+int persistent_cg_launch(const ToepGeom& tg, const double2* const* twiddles, const double2* vhat, const Herm48Operands* h48,
+                         const CgSolve& s, int* d_iters, hipStream_t stream, const LanczosOut* lz, const MeanFusedOperands* fuse) {
     using namespace pcg;
     Args a;
     a.ws_out = nullptr;
@@ -2474,22 +2471,23 @@ int persistent_cg_launch(const ToepGeom& tg, const double2* const* twiddles, con
             p->tw_glob = g.tw[p->dim];
         }
     }
-    a.ws = ws;
-    a.diag = diag;
-    a.diag_scale = diag_scale;
-    a.b_times_ws = b_times_ws;
-    a.zero_x0 = zero_x0;
-    a.x0 = x0 ? x0 : x;
+    a.ws = s.ws;
+    a.diag = s.diag;
+    a.diag_scale = s.diag_scale;
+    a.b_times_ws = s.b_times_ws;
+    a.zero_x0 = s.zero_x0;
+    a.x0 = s.x0 ? s.x0 : s.x;
     a.vhat = vhat;
-    a.sigmasq = sigmasq;
-    a.variant = variant;
-    a.tol = tol;
-    a.early_stop = early_stop;
-    a.batched = batched;
-    a.max_iter = max_iter;
-    a.b = b;
-    a.x = x;
+    a.sigmasq = s.sigmasq;
+    a.variant = s.variant;
+    a.tol = s.tol;
+    a.early_stop = s.early_stop;
+    a.batched = s.batched;
+    a.max_iter = s.max_iter;
+    a.b = s.b;
+    a.x = s.x;
     a.iters = d_iters;
+    const int rows = s.nbatch, variant = s.variant;
     a.hist = cg_history().buf;
     a.hist_cap = cg_history().capacity;
     a.lz_steps = lz ? lz->steps : 0;
@@ -2518,10 +2516,10 @@ int persistent_cg_launch(const ToepGeom& tg, const double2* const* twiddles, con
     }
     const bool fast64 = tg.d == 2 && g.F[0] == 64 && g.F[1] == 64 && g.n[0] == g.n[1] && g.n[0] <= 32 &&
                         std::getenv("EFGP_NO_CG64") == nullptr;
-    const bool herm64 = fast64 && hermitian && !lz && (g.n[0] & 1) && g.n[0] <= 31 && std::getenv("EFGP_NO_CG_HERM") == nullptr;
+    const bool herm64 = fast64 && s.hermitian && !lz && (g.n[0] & 1) && g.n[0] <= 31 && std::getenv("EFGP_NO_CG_HERM") == nullptr;
     // blocks of up to 23 x 23 modes: the smallest circulant grid, 48 x 48 (the operator holds a second spectrum for it)
     const bool herm48 = herm64 && h48 != nullptr && h48->vhat != nullptr && g.n[0] <= 23 && std::getenv("EFGP_NO_CG48") == nullptr;
-    if (fuse != nullptr && !(herm48 && variant == 0 && rows == 1 && zero_x0 && b_times_ws && !diag)) {
+    if (fuse != nullptr && !(herm48 && variant == 0 && rows == 1 && s.zero_x0 && s.b_times_ws && !s.diag)) {
         set_error("fused mean solve: the system is not a cold-start 48 x 48 Hermitian mean solve");
         return EFGP_EUNSUPPORTED;
     }

@@ -2473,20 +2473,54 @@ static int ensure_deferred_spectra(efgp_toeplitz_s* op, hipStream_t stream) {
     return EFGP_OK;
 }
 
-// geometry, twiddles and spectrum the single-launch CG kernels use for this operator (made first if it was deferred)
-static int cg_operands(efgp_toeplitz_s* op, hipStream_t stream, const ToepGeom** g, const double2* const** tw, const double2** vhat) {
-    const int rc = ensure_deferred_spectra(op, stream);
-    if (rc != EFGP_OK) return rc;
-    if (op->cg64) {
-        *g = &op->g_cg;
-        *tw = (const double2* const*)op->tw_cg;
-        *vhat = op->vhat_cg;
-    } else {
-        *g = &op->g;
-        *tw = (const double2* const*)op->tw;
-        *vhat = op->vhat;
+// geometry, twiddles and spectrum the single-launch kernels use for this operator: the 64 x 64 embedding where there is one
+struct CgGrid {
+    const ToepGeom& g;
+    const double2* const* tw;
+    const double2* vhat;
+};
+static CgGrid cg_grid(const efgp_toeplitz_s* op) {
+    if (op->cg64) return {op->g_cg, (const double2* const*)op->tw_cg, op->vhat_cg};
+    return {op->g, (const double2* const*)op->tw, op->vhat};
+}
+
+// the two single-launch solves an operator may offer, each with its test hooks
+static bool persistent_usable(const efgp_toeplitz_s* op) { return op->persistent_ok && std::getenv("EFGP_NO_PERSISTENT_CG") == nullptr; }
+static bool coop_usable(const efgp_toeplitz_s* op) {
+    return op->lines_ok && std::getenv("EFGP_NO_CG_COOP") == nullptr && std::getenv("EFGP_NO_CG_LINES") == nullptr;
+}
+
+// the arguments every exported solve shares, in the C ABI's order, with the default iteration cap
+static CgSolve make_solve(const efgp_toeplitz_s* op, const void* ws, double sigmasq, int variant, const double* diag, const void* b, void* x,
+                          int nbatch, double tol, int max_iter, int early_stop, int batched) {
+    CgSolve s;
+    s.ws = (const double2*)ws;
+    s.sigmasq = sigmasq;
+    s.variant = variant;
+    s.diag = diag;
+    s.b = (const double2*)b;
+    s.x = (double2*)x;
+    s.nbatch = nbatch;
+    s.tol = tol;
+    s.max_iter = max_iter;
+    s.early_stop = early_stop;
+    s.batched = batched;
+    s.default_max_iter(op->g.M);
+    return s;
+}
+
+// Enqueues the persistent single-launch solve of `s` on the operator's CG grid (persistent_usable(op)); counts go to d_iters
+// (device, s.nbatch ints).  lz: Lanczos mode.  fuse: the fused mean solve, which makes the 48 x 48 spectrum itself and reads no
+// other -- what is deferred stays deferred.
+static int enqueue_persistent(efgp_toeplitz_s* op, const CgSolve& s, int* d_iters, hipStream_t stream, const LanczosOut* lz = nullptr,
+                              const MeanFusedOperands* fuse = nullptr) {
+    KernelTimer timer("cg_persistent", stream);
+    if (!fuse) {
+        const int rc = ensure_deferred_spectra(op, stream);
+        if (rc != EFGP_OK) return rc;
     }
-    return EFGP_OK;
+    const CgGrid q = cg_grid(op);
+    return persistent_cg_launch(q.g, q.tw, fuse ? nullptr : q.vhat, op->h48.vhat ? &op->h48 : nullptr, s, d_iters, stream, lz, fuse);
 }
 
 namespace efgp {
@@ -2556,6 +2590,468 @@ static bool ensure_centred_spectrum(efgp_toeplitz_s* op, hipStream_t stream) {
     return true;
 }
 
+// ---- the multi-launch solver ----------------------------------------------------------------------------------------------------
+constexpr int kPollEvery = 8;        // iterations per burst: enqueued (or replayed) together, then the host reads the scalars
+
+// The pruned line-transform kernels keep 2 x lpb lines of F + 1 elements and the F twiddles in LDS: the lines that fit, and the
+// bytes of lpb of them
+static int64_t line_lds_fit(const DeviceCtx* ctx, int64_t F) {
+    return ((int64_t)ctx->max_lds / (int64_t)sizeof(double2) - F) / (2 * (F + 1));
+}
+static size_t line_lds_bytes(int lpb, int64_t F) { return ((size_t)2 * lpb * (size_t)(F + 1) + (size_t)F) * sizeof(double2); }
+// Lines per workgroup of the reducing line kernels, from `lpb`: doubled while the workgroups (one partial sum each) outnumber
+// kCgBlocksMax, then for more than 8 systems up to `many_cap`.  Every workgroup of the reducing kernels pays a device-scope fence
+// (an L2 write-back, ~2 us each, serialised per XCD): few systems -> many small workgroups for parallelism, many systems -> few
+// large ones (fewer reduction fences).  Both limits must hold, LDS and partial sums (found at full size: mtot = 57, F = 128 asked
+// for 64 lines per block = 266 KB of LDS).
+static int lines_per_block(int lpb, int64_t nlines, int64_t fit, int rows, int many_cap) {
+    while ((nlines + lpb - 1) / lpb > kCgBlocksMax && lpb * 2 <= fit) lpb <<= 1;
+    if (rows > 8) {
+        while (lpb * 2 <= fit && lpb < many_cap) lpb <<= 1;
+    }
+    return lpb;
+}
+
+// How an iteration of the multi-launch solver applies the operator to p: the chosen kind with its kernel arguments (their copy of
+// the CgArgs, `c`, is set at every enqueue) and LDS bytes
+struct OperatorApply {
+    enum Kind {
+        kFft,        // pad + FFT + multiply + FFT (circulant) and the dot kernel
+        kLines2,     // 2-D mid-size grids: three launches of pruned in-LDS line transforms instead of pad + rocFFT + multiply
+        kLines3,     // 3-D: the same with five pruned line passes
+        kLines3H     // Hermitian 3-D systems: the planes k0 >= 0 only (cg3h_* kernels)
+    } kind = kFft;
+    LineArgs la;
+    Line3Args l3;
+    Line3HArgs l3h;
+    size_t lds[3] = {0, 0, 0};       // of the kernels that transform along dimension q
+};
+
+// The Hermitian 3-D set-up on top of the general one: the real centred spectrum on first use, the check of the data (once per group
+// of rows, through the pinned `host`), the half block in `a`
+static int setup_apply_herm3(efgp_toeplitz_s* op, CgArgs& a, int rows, int* host, hipStream_t stream, OperatorApply* ap) {
+    DeviceCtx* ctx = op->ctx;
+    const ToepGeom& g = op->g;
+    if (!op->vc3) {
+        op->vc3 = (double*)pool_alloc(ctx, (size_t)g.Ftot * sizeof(double));
+        if (!op->vc3) return EFGP_ENOMEM;
+        hipLaunchKernelGGL(center_spectrum3_real_kernel, dim3((unsigned)((g.Ftot + 255) / 256)), dim3(256), 0, stream, op->vhat, op->tw[0],
+                           op->tw[1], op->tw[2], (int)g.n[0], (int)g.n[1], (int)g.n[2], (int)g.F[0], (int)g.F[1], (int)g.F[2], op->vc3);
+        EFGP_HIP_CHECK(hipGetLastError());
+    }
+    double* chk_buf = (double*)scratch(ctx, SLOT_MISC, 64);
+    if (!chk_buf) return EFGP_ENOMEM;
+    EFGP_HIP_CHECK(hipMemsetAsync(chk_buf, 0, 64, stream));
+    hipLaunchKernelGGL(cg_herm_check_kernel, dim3(256), dim3(kVecThreads), 0, stream, a.b, (const double2*)a.x, a.ws, g.M, rows, chk_buf);
+    EFGP_HIP_CHECK(hipGetLastError());
+    EFGP_HIP_CHECK(hipMemcpyAsync(host, chk_buf, 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
+    EFGP_HIP_CHECK(stream_wait(stream));
+    double hv[3];
+    std::memcpy(hv, host, sizeof(hv));
+    if (!(hv[0] <= 1e-16 * hv[1]) || hv[2] > 0.0) {
+        set_error("efgp_cg_solve_hermitian: right-hand side / start vector not conjugate-even or ws not real and even");
+        return EFGP_EINVAL;
+    }
+    const int64_t nh = (g.n[0] + 1) / 2;
+    a.v_off = (nh - 1) * g.n[1] * g.n[2];
+    a.v_len = nh * g.n[1] * g.n[2];
+    a.v_w1 = g.n[1] * g.n[2];
+    Line3HArgs& l3h = ap->l3h;
+    l3h.vc = op->vc3;
+    for (int q = 0; q < 3; ++q) l3h.tw[q] = op->tw[q];
+    l3h.b1 = a.pad_out;
+    l3h.b2 = a.pad_out + (int64_t)rows * nh * g.n[1] * g.F[2];
+    const int64_t nlines = nh * g.n[1];
+    const int64_t fit = line_lds_fit(ctx, g.F[2]);
+    int lpb = lines_per_block(8, nlines, fit, rows, 64);
+    if (rows >= 3 && lpb < 16 && 32 <= fit) lpb = 16;          // measured at mtot 57: 125 vs 133 us per iteration of 3 systems
+    auto knob = [](const char* name, int dflt) {
+        const char* e = std::getenv(name);
+        int v = e ? std::atoi(e) : dflt;
+        int p2 = 1;
+        while (p2 * 2 <= v) p2 <<= 1;
+        return std::max(1, p2);
+    };
+    if (std::getenv("EFGP_CG3_LC")) {
+        lpb = knob("EFGP_CG3_LC", lpb);
+        while ((nlines + lpb - 1) / lpb > kCgBlocksMax) lpb <<= 1;
+    }
+    l3h.lpb_c = lpb;
+    l3h.lpb_s = (int)std::min<int64_t>(knob("EFGP_CG3_LS", 16), g.F[2] / 2);
+    l3h.lpb_m = (int)std::min<int64_t>(knob("EFGP_CG3_LM", rows >= 3 ? 32 : 16), g.F[2] / 2);      // 3 systems: 124.6 vs 132.6 us
+    l3h.nblk_lines = (int)((nlines + lpb - 1) / lpb);
+    ap->lds[2] = line_lds_bytes(lpb, g.F[2]);
+    ap->lds[1] = line_lds_bytes(l3h.lpb_s, g.F[1]);
+    ap->lds[0] = line_lds_bytes(l3h.lpb_m, g.F[0]);
+    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3h_fwd2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[2]));
+    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3h_inv2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[2]));
+    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3h_dim1_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[1]));
+    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3h_dim1_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[1]));
+    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3h_mid0_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[0]));
+    a.nblk = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(std::min(kCgBlocksMax, knob("EFGP_CG_NBLK", 128)), (a.v_len + kVecThreads - 1) / kVecThreads),
+                                                        std::max<int64_t>(1, 1024 / rows)));
+    ap->kind = OperatorApply::kLines3H;
+    return EFGP_OK;
+}
+
+// Chooses how the iterations of this group of `rows` systems apply the operator and sets it up (the 2-D line kernels need the
+// reference grid's spectrum; the Hermitian 3-D ones change the block `a` describes)
+static int setup_apply(efgp_toeplitz_s* op, const CgSolve& s, CgArgs& a, int rows, int* host, hipStream_t stream, OperatorApply* ap) {
+    DeviceCtx* ctx = op->ctx;
+    const ToepGeom& g = op->g;
+    if (std::getenv("EFGP_NO_CG_LINES") != nullptr) return EFGP_OK;
+    if (op->lines_ok) {
+        const int rc = ensure_reference_spectrum(op, stream);
+        if (rc != EFGP_OK) return rc;
+        LineArgs& la = ap->la;
+        la.vhat = op->vhat;
+        la.tw0 = op->tw[0];
+        la.tw1 = op->tw[1];
+        la.b1 = a.pad_out;                                                     // [rows][n0][F1] fits: Ftot >= 2 n0 F1
+        la.b2 = a.pad_out + (int64_t)rows * g.n[0] * g.F[1];
+        la.lpb = lines_per_block(4, g.n[0], line_lds_fit(ctx, std::max(g.F[0], g.F[1])), rows, 32);
+        la.nblk_rows = (int)((g.n[0] + la.lpb - 1) / la.lpb);
+        ap->lds[1] = line_lds_bytes(la.lpb, g.F[1]);
+        ap->lds[0] = line_lds_bytes(la.lpb, g.F[0]);
+        EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg_rows_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[1]));
+        EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg_rows_inv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[1]));
+        EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg_cols_mid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[0]));
+        ap->kind = OperatorApply::kLines2;
+        return EFGP_OK;
+    }
+    if (!op->lines3_ok) return EFGP_OK;
+    const int64_t nlines = g.n[0] * g.n[1];
+    const int64_t fit = line_lds_fit(ctx, g.F[2]);
+    int64_t lmax = 16;
+    while (lmax * 2 <= fit) lmax <<= 1;
+    if (fit < 16 || (nlines + lmax - 1) / lmax > kCgBlocksMax) return EFGP_OK;      // no lines-per-block count meets both limits
+    Line3Args& l3 = ap->l3;
+    l3.vhat = op->vhat;
+    for (int q = 0; q < 3; ++q) l3.tw[q] = op->tw[q];
+    l3.b1 = a.pad_out;
+    l3.b2 = a.pad_out + (int64_t)rows * nlines * g.F[2];
+    l3.lpb_c = lines_per_block(16, nlines, fit, rows, 64);
+    l3.lpb_s = 16;
+    l3.nblk_lines = (int)((nlines + l3.lpb_c - 1) / l3.lpb_c);
+    ap->lds[2] = line_lds_bytes(l3.lpb_c, g.F[2]);
+    for (int q = 0; q < 2; ++q) ap->lds[q] = line_lds_bytes(l3.lpb_s, g.F[q]);
+    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3_fwd2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[2]));
+    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3_inv2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[2]));
+    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3_dim1_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[1]));
+    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3_dim1_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[1]));
+    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3_mid0_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[0]));
+    ap->kind = OperatorApply::kLines3;
+    if (s.hermitian && (g.n[0] & 1) && (g.n[1] & 1) && (g.n[2] & 1) && g.n[0] >= 3 && std::getenv("EFGP_NO_CG_HERM3") == nullptr)
+        return setup_apply_herm3(op, a, rows, host, stream, ap);
+    return EFGP_OK;
+}
+
+// one CG iteration of `slots` systems: A p by the chosen kind, then the fused update
+static int enqueue_iteration(efgp_toeplitz_s* op, OperatorApply& ap, const CgArgs& a, int slots, hipStream_t stream) {
+    const ToepGeom& g = op->g;
+    switch (ap.kind) {
+    case OperatorApply::kLines3H: {
+        Line3HArgs& l3h = ap.l3h;
+        l3h.c = a;
+        const unsigned nhp = (unsigned)((g.n[0] + 1) / 2);
+        const unsigned gs = (unsigned)(g.F[2] / l3h.lpb_s), gp = (unsigned)(g.F[2] / 2 / l3h.lpb_m);
+        hipLaunchKernelGGL(cg3h_fwd2_kernel, dim3(l3h.nblk_lines, slots), dim3(kLineThreads), ap.lds[2], stream, l3h);
+        hipLaunchKernelGGL((cg3h_dim1_kernel<0>), dim3(nhp * gs, slots), dim3(kLineThreads), ap.lds[1], stream, l3h);
+        hipLaunchKernelGGL(cg3h_mid0_kernel, dim3((unsigned)g.F[1] * gp, slots), dim3(kLineThreads), ap.lds[0], stream, l3h);
+        hipLaunchKernelGGL((cg3h_dim1_kernel<1>), dim3(nhp * gs, slots), dim3(kLineThreads), ap.lds[1], stream, l3h);
+        hipLaunchKernelGGL(cg3h_inv2_kernel, dim3(l3h.nblk_lines, slots), dim3(kLineThreads), ap.lds[2], stream, l3h);
+        break;
+    }
+    case OperatorApply::kLines3: {
+        Line3Args& l3 = ap.l3;
+        l3.c = a;
+        const unsigned gs = (unsigned)(g.F[2] / l3.lpb_s);
+        hipLaunchKernelGGL(cg3_fwd2_kernel, dim3(l3.nblk_lines, slots), dim3(kLineThreads), ap.lds[2], stream, l3);
+        hipLaunchKernelGGL((cg3_dim1_kernel<0>), dim3((unsigned)g.n[0] * gs, slots), dim3(kLineThreads), ap.lds[1], stream, l3);
+        hipLaunchKernelGGL(cg3_mid0_kernel, dim3((unsigned)g.F[1] * gs, slots), dim3(kLineThreads), ap.lds[0], stream, l3);
+        hipLaunchKernelGGL((cg3_dim1_kernel<1>), dim3((unsigned)g.n[0] * gs, slots), dim3(kLineThreads), ap.lds[1], stream, l3);
+        hipLaunchKernelGGL(cg3_inv2_kernel, dim3(l3.nblk_lines, slots), dim3(kLineThreads), ap.lds[2], stream, l3);
+        break;
+    }
+    case OperatorApply::kLines2: {
+        LineArgs& la = ap.la;
+        la.c = a;
+        hipLaunchKernelGGL(cg_rows_fwd_kernel, dim3(la.nblk_rows, slots), dim3(kLineThreads), ap.lds[1], stream, la);
+        hipLaunchKernelGGL(cg_cols_mid_kernel, dim3((unsigned)(g.F[1] / la.lpb), slots), dim3(kLineThreads), ap.lds[0], stream, la);
+        hipLaunchKernelGGL(cg_rows_inv_kernel, dim3(la.nblk_rows, slots), dim3(kLineThreads), ap.lds[1], stream, la);
+        break;
+    }
+    case OperatorApply::kFft: {
+        hipLaunchKernelGGL(cg_pad_kernel, grid_for(g.Ftot, slots, kVecThreads), dim3(kVecThreads), 0, stream, a);
+        EFGP_HIP_CHECK(hipGetLastError());
+        const int rc = circulant(op, a.pad_out, slots, stream);
+        if (rc != EFGP_OK) return rc;
+        hipLaunchKernelGGL(cg_dot_kernel, dim3(a.nblk, slots), dim3(kVecThreads), 0, stream, a);
+        break;
+    }
+    }
+    hipLaunchKernelGGL(cg_axpy_kernel, dim3(a.nblk, slots), dim3(kVecThreads), 0, stream, a);
+    EFGP_HIP_CHECK(hipGetLastError());
+    return EFGP_OK;
+}
+
+// The replayed burst.  One iteration = 5 launches of ours + two rocFFT executions (~11 kernels): enqueueing them one by one costs
+// the host ~300 us per iteration (measured, 3-D 64^3), far more than the GPU needs.  A full burst is therefore captured ONCE into a
+// hipGraph per (slots, row map) state and replayed with one launch.  Owns the instantiated graph: every return path destroys it.
+struct BurstGraph {
+    efgp_toeplitz_s* op;
+    hipStream_t stream;
+    bool usable;                     // false: kernel timing on, EFGP_NO_CG_GRAPH, or this runtime cannot capture the sequence
+    hipGraphExec_t exec = nullptr;
+    int slots = -1;                  // the state `exec` was built for
+    const int* rows = nullptr;
+    BurstGraph(efgp_toeplitz_s* op_, hipStream_t stream_)
+        : op(op_), stream(stream_), usable(!timing_enabled() && std::getenv("EFGP_NO_CG_GRAPH") == nullptr) {}
+    BurstGraph(const BurstGraph&) = delete;
+    BurstGraph& operator=(const BurstGraph&) = delete;
+    ~BurstGraph() {
+        if (!exec) return;
+        TraceSpan span_destroy("hipGraphExecDestroy");
+        (void)hipGraphExecDestroy(exec);
+    }
+
+    // captures and instantiates a full burst for this state; on failure `usable` goes false and nothing is held
+    template <class Enqueue>
+    int build(int slots_now, const int* rows_now, Enqueue& enqueue) {
+        TraceSpan span_build("graph build (plan + capture + instantiate)");
+        const ToepGeom& g = op->g;
+        hipGraph_t graph = nullptr;
+        // make sure the FFT plan exists and is bound to the stream before capturing
+        int rc;
+        if (own_fft_supported(g.d, g.F)) {
+            rc = own_fft_prepare(op->ctx, g.d, g.F, stream);
+        } else {
+            hipfftHandle fh_unused;
+            rc = fft_plan(op->ctx, g.d, g.F, slots_now, stream, &fh_unused);
+        }
+        if (rc != EFGP_OK) return rc;
+        bool ok = hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
+        if (ok) {
+            int rcap = EFGP_OK;
+            for (int k = 0; k < kPollEvery && rcap == EFGP_OK; ++k) rcap = enqueue();
+            const hipError_t ee = hipStreamEndCapture(stream, &graph);
+            ok = rcap == EFGP_OK && ee == hipSuccess && graph != nullptr;
+        }
+        if (ok) ok = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
+        if (graph) (void)hipGraphDestroy(graph);
+        if (!ok) {
+            (void)hipGetLastError();
+            exec = nullptr;
+            usable = false;            // this runtime cannot capture the sequence: enqueue directly
+        } else {
+            slots = slots_now;
+            rows = rows_now;
+        }
+        return EFGP_OK;
+    }
+
+    // `burst` iterations of `slots_now` slots behind the row map `rows_now`: a full burst replays the graph (rebuilt when the state
+    // changed); the tail of a solve, and every burst when graphs are not usable, is enqueued directly
+    template <class Enqueue>
+    int launch(int slots_now, const int* rows_now, int burst, Enqueue enqueue) {
+        if (usable && burst == kPollEvery) {
+            if (exec && (slots != slots_now || rows != rows_now)) {
+                (void)hipGraphExecDestroy(exec);
+                exec = nullptr;
+            }
+            if (!exec) {
+                const int rc = build(slots_now, rows_now, enqueue);
+                if (rc != EFGP_OK) return rc;
+            }
+            if (exec) {
+                TraceSpan span_launch("hipGraphLaunch");
+                EFGP_HIP_CHECK(hipGraphLaunch(exec, stream));
+                return EFGP_OK;
+            }
+        }
+        for (int k = 0; k < burst; ++k) {
+            KernelTimer timer("cg_iteration", stream);
+            const int rc = enqueue();
+            if (rc != EFGP_OK) return rc;
+        }
+        return EFGP_OK;
+    }
+};
+
+// The rows of one group that still iterate.  Until the first row leaves, slot i is row i and no map is used.
+struct ActiveRows {
+    int rows;
+    int n_active;
+    bool compacted = false;
+    int last_active_it = 0;          // number of iterations in which at least one row was active
+    std::vector<int> active;
+    std::vector<CgRowScalars> hsc;   // the scalars as last polled
+    explicit ActiveRows(int rows_) : rows(rows_), n_active(rows_), active(rows_), hsc(rows_) {
+        for (int i = 0; i < rows; ++i) active[i] = i;
+    }
+    // FFT batch = number of slots (bucketed to a power of two to bound the number of plans)
+    int slots() const {
+        if (!compacted) return n_active;
+        int p2 = 1;
+        while (p2 < n_active) p2 <<= 1;
+        return std::min(p2, rows);
+    }
+};
+
+// Reads the scalars of every row (the wait orders the host behind the burst), rebuilds the active list and, when rows have left,
+// uploads the slot -> row map to d_rows and points a.rows at it.  Returns the new active count, or a negative error.
+static int poll_and_compact(ActiveRows& st, CgArgs& a, int* d_rows, int* host, hipStream_t stream) {
+    {
+        TraceSpan span_poll("poll (D2H scalars + stream synchronize)");
+        // into the context's PINNED buffer (a pageable destination is staged by the runtime on every call)
+        EFGP_HIP_CHECK(hipMemcpyAsync(host, a.sc, (size_t)st.rows * sizeof(CgRowScalars), hipMemcpyDeviceToHost, stream));
+        EFGP_HIP_CHECK(stream_wait(stream));
+        std::memcpy(st.hsc.data(), host, (size_t)st.rows * sizeof(CgRowScalars));
+    }
+    int new_active = 0;
+    for (int i = 0; i < st.rows; ++i) {
+        if (st.hsc[i].active) st.active[new_active++] = i;
+        st.last_active_it = std::max(st.last_active_it, st.hsc[i].iters);
+    }
+    if ((new_active != st.n_active || !st.compacted) && new_active > 0 && new_active < st.rows) {
+        int p2 = 1;
+        while (p2 < new_active) p2 <<= 1;
+        const int nslots = std::min(p2, st.rows);
+        std::vector<int> map(nslots, -1);
+        for (int i = 0; i < new_active; ++i) map[i] = st.active[i];
+        std::memcpy(host, map.data(), nslots * sizeof(int));
+        EFGP_HIP_CHECK(hipMemcpyAsync(d_rows, host, nslots * sizeof(int), hipMemcpyHostToDevice, stream));
+        EFGP_HIP_CHECK(stream_wait(stream));
+        a.rows = d_rows;
+        st.compacted = true;
+    }
+    st.n_active = new_active;
+    return new_active;
+}
+
+// One group of `rows` systems (from row r0 of the solve) whose padded grids fit the scratch: lay out the scratch, initialise, then
+// bursts of iterations with a poll and a compaction behind each.  st->hsc holds the final scalars.
+static int solve_group(efgp_toeplitz_s* op, const CgSolve& s, int64_t r0, ActiveRows* st, hipStream_t stream) {
+    DeviceCtx* ctx = op->ctx;
+    const ToepGeom g = op->g;
+    const int rows = st->rows;
+    double2* pad = (double2*)scratch(ctx, SLOT_TOEP_PAD, (size_t)rows * (size_t)g.Ftot * sizeof(double2));
+    double2* vec = (double2*)scratch(ctx, SLOT_CG_VEC, (size_t)3 * rows * (size_t)g.M * sizeof(double2));
+    // scalars | status (64 B) + slot->row map | arrival counters | per-workgroup partial sums
+    const size_t off_status = ((size_t)rows * sizeof(CgRowScalars) + 63) & ~size_t(63);
+    const size_t off_counter = off_status + 64 + (((size_t)rows * sizeof(int) + 63) & ~size_t(63));
+    const size_t off_partial = off_counter + (((size_t)2 * rows * sizeof(int) + 63) & ~size_t(63));
+    const size_t sc_bytes = off_partial + (size_t)rows * 3 * kCgBlocksMax * sizeof(double);
+    char* scb = (char*)scratch(ctx, SLOT_CG_SCALARS, sc_bytes);
+    int* host = pinned_host(ctx, (size_t)rows * sizeof(CgRowScalars) + 64);
+    if (!pad || !vec || !scb || !host) return EFGP_ENOMEM;
+    CgArgs a;
+    a.g = g;
+    a.ws = s.ws;
+    a.diag = s.diag;
+    a.sigmasq = s.sigmasq;
+    a.variant = s.variant;
+    a.tol = s.tol;
+    a.early_stop = s.early_stop;
+    a.batched = s.batched;
+    a.b = s.b + r0 * g.M;
+    a.x = s.x + r0 * g.M;
+    a.r = vec;
+    a.p = vec + (int64_t)rows * g.M;
+    a.ap = vec + (int64_t)2 * rows * g.M;
+    a.pad = pad;
+    a.pad_out = pad;
+    a.rows = nullptr;
+    a.hist = r0 == 0 ? cg_history().buf : nullptr;
+    a.hist_cap = cg_history().capacity;
+    a.sc = (CgRowScalars*)scb;
+    a.status = (int*)(scb + off_status);
+    int* d_rows = a.status + 16;
+    a.counter = (int*)(scb + off_counter);
+    a.partial = (double*)(scb + off_partial);
+    a.v_off = 0;
+    a.v_len = g.M;
+    a.v_w1 = g.M;
+    a.nblk = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(64 /* update kernels: measured optimum */, (g.M + kVecThreads - 1) / kVecThreads),
+                                                        std::max<int64_t>(1, 1024 / rows)));
+    EFGP_HIP_CHECK(hipMemsetAsync(a.status, 0, off_partial - off_status, stream));      // status, map, counters
+
+    // r0 = b - A x0
+    hipLaunchKernelGGL(pad_scale_kernel, grid_for(g.Ftot, rows, kVecThreads), dim3(kVecThreads), 0, stream, g,
+                       (const double2*)a.x, g.M, a.ws, (const int*)nullptr, (const int*)nullptr, pad, 1.0);
+    EFGP_HIP_CHECK(hipGetLastError());
+    int rc = circulant(op, pad, rows, stream);
+    if (rc != EFGP_OK) return rc;
+    hipLaunchKernelGGL(cg_init_kernel, dim3(a.nblk, rows), dim3(kVecThreads), 0, stream, a);
+    EFGP_HIP_CHECK(hipGetLastError());
+
+    OperatorApply ap;
+    rc = setup_apply(op, s, a, rows, host, stream, &ap);
+    if (rc != EFGP_OK) return rc;
+    // iteration loop; active rows are compacted on the host whenever the status is polled
+    BurstGraph graph(op, stream);
+    for (int it = 0; it < s.max_iter && st->n_active > 0;) {
+        const int burst = std::min(kPollEvery, s.max_iter - it);
+        const int slots = st->slots();
+        rc = graph.launch(slots, a.rows, burst, [&]() { return enqueue_iteration(op, ap, a, slots, stream); });
+        if (rc != EFGP_OK) return rc;
+        it += burst;
+        rc = poll_and_compact(*st, a, d_rows, host, stream);
+        if (rc < 0) return rc;
+    }
+    if (ap.kind == OperatorApply::kLines3H) {          // the planes k0 < 0 of the solutions
+        CgArgs am = a;
+        am.rows = nullptr;
+        hipLaunchKernelGGL(cg3h_mirror_kernel, dim3(64, rows), dim3(kVecThreads), 0, stream, am);
+        EFGP_HIP_CHECK(hipGetLastError());
+        EFGP_HIP_CHECK(stream_wait(stream));
+    }
+    return EFGP_OK;
+}
+
+// The multi-launch solve of s.nbatch systems on any grid; returns when they are solved.  The counts follow the reference's two
+// conventions (cg.py:152 single; cg.py:193-199,243 batched: +1 for the terminating pass).
+static int solve_multi_launch(efgp_toeplitz_s* op, const CgSolve& s, int* iters_out, int* row_iters_out, hipStream_t stream) {
+    DeviceCtx* ctx = op->ctx;
+    // The iteration bursts are replayed as hipGraphs, which cannot be captured on the legacy default stream:
+    // run the multi-kernel solve on a side stream ordered after the caller's stream (the final poll of every group
+    // synchronises the host with it, so later work on the caller's stream is ordered after the solve).
+    if (!timing_enabled() && std::getenv("EFGP_NO_CG_GRAPH") == nullptr) {
+        if (!ctx->aux_stream) {
+            if (hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking) != hipSuccess ||
+                hipEventCreateWithFlags(&ctx->aux_event, hipEventDisableTiming) != hipSuccess) {
+                (void)hipGetLastError();
+                ctx->aux_stream = nullptr;
+            }
+        }
+        if (ctx->aux_stream) {
+            EFGP_HIP_CHECK(hipEventRecord(ctx->aux_event, stream));
+            EFGP_HIP_CHECK(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_event, 0));
+            stream = ctx->aux_stream;
+        }
+    }
+    // rows are processed in groups whose padded grids fit ~512 MB of scratch
+    const int64_t group_cap = std::max<int64_t>(1, (int64_t)(512ll << 20) / (op->g.Ftot * (int64_t)sizeof(double2)));
+    int global_iters = 0;
+    for (int64_t r0 = 0; r0 < s.nbatch; r0 += group_cap) {
+        ActiveRows st((int)std::min<int64_t>(group_cap, s.nbatch - r0));
+        const int rc = solve_group(op, s, r0, &st, stream);
+        if (rc != EFGP_OK) return rc;
+        int group_iters;
+        if (!s.batched) {
+            group_iters = st.hsc[0].iters;       // (max_iter >= 1 and rows >= 1: at least one burst ran and was polled)
+        } else {
+            group_iters = st.last_active_it;
+            if (st.n_active == 0 && st.last_active_it < s.max_iter) group_iters = st.last_active_it + 1;
+        }
+        if (row_iters_out)
+            for (int i = 0; i < st.rows; ++i) row_iters_out[r0 + i] = st.hsc[i].iters;
+        global_iters = std::max(global_iters, group_iters);
+    }
+    if (iters_out) *iters_out = global_iters;
+    return EFGP_OK;
+}
+
 }  // namespace efgp
 
 extern "C" {
@@ -2590,7 +3086,7 @@ int efgp_toeplitz_create_ex(efgp_toeplitz_t** op_out, int device, int dim, const
     }
     op->vhat = (double2*)pool_alloc(ctx, (size_t)op->g.Ftot * sizeof(double2));
     if (!op->vhat) {
-        delete op;
+        efgp_toeplitz_destroy(op);
         return EFGP_ENOMEM;
     }
     // vhat = FFT(zero-padded v) / Ftot.  Reuse the pad kernel with n := L, i.e. a geometry whose block is L.
@@ -2652,16 +3148,14 @@ int efgp_toeplitz_create_ex(efgp_toeplitz_t** op_out, int device, int dim, const
                            op->vhat, 1.0 / (double)op->g.Ftot);   // the inverse transform's 1/Ftot, folded in before the FFT
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
-            pool_free(ctx, op->vhat, (size_t)op->g.Ftot * sizeof(double2));
-            delete op;
+            efgp_toeplitz_destroy(op);          // vhat, and vhat48 / v_keep where they were taken
             set_error("efgp_toeplitz_create: pad launch failed: %s", hipGetErrorString(e));
             return EFGP_EHIP;
         }
         rc = fft_c2c(ctx, dim, op->g.F, 1, op->vhat, true, stream);
     }
     if (rc != EFGP_OK) {
-        pool_free(ctx, op->vhat, (size_t)op->g.Ftot * sizeof(double2));
-        delete op;
+        efgp_toeplitz_destroy(op);
         return rc;
     }
     op->persistent_ok = persistent_cg_eligible(op->g);
@@ -2677,30 +3171,12 @@ int efgp_toeplitz_create_ex(efgp_toeplitz_t** op_out, int device, int dim, const
     }
     if (op->persistent_ok || op->lines_ok || op->lines3_ok) {
         for (int a = 0; a < dim; ++a) {
-            const int64_t n = op->g.F[a];
-            auto it = ctx->twiddles.find(n);
-            if (it != ctx->twiddles.end()) {
-                op->tw[a] = (double2*)it->second;
-                continue;
-            }
-            std::vector<double2> tw((size_t)n);
-            const long double two_pi = 2.0L * acosl(-1.0L);
-            for (int64_t q = 0; q < n; ++q) {
-                long double ang = -two_pi * (long double)q / (long double)n;
-                tw[(size_t)q] = make_double2((double)cosl(ang), (double)sinl(ang));
-            }
-            double2* dtw = nullptr;
-            if (hipMalloc((void**)&dtw, (size_t)n * sizeof(double2)) != hipSuccess ||
-                hipMemcpyAsync(dtw, tw.data(), (size_t)n * sizeof(double2), hipMemcpyHostToDevice, stream) != hipSuccess ||
-                hipStreamSynchronize(stream) != hipSuccess) {
-                if (dtw) (void)hipFree(dtw);
-                op->persistent_ok = false;
-                op->lines_ok = false;
-                op->lines3_ok = false;
-                break;
-            }
-            ctx->twiddles[n] = dtw;
-            op->tw[a] = dtw;
+            op->tw[a] = twiddle_table_for(ctx, op->g.F[a], stream);
+            if (op->tw[a]) continue;
+            op->persistent_ok = false;
+            op->lines_ok = false;
+            op->lines3_ok = false;
+            break;
         }
     }
     if (op->lines_ok && std::getenv("EFGP_NO_COOP_SMALL") == nullptr) {
@@ -2766,19 +3242,8 @@ int efgp_toeplitz_create_ex(efgp_toeplitz_t** op_out, int device, int dim, const
         op->vhat_cg = (double2*)pool_alloc(ctx, (size_t)4096 * sizeof(double2));
         bool ok = op->vhat_cg != nullptr;
         if (ok) {
-            auto it = ctx->twiddles.find(64);
-            if (it == ctx->twiddles.end()) {
-                std::vector<double2> tw(64);
-                const long double two_pi = 2.0L * acosl(-1.0L);
-                for (int q = 0; q < 64; ++q) tw[(size_t)q] = make_double2((double)cosl(-two_pi * q / 64.0L), (double)sinl(-two_pi * q / 64.0L));
-                double2* dtw = nullptr;
-                ok = hipMalloc((void**)&dtw, 64 * sizeof(double2)) == hipSuccess &&
-                     hipMemcpyAsync(dtw, tw.data(), 64 * sizeof(double2), hipMemcpyHostToDevice, stream) == hipSuccess &&
-                     hipStreamSynchronize(stream) == hipSuccess;
-                if (ok) ctx->twiddles[64] = dtw;
-                else if (dtw) (void)hipFree(dtw);
-            }
-            if (ok) op->tw_cg[0] = op->tw_cg[1] = (double2*)ctx->twiddles[64];
+            op->tw_cg[0] = op->tw_cg[1] = twiddle_table_for(ctx, 64, stream);
+            ok = op->tw_cg[0] != nullptr;
         }
         if (ok) {
             if (op->vhat48 && !made48 && defer_pair) {
@@ -2838,7 +3303,7 @@ int efgp_toeplitz_fft_shape(efgp_toeplitz_t* op, int64_t* shape_out) {
 
 int efgp_toeplitz_single_launch_solves(efgp_toeplitz_t* op) {
     EFGP_REQUIRE(op, "efgp_toeplitz_single_launch_solves: null argument");
-    return (op->persistent_ok && std::getenv("EFGP_NO_PERSISTENT_CG") == nullptr) ? 1 : 0;
+    return persistent_usable(op) ? 1 : 0;
 }
 
 int efgp_toeplitz_cg_shape(efgp_toeplitz_t* op, int hermitian, int64_t* shape_out) {
@@ -2884,12 +3349,10 @@ int efgp_toeplitz_apply_scaled(efgp_toeplitz_t* op, const void* x, int x_is_real
     EFGP_REQUIRE(x != y, "efgp_toeplitz_apply_scaled: x and y must not alias");
     hipStream_t stream = (hipStream_t)stream_;
     DeviceGuard guard(op->device, (hipStream_t)stream_);
-    const ToepGeom* gq;
-    const double2* const* twq;
-    const double2* vq;
-    if (const int rc_ops = cg_operands(op, stream, &gq, &twq, &vq)) return rc_ops;
-    if (toeplitz_apply_fused_eligible(*gq))
-        return toeplitz_apply_fused_launch(*gq, twq[0], vq, (const double2*)pre, (const double2*)post, x, x_is_real, (double2*)y, nbatch,
+    if (const int rc_ops = ensure_deferred_spectra(op, stream)) return rc_ops;
+    const CgGrid q = cg_grid(op);
+    if (toeplitz_apply_fused_eligible(q.g))
+        return toeplitz_apply_fused_launch(q.g, q.tw[0], q.vhat, (const double2*)pre, (const double2*)post, x, x_is_real, (double2*)y, nbatch,
                                            stream);
     const int64_t max_rows = std::max<int64_t>(1, (int64_t)(256ll << 20) / (op->g.Ftot * (int64_t)sizeof(double2)));
     for (int64_t r0 = 0; r0 < nbatch; r0 += max_rows) {
@@ -2917,12 +3380,10 @@ int efgp_internal_apply_scaled(efgp_toeplitz_s* op, const void* x, int x_is_real
     if (pre == nullptr || pre_stride == 1) return efgp_toeplitz_apply_scaled(op, x, x_is_real, nbatch, pre, post, y, stream);
     EFGP_REQUIRE(op && x && y && nbatch >= 1 && x != y && pre_stride >= 1, "efgp_internal_apply_scaled: bad argument");
     DeviceGuard guard(op->device, stream);
-    const ToepGeom* gq;
-    const double2* const* twq;
-    const double2* vq;
-    if (const int rc_ops = cg_operands(op, stream, &gq, &twq, &vq)) return rc_ops;
-    if (!toeplitz_apply_fused_eligible(*gq)) return EFGP_EUNSUPPORTED;
-    return toeplitz_apply_fused_launch(*gq, twq[0], vq, (const double2*)pre, (const double2*)post, x, x_is_real, (double2*)y, nbatch, stream,
+    if (const int rc_ops = ensure_deferred_spectra(op, stream)) return rc_ops;
+    const CgGrid q = cg_grid(op);
+    if (!toeplitz_apply_fused_eligible(q.g)) return EFGP_EUNSUPPORTED;
+    return toeplitz_apply_fused_launch(q.g, q.tw[0], q.vhat, (const double2*)pre, (const double2*)post, x, x_is_real, (double2*)y, nbatch, stream,
                                        pre_stride);
 }
 
@@ -2932,17 +3393,15 @@ int efgp_internal_cg_single_launch(efgp_toeplitz_s* op, const void* ws, double s
                                    int hermitian, const void* x0) {
     EFGP_REQUIRE(op && ws && b && x && row_iters_dev && nbatch >= 1, "efgp_internal_cg_single_launch: bad argument");
     EFGP_REQUIRE(batched_semantics || nbatch == 1, "efgp_internal_cg_single_launch: single-system semantics need nbatch == 1");
-    if (!op->persistent_ok || std::getenv("EFGP_NO_PERSISTENT_CG") != nullptr) return EFGP_EUNSUPPORTED;
+    if (!persistent_usable(op)) return EFGP_EUNSUPPORTED;
     DeviceGuard guard(op->device, stream);
-    if (max_iter <= 0) max_iter = (int)std::min<int64_t>(2 * op->g.M, 2000000000);
-    KernelTimer timer("cg_persistent", stream);
-    const ToepGeom* gq;
-    const double2* const* twq;
-    const double2* vq;
-    if (const int rc_ops = cg_operands(op, stream, &gq, &twq, &vq)) return rc_ops;
-    return persistent_cg_launch(*gq, twq, vq, (const double2*)ws, diag, sigmasq, variant, tol, early_stop, batched_semantics, max_iter,
-                                (const double2*)b, (double2*)x, nbatch, row_iters_dev, stream, diag ? nullptr : diag_scale, b_times_ws, zero_x0,
-                                nullptr, hermitian, op->h48.vhat ? &op->h48 : nullptr, (const double2*)x0);
+    CgSolve s = make_solve(op, ws, sigmasq, variant, diag, b, x, nbatch, tol, max_iter, early_stop, batched_semantics);
+    s.diag_scale = diag ? nullptr : diag_scale;
+    s.b_times_ws = b_times_ws;
+    s.zero_x0 = zero_x0;
+    s.hermitian = hermitian;
+    s.x0 = (const double2*)x0;
+    return enqueue_persistent(op, s, row_iters_dev, stream);
 }
 
 // Enqueues the cooperative solve of `nbatch` systems on a 2-D 128^2..512^2 grid (cg_coop2d_kernel).  Few systems: G = 32-64
@@ -2957,16 +3416,14 @@ struct CoopInfo {
     int dbg = 0;
     bool herm = false;
 };
-static int coop_enqueue(efgp_toeplitz_s* op, const void* ws, double sigmasq, int variant, const double* precond_diag, const void* b,
-                        void* x, int nbatch, double tol, int max_iter, int early_stop, int batched_semantics, int* d_iters,
-                        hipStream_t stream, CoopInfo* info, int nan_on_dead, int hermitian = 0, const double* diag_scale = nullptr,
-                        int b_times_ws = 0, int zero_x0 = 0) {
+static int coop_enqueue(efgp_toeplitz_s* op, const CgSolve& s, int* d_iters, hipStream_t stream, CoopInfo* info, int nan_on_dead) {
+    const int nbatch = s.nbatch;
     DeviceCtx* ctx = op->ctx;
     const bool small = op->coop_small && std::getenv("EFGP_NO_COOP_SMALL") == nullptr;
     const ToepGeom g = small ? op->g_co : op->g;
     const int F0 = (int)g.F[0], F1 = (int)g.F[1], n0 = (int)g.n[0], n1 = (int)g.n[1];
     // Hermitian systems (the caller's promise, checked by the kernel): rows k0 >= 0 only, column pairs (cg_coop2d_herm_kernel)
-    const bool herm = hermitian && (n0 & 1) && (n1 & 1) && n0 >= 3 && std::getenv("EFGP_NO_CG_COOP_HERM") == nullptr;
+    const bool herm = s.hermitian && (n0 & 1) && (n1 & 1) && n0 >= 3 && std::getenv("EFGP_NO_CG_COOP_HERM") == nullptr;
     const int nrow = herm ? (n0 + 1) / 2 : n0;            // rows of the mode block the workgroups share out
     const int ncol = herm ? F1 / 2 : F1;                  // column lines (pairs) they share out
     // workgroups per system: as many as the latency shape uses (16 / 32 / 64) while the whole batch stays resident (one
@@ -3027,17 +3484,17 @@ static int coop_enqueue(efgp_toeplitz_s* op, const void* ws, double sigmasq, int
     if (!pad || !scb) return EFGP_ENOMEM;
     CoopArgs ca;
     ca.g = g;
-    ca.ws = (const double2*)ws;
-    ca.diag = precond_diag;
-    ca.diag_scale = precond_diag ? nullptr : diag_scale;
-    ca.b_times_ws = b_times_ws;
-    ca.zero_x0 = zero_x0;
-    ca.sigmasq = sigmasq;
-    ca.variant = variant;
-    ca.tol = tol;
-    ca.early_stop = early_stop;
-    ca.batched = batched_semantics;
-    ca.max_iter = max_iter;
+    ca.ws = s.ws;
+    ca.diag = s.diag;
+    ca.diag_scale = s.diag ? nullptr : s.diag_scale;
+    ca.b_times_ws = s.b_times_ws;
+    ca.zero_x0 = s.zero_x0;
+    ca.sigmasq = s.sigmasq;
+    ca.variant = s.variant;
+    ca.tol = s.tol;
+    ca.early_stop = s.early_stop;
+    ca.batched = s.batched;
+    ca.max_iter = s.max_iter;
     if (!small && !ensure_centred_spectrum(op, stream)) return EFGP_EUNSUPPORTED;
     ca.vhat = small ? op->vhat_co : op->vhat_c;
     ca.tw0 = small ? op->tw_co[0] : op->tw[0];
@@ -3099,8 +3556,8 @@ static int coop_enqueue(efgp_toeplitz_s* op, const void* ws, double sigmasq, int
         KernelTimer timer("cg_coop", stream);
         for (int s0 = 0; s0 < nbatch; s0 += per) {
             const int nsys = std::min(per, nbatch - s0);
-            ca.b = (const double2*)b + (int64_t)s0 * g.M;
-            ca.x = (double2*)x + (int64_t)s0 * g.M;
+            ca.b = s.b + (int64_t)s0 * g.M;
+            ca.x = s.x + (int64_t)s0 * g.M;
             ca.iters = d_iters + s0;
             ca.hist = s0 == 0 ? cg_history().buf : nullptr;
             // the status word is cleared before EVERY launch: a dead barrier in one slab of systems must not make the later
@@ -3152,27 +3609,71 @@ static int coop_enqueue(efgp_toeplitz_s* op, const void* ws, double sigmasq, int
     return EFGP_OK;
 }
 
-static thread_local bool t_no_coop = false;    // set while the cooperative solve hands systems to the multi-launch path
-
-static int cg_solve_impl(efgp_toeplitz_t* op, const void* ws, double sigmasq, int variant, const double* precond_diag,
-                         const void* b, void* x, int nbatch, double tol, int max_iter, int early_stop,
-                         int batched_semantics, int* iters_out, int* row_iters_out, void* stream_, int hermitian);
-
-int efgp_cg_solve(efgp_toeplitz_t* op, const void* ws, double sigmasq, int variant, const double* precond_diag,
-                  const void* b, void* x, int nbatch, double tol, int max_iter, int early_stop,
-                  int batched_semantics, int* iters_out, int* row_iters_out, void* stream_) {
-    return cg_solve_impl(op, ws, sigmasq, variant, precond_diag, b, x, nbatch, tol, max_iter, early_stop, batched_semantics, iters_out,
-                         row_iters_out, stream_, 0);
+// ---- the synchronous entries: read-back of the single-launch solves -------------------------------------------------------------
+// per-row counts and the total of a finished solve.  The one place where the batched count becomes max + 1 unless capped (the
+// terminating pass, cg.py:193-199,243; cg.py:152 counts a single system as it is)
+static void report_counts(const int* its, const CgSolve& s, int* iters_out, int* row_iters_out) {
+    int mx = 0;
+    for (int i = 0; i < s.nbatch; ++i) {
+        mx = std::max(mx, its[i]);
+        if (row_iters_out) row_iters_out[i] = its[i];
+    }
+    if (iters_out) *iters_out = (s.batched && mx < s.max_iter) ? mx + 1 : mx;
 }
 
-int efgp_cg_solve_hermitian(efgp_toeplitz_t* op, const void* ws, double sigmasq, int variant, const double* precond_diag,
-                            const void* b, void* x, int nbatch, double tol, int max_iter, int early_stop,
-                            int batched_semantics, int* iters_out, int* row_iters_out, void* stream_) {
-    return cg_solve_impl(op, ws, sigmasq, variant, precond_diag, b, x, nbatch, tol, max_iter, early_stop, batched_semantics, iters_out,
-                         row_iters_out, stream_, 1);
+// Ends a single-launch solve on the host: d_iters (and the cooperative solve's status word, d_status, where there is one) come back
+// through the context's pinned buffer, the stream is waited for and the counts are reported.  With a status word, *its keeps the
+// counts and *any_dead says whether a grid barrier died (the word is set, or a row reports a negative count).
+static int read_back_counts(DeviceCtx* ctx, const CgSolve& s, const int* d_iters, const int* d_status, hipStream_t stream, int* iters_out,
+                            int* row_iters_out, std::vector<int>* its = nullptr, bool* any_dead = nullptr) {
+    int* host = pinned_host(ctx, (size_t)s.nbatch * sizeof(int) + 128);
+    if (!host) return EFGP_ENOMEM;
+    const int* hit = host + 16;
+    if (d_status) EFGP_HIP_CHECK(hipMemcpyAsync(host, d_status, sizeof(int), hipMemcpyDeviceToHost, stream));
+    EFGP_HIP_CHECK(hipMemcpyAsync(host + 16, d_iters, (size_t)s.nbatch * sizeof(int), hipMemcpyDeviceToHost, stream));
+    EFGP_HIP_CHECK(stream_wait(stream));
+    if (d_status) {
+        bool dead = host[0] != 0;
+        for (int i = 0; i < s.nbatch; ++i) dead = dead || hit[i] < 0;
+        *any_dead = dead;
+        its->assign(hit, hit + s.nbatch);
+    }
+    report_counts(hit, s, iters_out, row_iters_out);
+    return EFGP_OK;
 }
 
-static int cg_solve_impl(efgp_toeplitz_t* op, const void* ws, double sigmasq, int variant, const double* precond_diag,
+// diagnostic run of the cooperative solve (EFGP_COOP_DBG=2): the phase shares of workgroup 0, system 0
+static int coop_print_stamps(const CoopInfo& ci, int iters0) {
+    double hs[14];
+    EFGP_HIP_CHECK(hipMemcpy(hs, ci.stamps, sizeof(hs), hipMemcpyDeviceToHost));
+    const char* nm[14] = {"R store to b1", "barrier 1", "C store", "barrier 2", "Ri load+fft", "pAp sum (incl. barrier)", "update", "rr/rz sum (incl. barrier)",
+                          "C load", "C transform 1 (+ multiply)", "-", "C transform 2", "R zero fill, ws u", "R transform"};
+    double tot = 0;
+    for (int q = 0; q < 14; ++q) tot += hs[q];
+    std::fprintf(stderr, "[coop] G = %d, rows/wg %d, lines/pass %d, columns/wg %d, systems/launch %d\n", ci.G, ci.rows_wg, ci.lines, ci.cols_wg, ci.per);
+    for (int q = 0; q < 14; ++q) std::fprintf(stderr, "[coop] %-28s %9.0f cycles/iter %5.1f%%\n", nm[q], hs[q] / std::max(1, iters0), 100.0 * hs[q] / tot);
+    return EFGP_OK;
+}
+
+// a grid barrier ran out of polls (the workgroups were not co-resident): the systems it hit still hold x0 in x (a solution is
+// written only by a system that finished) and go through the multi-launch path one by one
+static int resolve_dead_rows(efgp_toeplitz_s* op, const CgSolve& s, std::vector<int>& its, hipStream_t stream) {
+    std::fprintf(stderr, "[efgp_hip] cooperative CG: grid barrier timed out, falling back to the multi-launch iteration\n");
+    for (int i = 0; i < s.nbatch; ++i) {
+        if (its[i] >= 0) continue;
+        CgSolve one = s;
+        one.b = s.b + (int64_t)i * op->g.M;
+        one.x = s.x + (int64_t)i * op->g.M;
+        one.nbatch = 1;
+        const int rc = solve_multi_launch(op, one, nullptr, &its[i], stream);
+        if (rc != EFGP_OK) return rc;
+    }
+    return EFGP_OK;
+}
+
+// efgp_cg_solve / efgp_cg_solve_hermitian: the persistent kernel, the cooperative launches or the multi-launch solver, whichever
+// the grid allows first, and the counts on the host
+static int cg_solve_sync(efgp_toeplitz_t* op, const void* ws, double sigmasq, int variant, const double* precond_diag,
                          const void* b, void* x, int nbatch, double tol, int max_iter, int early_stop,
                          int batched_semantics, int* iters_out, int* row_iters_out, void* stream_, int hermitian) {
     EFGP_REQUIRE(op && ws && b && x, "efgp_cg_solve: null argument");
@@ -3181,538 +3682,101 @@ static int cg_solve_impl(efgp_toeplitz_t* op, const void* ws, double sigmasq, in
     EFGP_REQUIRE(batched_semantics || nbatch == 1, "efgp_cg_solve: single-system semantics need nbatch == 1");
     EFGP_REQUIRE(sigmasq > 0.0 || variant == 0, "efgp_cg_solve: sigmasq must be positive for A_var");
     hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard guard(op->device, (hipStream_t)stream_);
+    DeviceGuard guard(op->device, stream);
     DeviceCtx* ctx = op->ctx;
-    const ToepGeom g = op->g;
-    if (max_iter <= 0) max_iter = (int)std::min<int64_t>(2 * g.M, 2000000000);
+    // Only the multi-launch 3-D iteration honours the Hermitian promise here: the persistent kernel is given neither `hermitian`
+    // nor a use for the 48 x 48 operands, and the cooperative kernel runs with hermitian = 0 (the asynchronous entries pass the
+    // promise on).  Which kernel runs is behaviour: kept as it is.
+    CgSolve s = make_solve(op, ws, sigmasq, variant, precond_diag, b, x, nbatch, tol, max_iter, early_stop, batched_semantics);
+    CgSolve promised = s;
+    promised.hermitian = hermitian;
 
     // small circulant grids: the whole solve in one persistent kernel, one workgroup per system
-    const bool no_persistent = std::getenv("EFGP_NO_PERSISTENT_CG") != nullptr;   // test hook
-    if (op->persistent_ok && !no_persistent) {
+    if (persistent_usable(op)) {
         int* d_iters = (int*)scratch(ctx, SLOT_CG_SCALARS, (size_t)nbatch * sizeof(int) + 64);
-        int* host = pinned_host(ctx, (size_t)nbatch * sizeof(int) + 64);
-        if (!d_iters || !host) return EFGP_ENOMEM;
-        int rc;
-        {
-            KernelTimer timer("cg_persistent", stream);
-            const ToepGeom* gq;
-            const double2* const* twq;
-            const double2* vq;
-            if (const int rc_ops = cg_operands(op, stream, &gq, &twq, &vq)) return rc_ops;
-            rc = persistent_cg_launch(*gq, twq, vq, (const double2*)ws, precond_diag, sigmasq,
-                                      variant, tol, early_stop, batched_semantics, max_iter, (const double2*)b, (double2*)x,
-                                      nbatch, d_iters, stream);
-        }
+        if (!d_iters) return EFGP_ENOMEM;
+        const int rc = enqueue_persistent(op, s, d_iters, stream);
         if (rc != EFGP_OK) return rc;
-        EFGP_HIP_CHECK(hipMemcpyAsync(host, d_iters, (size_t)nbatch * sizeof(int), hipMemcpyDeviceToHost, stream));
-        EFGP_HIP_CHECK(stream_wait(stream));
-        int mx = 0;
-        for (int i = 0; i < nbatch; ++i) {
-            mx = std::max(mx, host[i]);
-            if (row_iters_out) row_iters_out[i] = host[i];
-        }
-        int total = mx;
-        if (batched_semantics && mx < max_iter) total = mx + 1;      // the terminating pass, cg.py:193-199,243
-        if (iters_out) *iters_out = total;
-        return EFGP_OK;
+        return read_back_counts(ctx, s, d_iters, nullptr, stream, iters_out, row_iters_out);
     }
-
     // 2-D grids of 128..512 per dimension: the whole solve in cooperative launches (coop_enqueue)
-    if (op->lines_ok && !t_no_coop && std::getenv("EFGP_NO_CG_COOP") == nullptr && std::getenv("EFGP_NO_CG_LINES") == nullptr) {
+    if (coop_usable(op)) {
         int* d_iters = (int*)scratch(ctx, SLOT_CG_SCALARS, (size_t)nbatch * sizeof(int) + 64);
-        int* host = pinned_host(ctx, (size_t)nbatch * sizeof(int) + 128);
-        if (!d_iters || !host) return EFGP_ENOMEM;
+        if (!d_iters) return EFGP_ENOMEM;
         CoopInfo ci;
-        const int rcq = coop_enqueue(op, ws, sigmasq, variant, precond_diag, b, x, nbatch, tol, max_iter, early_stop, batched_semantics,
-                                     d_iters, stream, &ci, /*nan_on_dead: this entry re-solves dead systems from x0*/ 0);
-        if (rcq != EFGP_OK && rcq != EFGP_EUNSUPPORTED) return rcq;
-        if (rcq == EFGP_OK) {
-            EFGP_HIP_CHECK(hipMemcpyAsync(host, ci.d_status, sizeof(int), hipMemcpyDeviceToHost, stream));
-            EFGP_HIP_CHECK(hipMemcpyAsync(host + 16, d_iters, (size_t)nbatch * sizeof(int), hipMemcpyDeviceToHost, stream));
-            EFGP_HIP_CHECK(stream_wait(stream));
-            const int dead = host[0];
-            const int* hit = host + 16;
-            if (ci.dbg == 2) {
-                double hs[14];
-                EFGP_HIP_CHECK(hipMemcpy(hs, ci.stamps, sizeof(hs), hipMemcpyDeviceToHost));
-                const char* nm[14] = {"R store to b1", "barrier 1", "C store", "barrier 2", "Ri load+fft", "pAp sum (incl. barrier)", "update", "rr/rz sum (incl. barrier)",
-                                      "C load", "C transform 1 (+ multiply)", "-", "C transform 2", "R zero fill, ws u", "R transform"};
-                double tot = 0;
-                for (int q = 0; q < 14; ++q) tot += hs[q];
-                std::fprintf(stderr, "[coop] G = %d, rows/wg %d, lines/pass %d, columns/wg %d, systems/launch %d\n", ci.G, ci.rows_wg, ci.lines, ci.cols_wg, ci.per);
-                for (int q = 0; q < 14; ++q) std::fprintf(stderr, "[coop] %-28s %9.0f cycles/iter %5.1f%%\n", nm[q], hs[q] / std::max(1, hit[0]), 100.0 * hs[q] / tot);
-            }
-            bool any_dead = dead != 0;
-            for (int i = 0; i < nbatch; ++i) any_dead = any_dead || hit[i] < 0;
-            if (!any_dead) {
-                int mx = 0;
-                for (int i = 0; i < nbatch; ++i) {
-                    mx = std::max(mx, hit[i]);
-                    if (row_iters_out) row_iters_out[i] = hit[i];
-                }
-                if (iters_out) *iters_out = (batched_semantics && mx < max_iter) ? mx + 1 : mx;
-                return EFGP_OK;
-            }
-            // a grid barrier ran out of polls (the workgroups were not co-resident): the systems it hit still hold x0 in x (a
-            // solution is written only by a system that finished) and go through the multi-launch path one by one
-            std::fprintf(stderr, "[efgp_hip] cooperative CG: grid barrier timed out, falling back to the multi-launch iteration\n");
-            int mx = 0;
-            std::vector<int> its(hit, hit + nbatch);
-            for (int i = 0; i < nbatch; ++i) {
-                if (its[i] < 0) {
-                    int one = 0;
-                    t_no_coop = true;
-                    const int rc1 = efgp_cg_solve(op, ws, sigmasq, variant, precond_diag, (const double2*)b + (int64_t)i * g.M,
-                                                  (double2*)x + (int64_t)i * g.M, 1, tol, max_iter, early_stop, batched_semantics, nullptr, &one,
-                                                  stream_);
-                    t_no_coop = false;
-                    if (rc1 != EFGP_OK) return rc1;
-                    its[i] = one;
-                }
-                mx = std::max(mx, its[i]);
-                if (row_iters_out) row_iters_out[i] = its[i];
-            }
-            if (iters_out) *iters_out = (batched_semantics && mx < max_iter) ? mx + 1 : mx;
-            return EFGP_OK;
+        int rc = coop_enqueue(op, s, d_iters, stream, &ci, /*nan_on_dead: this entry re-solves dead systems from x0*/ 0);
+        if (rc != EFGP_OK && rc != EFGP_EUNSUPPORTED) return rc;
+        if (rc == EFGP_OK) {
+            std::vector<int> its;
+            bool any_dead = false;
+            rc = read_back_counts(ctx, s, d_iters, ci.d_status, stream, iters_out, row_iters_out, &its, &any_dead);
+            if (rc == EFGP_OK && ci.dbg == 2) rc = coop_print_stamps(ci, its[0]);
+            if (rc != EFGP_OK || !any_dead) return rc;
+            rc = resolve_dead_rows(op, s, its, stream);
+            if (rc == EFGP_OK) report_counts(its.data(), s, iters_out, row_iters_out);
+            return rc;
         }
     }
-
-    // The iteration bursts below are replayed as hipGraphs, which cannot be captured on the legacy default stream:
-    // run the multi-kernel solve on a side stream ordered after the caller's stream (the final poll of every group
-    // synchronises the host with it, so later work on the caller's stream is ordered after the solve).
-    if (!timing_enabled() && std::getenv("EFGP_NO_CG_GRAPH") == nullptr) {
-        if (!ctx->aux_stream) {
-            if (hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking) != hipSuccess ||
-                hipEventCreateWithFlags(&ctx->aux_event, hipEventDisableTiming) != hipSuccess) {
-                (void)hipGetLastError();
-                ctx->aux_stream = nullptr;
-            }
-        }
-        if (ctx->aux_stream) {
-            EFGP_HIP_CHECK(hipEventRecord(ctx->aux_event, stream));
-            EFGP_HIP_CHECK(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_event, 0));
-            stream = ctx->aux_stream;
-        }
-    }
-    // rows are processed in groups whose padded grids fit ~512 MB of scratch
-    const int64_t group_cap = std::max<int64_t>(1, (int64_t)(512ll << 20) / (g.Ftot * (int64_t)sizeof(double2)));
-    int global_iters = 0;
-    for (int64_t r0 = 0; r0 < nbatch; r0 += group_cap) {
-        const int rows = (int)std::min<int64_t>(group_cap, nbatch - r0);
-        double2* pad = (double2*)scratch(ctx, SLOT_TOEP_PAD, (size_t)rows * (size_t)g.Ftot * sizeof(double2));
-        double2* vec = (double2*)scratch(ctx, SLOT_CG_VEC, (size_t)3 * rows * (size_t)g.M * sizeof(double2));
-        // scalars | status (64 B) + slot->row map | arrival counters | per-workgroup partial sums
-        const size_t off_status = ((size_t)rows * sizeof(CgRowScalars) + 63) & ~size_t(63);
-        const size_t off_counter = off_status + 64 + (((size_t)rows * sizeof(int) + 63) & ~size_t(63));
-        const size_t off_partial = off_counter + (((size_t)2 * rows * sizeof(int) + 63) & ~size_t(63));
-        const size_t sc_bytes = off_partial + (size_t)rows * 3 * kCgBlocksMax * sizeof(double);
-        char* scb = (char*)scratch(ctx, SLOT_CG_SCALARS, sc_bytes);
-        int* host = pinned_host(ctx, (size_t)rows * sizeof(CgRowScalars) + 64);
-        if (!pad || !vec || !scb || !host) return EFGP_ENOMEM;
-        CgArgs a;
-        a.g = g;
-        a.ws = (const double2*)ws;
-        a.diag = precond_diag;
-        a.sigmasq = sigmasq;
-        a.variant = variant;
-        a.tol = tol;
-        a.early_stop = early_stop;
-        a.batched = batched_semantics;
-        a.b = (const double2*)b + r0 * g.M;
-        a.x = (double2*)x + r0 * g.M;
-        a.r = vec;
-        a.p = vec + (int64_t)rows * g.M;
-        a.ap = vec + (int64_t)2 * rows * g.M;
-        a.pad = pad;
-        a.pad_out = pad;
-        a.rows = nullptr;
-        a.hist = r0 == 0 ? cg_history().buf : nullptr;
-        a.hist_cap = cg_history().capacity;
-        a.sc = (CgRowScalars*)scb;
-        a.status = (int*)(scb + off_status);
-        int* d_rows = a.status + 16;
-        a.counter = (int*)(scb + off_counter);
-        a.partial = (double*)(scb + off_partial);
-        a.v_off = 0;
-        a.v_len = g.M;
-        a.v_w1 = g.M;
-        a.nblk = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(64 /* update kernels: measured optimum */, (g.M + kVecThreads - 1) / kVecThreads),
-                                                            std::max<int64_t>(1, 1024 / rows)));
-        EFGP_HIP_CHECK(hipMemsetAsync(a.status, 0, off_partial - off_status, stream));      // status, map, counters
-
-        // r0 = b - A x0
-        hipLaunchKernelGGL(pad_scale_kernel, grid_for(g.Ftot, rows, kVecThreads), dim3(kVecThreads), 0, stream, g,
-                           (const double2*)a.x, g.M, a.ws, (const int*)nullptr, (const int*)nullptr, pad, 1.0);
-        EFGP_HIP_CHECK(hipGetLastError());
-        int rc = circulant(op, pad, rows, stream);
-        if (rc != EFGP_OK) return rc;
-        hipLaunchKernelGGL(cg_init_kernel, dim3(a.nblk, rows), dim3(kVecThreads), 0, stream, a);
-        EFGP_HIP_CHECK(hipGetLastError());
-
-        // iteration loop; active rows are compacted on the host whenever the status is polled
-        std::vector<int> active_rows(rows);
-        for (int i = 0; i < rows; ++i) active_rows[i] = i;
-        int n_active = rows;
-        bool compacted = false;
-        int it = 0;
-        int last_active_it = 0;       // number of iterations in which at least one row was active
-        const int poll_every = 8;
-        std::vector<CgRowScalars> hsc(rows);
-        // 2-D mid-size grids: three launches of pruned in-LDS line transforms instead of pad + rocFFT + multiply
-        const bool use_lines = op->lines_ok && std::getenv("EFGP_NO_CG_LINES") == nullptr;
-        LineArgs la;
-        size_t lds_rows = 0, lds_cols = 0;
-        if (use_lines) {
-            rc = ensure_reference_spectrum(op, stream);
-            if (rc != EFGP_OK) return rc;
-            la.vhat = op->vhat;
-            la.tw0 = op->tw[0];
-            la.tw1 = op->tw[1];
-            la.b1 = pad;                                                     // [rows][n0][F1] fits: Ftot >= 2 n0 F1
-            la.b2 = pad + (int64_t)rows * g.n[0] * g.F[1];
-            // every workgroup of the reducing kernels pays a device-scope fence (an L2 write-back, ~2 us each, serialised
-            // per XCD): few systems -> many small workgroups for parallelism, many systems -> few large ones
-            const int64_t Fmax = std::max(g.F[0], g.F[1]);
-            int lpb = 4;
-            if (rows > 8) {
-                const int64_t fit = ((int64_t)ctx->max_lds / (int64_t)sizeof(double2) - Fmax) / (2 * (Fmax + 1));
-                while (lpb * 2 <= fit && lpb < 32) lpb <<= 1;
-            }
-            la.lpb = lpb;
-            la.nblk_rows = (int)((g.n[0] + lpb - 1) / lpb);
-            lds_rows = ((size_t)2 * lpb * (size_t)(g.F[1] + 1) + (size_t)g.F[1]) * sizeof(double2);   // + twiddles
-            lds_cols = ((size_t)2 * lpb * (size_t)(g.F[0] + 1) + (size_t)g.F[0]) * sizeof(double2);
-            EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg_rows_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rows));
-            EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg_rows_inv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rows));
-            EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg_cols_mid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cols));
-        }
-        bool use_lines3 = op->lines3_ok && std::getenv("EFGP_NO_CG_LINES") == nullptr;
-        if (use_lines3) {
-            // the line kernels keep 2 x lpb lines of F2 + 1 elements in LDS and one partial sum per workgroup: both limits must
-            // hold (found at full size: mtot = 57, F = 128 asked for 64 lines per block = 266 KB of LDS)
-            const int64_t fit = ((int64_t)ctx->max_lds / (int64_t)sizeof(double2) - g.F[2]) / (2 * (g.F[2] + 1));
-            int64_t lmax = 16;
-            while (lmax * 2 <= fit) lmax <<= 1;
-            if (fit < 16 || (g.n[0] * g.n[1] + lmax - 1) / lmax > kCgBlocksMax) use_lines3 = false;
-        }
-        Line3Args l3;
-        size_t lds3_c = 0, lds3_s[3] = {0, 0, 0};
-        if (use_lines3) {
-            l3.vhat = op->vhat;
-            for (int q = 0; q < 3; ++q) l3.tw[q] = op->tw[q];
-            l3.b1 = pad;
-            l3.b2 = pad + (int64_t)rows * g.n[0] * g.n[1] * g.F[2];
-            const int64_t nlines = g.n[0] * g.n[1];
-            const int64_t fit = ((int64_t)ctx->max_lds / (int64_t)sizeof(double2) - g.F[2]) / (2 * (g.F[2] + 1));
-            int lpb = 16;
-            while ((nlines + lpb - 1) / lpb > kCgBlocksMax && lpb * 2 <= fit) lpb <<= 1;
-            if (rows > 8) {                               // batched: fewer, larger workgroups (fewer reduction fences)
-                while (lpb * 2 <= fit && lpb < 64) lpb <<= 1;
-            }
-            l3.lpb_c = lpb;
-            l3.lpb_s = 16;
-            l3.nblk_lines = (int)((nlines + lpb - 1) / lpb);
-            lds3_c = ((size_t)2 * lpb * (size_t)(g.F[2] + 1) + (size_t)g.F[2]) * sizeof(double2);
-            for (int q = 0; q < 2; ++q) lds3_s[q] = ((size_t)2 * l3.lpb_s * (size_t)(g.F[q] + 1) + (size_t)g.F[q]) * sizeof(double2);
-            EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3_fwd2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3_c));
-            EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3_inv2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3_c));
-            EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3_dim1_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3_s[1]));
-            EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3_dim1_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3_s[1]));
-            EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3_mid0_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3_s[0]));
-        }
-        // Hermitian 3-D systems: the planes k0 >= 0 only (cg3h_* kernels).  The data are checked once per group of rows.
-        bool use_lines3h = use_lines3 && hermitian && (g.n[0] & 1) && (g.n[1] & 1) && (g.n[2] & 1) && g.n[0] >= 3 &&
-                           std::getenv("EFGP_NO_CG_HERM3") == nullptr;
-        Line3HArgs l3h;
-        size_t lds3h_c = 0, lds3h_s[2] = {0, 0};
-        if (use_lines3h) {
-            if (!op->vc3) {
-                op->vc3 = (double*)pool_alloc(ctx, (size_t)g.Ftot * sizeof(double));
-                if (!op->vc3) return EFGP_ENOMEM;
-                hipLaunchKernelGGL(center_spectrum3_real_kernel, dim3((unsigned)((g.Ftot + 255) / 256)), dim3(256), 0, stream, op->vhat, op->tw[0],
-                                   op->tw[1], op->tw[2], (int)g.n[0], (int)g.n[1], (int)g.n[2], (int)g.F[0], (int)g.F[1], (int)g.F[2], op->vc3);
-                EFGP_HIP_CHECK(hipGetLastError());
-            }
-            double* chk_buf = (double*)scratch(ctx, SLOT_MISC, 64);
-            if (!chk_buf) return EFGP_ENOMEM;
-            EFGP_HIP_CHECK(hipMemsetAsync(chk_buf, 0, 64, stream));
-            hipLaunchKernelGGL(cg_herm_check_kernel, dim3(256), dim3(kVecThreads), 0, stream, a.b, (const double2*)a.x, a.ws, g.M, rows, chk_buf);
-            EFGP_HIP_CHECK(hipGetLastError());
-            EFGP_HIP_CHECK(hipMemcpyAsync(host, chk_buf, 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
-            EFGP_HIP_CHECK(stream_wait(stream));
-            double hv[3];
-            std::memcpy(hv, host, sizeof(hv));
-            if (!(hv[0] <= 1e-16 * hv[1]) || hv[2] > 0.0) {
-                set_error("efgp_cg_solve_hermitian: right-hand side / start vector not conjugate-even or ws not real and even");
-                return EFGP_EINVAL;
-            }
-            const int64_t nh = (g.n[0] + 1) / 2;
-            a.v_off = (nh - 1) * g.n[1] * g.n[2];
-            a.v_len = nh * g.n[1] * g.n[2];
-            a.v_w1 = g.n[1] * g.n[2];
-            l3h.vc = op->vc3;
-            for (int q = 0; q < 3; ++q) l3h.tw[q] = op->tw[q];
-            l3h.b1 = pad;
-            l3h.b2 = pad + (int64_t)rows * nh * g.n[1] * g.F[2];
-            const int64_t nlines = nh * g.n[1];
-            const int64_t fit = ((int64_t)ctx->max_lds / (int64_t)sizeof(double2) - g.F[2]) / (2 * (g.F[2] + 1));
-            int lpb = 8;
-            while ((nlines + lpb - 1) / lpb > kCgBlocksMax && lpb * 2 <= fit) lpb <<= 1;
-            if (rows >= 3 && lpb < 16 && 32 <= fit) lpb = 16;          // measured at mtot 57: 125 vs 133 us per iteration of 3 systems
-            if (rows > 8) {
-                while (lpb * 2 <= fit && lpb < 64) lpb <<= 1;
-            }
-            auto knob = [](const char* name, int dflt) {
-                const char* e = std::getenv(name);
-                int v = e ? std::atoi(e) : dflt;
-                int p2 = 1;
-                while (p2 * 2 <= v) p2 <<= 1;
-                return std::max(1, p2);
-            };
-            if (std::getenv("EFGP_CG3_LC")) {
-                lpb = knob("EFGP_CG3_LC", lpb);
-                while ((nlines + lpb - 1) / lpb > kCgBlocksMax) lpb <<= 1;
-            }
-            l3h.lpb_c = lpb;
-            l3h.lpb_s = (int)std::min<int64_t>(knob("EFGP_CG3_LS", 16), g.F[2] / 2);
-            l3h.lpb_m = (int)std::min<int64_t>(knob("EFGP_CG3_LM", rows >= 3 ? 32 : 16), g.F[2] / 2);      // 3 systems: 124.6 vs 132.6 us
-            l3h.nblk_lines = (int)((nlines + lpb - 1) / lpb);
-            lds3h_c = ((size_t)2 * lpb * (size_t)(g.F[2] + 1) + (size_t)g.F[2]) * sizeof(double2);
-            lds3h_s[1] = ((size_t)2 * l3h.lpb_s * (size_t)(g.F[1] + 1) + (size_t)g.F[1]) * sizeof(double2);
-            lds3h_s[0] = ((size_t)2 * l3h.lpb_m * (size_t)(g.F[0] + 1) + (size_t)g.F[0]) * sizeof(double2);
-            EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3h_fwd2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3h_c));
-            EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3h_inv2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3h_c));
-            EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3h_dim1_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3h_s[1]));
-            EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3h_dim1_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3h_s[1]));
-            EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3h_mid0_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3h_s[0]));
-            a.nblk = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(std::min(kCgBlocksMax, knob("EFGP_CG_NBLK", 128)), (a.v_len + kVecThreads - 1) / kVecThreads),
-                                                                std::max<int64_t>(1, 1024 / rows)));
-        }
-        bool use_graph = !timing_enabled() && std::getenv("EFGP_NO_CG_GRAPH") == nullptr;
-        hipGraphExec_t graph_exec = nullptr;
-        int graph_slots = -1;
-        const int* graph_rows = nullptr;
-        while (it < max_iter && n_active > 0) {
-            const int burst = std::min(poll_every, max_iter - it);
-            // FFT batch = number of slots (bucketed to a power of two to bound the number of plans)
-            int slots = n_active;
-            if (compacted) {
-                int p2 = 1;
-                while (p2 < n_active) p2 <<= 1;
-                slots = std::min(p2, rows);
-            }
-            // One iteration = 5 launches of ours + two rocFFT executions (~11 kernels): enqueueing them one by one
-            // costs the host ~300 us per iteration (measured, 3-D 64^3), far more than the GPU needs.  A full burst is
-            // therefore captured ONCE into a hipGraph per (slots, row map) state and replayed with one launch.
-            auto enqueue_iteration = [&]() -> int {
-                if (use_lines3h) {
-                    l3h.c = a;
-                    const unsigned nhp = (unsigned)((g.n[0] + 1) / 2);
-                    const unsigned gs = (unsigned)(g.F[2] / l3h.lpb_s), gp = (unsigned)(g.F[2] / 2 / l3h.lpb_m);
-                    hipLaunchKernelGGL(cg3h_fwd2_kernel, dim3(l3h.nblk_lines, slots), dim3(kLineThreads), lds3h_c, stream, l3h);
-                    hipLaunchKernelGGL((cg3h_dim1_kernel<0>), dim3(nhp * gs, slots), dim3(kLineThreads), lds3h_s[1], stream, l3h);
-                    hipLaunchKernelGGL(cg3h_mid0_kernel, dim3((unsigned)g.F[1] * gp, slots), dim3(kLineThreads), lds3h_s[0], stream, l3h);
-                    hipLaunchKernelGGL((cg3h_dim1_kernel<1>), dim3(nhp * gs, slots), dim3(kLineThreads), lds3h_s[1], stream, l3h);
-                    hipLaunchKernelGGL(cg3h_inv2_kernel, dim3(l3h.nblk_lines, slots), dim3(kLineThreads), lds3h_c, stream, l3h);
-                    hipLaunchKernelGGL(cg_axpy_kernel, dim3(a.nblk, slots), dim3(kVecThreads), 0, stream, a);
-                    EFGP_HIP_CHECK(hipGetLastError());
-                    return EFGP_OK;
-                }
-                if (use_lines3) {
-                    l3.c = a;
-                    const unsigned gs = (unsigned)(g.F[2] / l3.lpb_s);
-                    hipLaunchKernelGGL(cg3_fwd2_kernel, dim3(l3.nblk_lines, slots), dim3(kLineThreads), lds3_c, stream, l3);
-                    hipLaunchKernelGGL((cg3_dim1_kernel<0>), dim3((unsigned)g.n[0] * gs, slots), dim3(kLineThreads), lds3_s[1], stream, l3);
-                    hipLaunchKernelGGL(cg3_mid0_kernel, dim3((unsigned)g.F[1] * gs, slots), dim3(kLineThreads), lds3_s[0], stream, l3);
-                    hipLaunchKernelGGL((cg3_dim1_kernel<1>), dim3((unsigned)g.n[0] * gs, slots), dim3(kLineThreads), lds3_s[1], stream, l3);
-                    hipLaunchKernelGGL(cg3_inv2_kernel, dim3(l3.nblk_lines, slots), dim3(kLineThreads), lds3_c, stream, l3);
-                    hipLaunchKernelGGL(cg_axpy_kernel, dim3(a.nblk, slots), dim3(kVecThreads), 0, stream, a);
-                    EFGP_HIP_CHECK(hipGetLastError());
-                    return EFGP_OK;
-                }
-                if (use_lines) {
-                    la.c = a;
-                    hipLaunchKernelGGL(cg_rows_fwd_kernel, dim3(la.nblk_rows, slots), dim3(kLineThreads), lds_rows, stream, la);
-                    hipLaunchKernelGGL(cg_cols_mid_kernel, dim3((unsigned)(g.F[1] / la.lpb), slots), dim3(kLineThreads),
-                                       lds_cols, stream, la);
-                    hipLaunchKernelGGL(cg_rows_inv_kernel, dim3(la.nblk_rows, slots), dim3(kLineThreads), lds_rows, stream, la);
-                    hipLaunchKernelGGL(cg_axpy_kernel, dim3(a.nblk, slots), dim3(kVecThreads), 0, stream, a);
-                    EFGP_HIP_CHECK(hipGetLastError());
-                    return EFGP_OK;
-                }
-                hipLaunchKernelGGL(cg_pad_kernel, grid_for(g.Ftot, slots, kVecThreads), dim3(kVecThreads), 0, stream, a);
-                EFGP_HIP_CHECK(hipGetLastError());
-                int rcc = circulant(op, pad, slots, stream);
-                if (rcc != EFGP_OK) return rcc;
-                hipLaunchKernelGGL(cg_dot_kernel, dim3(a.nblk, slots), dim3(kVecThreads), 0, stream, a);
-                hipLaunchKernelGGL(cg_axpy_kernel, dim3(a.nblk, slots), dim3(kVecThreads), 0, stream, a);
-                EFGP_HIP_CHECK(hipGetLastError());
-                return EFGP_OK;
-            };
-            bool launched = false;
-            if (use_graph && burst == poll_every) {
-                if (graph_exec && (graph_slots != slots || graph_rows != a.rows)) {
-                    (void)hipGraphExecDestroy(graph_exec);
-                    graph_exec = nullptr;
-                }
-                if (!graph_exec) {
-                    TraceSpan span_build("graph build (plan + capture + instantiate)");
-                    hipGraph_t graph = nullptr;
-                    // make sure the FFT plan exists and is bound to the stream before capturing
-                    if (own_fft_supported(g.d, g.F)) {
-                        rc = own_fft_prepare(ctx, g.d, g.F, stream);
-                    } else {
-                        hipfftHandle fh_unused;
-                        rc = fft_plan(ctx, g.d, g.F, slots, stream, &fh_unused);
-                    }
-                    if (rc != EFGP_OK) return rc;
-                    bool ok = hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-                    if (ok) {
-                        int rcap = EFGP_OK;
-                        for (int k = 0; k < burst && rcap == EFGP_OK; ++k) rcap = enqueue_iteration();
-                        const hipError_t ee = hipStreamEndCapture(stream, &graph);
-                        ok = rcap == EFGP_OK && ee == hipSuccess && graph != nullptr;
-                    }
-                    if (ok) ok = hipGraphInstantiate(&graph_exec, graph, nullptr, nullptr, 0) == hipSuccess;
-                    if (graph) (void)hipGraphDestroy(graph);
-                    if (!ok) {
-                        (void)hipGetLastError();
-                        graph_exec = nullptr;
-                        use_graph = false;            // this runtime cannot capture the sequence: enqueue directly
-                    } else {
-                        graph_slots = slots;
-                        graph_rows = a.rows;
-                    }
-                }
-                if (graph_exec) {
-                    TraceSpan span_launch("hipGraphLaunch");
-                    EFGP_HIP_CHECK(hipGraphLaunch(graph_exec, stream));
-                    launched = true;
-                }
-            }
-            if (!launched) {
-                for (int k = 0; k < burst; ++k) {
-                    KernelTimer timer("cg_iteration", stream);
-                    rc = enqueue_iteration();
-                    if (rc != EFGP_OK) return rc;
-                }
-            }
-            it += burst;
-            {
-                TraceSpan span_poll("poll (D2H scalars + stream synchronize)");
-                // into the context's PINNED buffer (a pageable destination is staged by the runtime on every call)
-                EFGP_HIP_CHECK(hipMemcpyAsync(host, a.sc, (size_t)rows * sizeof(CgRowScalars), hipMemcpyDeviceToHost, stream));
-                EFGP_HIP_CHECK(stream_wait(stream));
-                std::memcpy(hsc.data(), host, (size_t)rows * sizeof(CgRowScalars));
-            }
-            int new_active = 0;
-            for (int i = 0; i < rows; ++i) {
-                if (hsc[i].active) active_rows[new_active++] = i;
-                last_active_it = std::max(last_active_it, hsc[i].iters);
-            }
-            if (new_active != n_active || !compacted) {
-                if (new_active > 0 && new_active < rows) {
-                    int p2 = 1;
-                    while (p2 < new_active) p2 <<= 1;
-                    const int nslots = std::min(p2, rows);
-                    std::vector<int> map(nslots, -1);
-                    for (int i = 0; i < new_active; ++i) map[i] = active_rows[i];
-                    std::memcpy(host, map.data(), nslots * sizeof(int));
-                    EFGP_HIP_CHECK(hipMemcpyAsync(d_rows, host, nslots * sizeof(int), hipMemcpyHostToDevice, stream));
-                    EFGP_HIP_CHECK(stream_wait(stream));
-                    a.rows = d_rows;
-                    compacted = true;
-                }
-            }
-            n_active = new_active;
-        }
-        if (graph_exec) {
-            TraceSpan span_destroy("hipGraphExecDestroy");
-            (void)hipGraphExecDestroy(graph_exec);
-        }
-        if (use_lines3h) {          // the planes k0 < 0 of the solutions
-            CgArgs am = a;
-            am.rows = nullptr;
-            hipLaunchKernelGGL(cg3h_mirror_kernel, dim3(64, rows), dim3(kVecThreads), 0, stream, am);
-            EFGP_HIP_CHECK(hipGetLastError());
-            EFGP_HIP_CHECK(stream_wait(stream));
-        }
-        // iteration counts (cg.py:152 single; cg.py:193-199,243 batched: +1 for the terminating pass)
-        int group_iters;
-        if (!batched_semantics) {
-            group_iters = hsc.empty() ? 0 : hsc[0].iters;
-            if (it == 0) {   // max_iter == 0 or nothing ran
-                EFGP_HIP_CHECK(stream_wait(stream));
-            }
-        } else {
-            group_iters = last_active_it;
-            if (n_active == 0 && last_active_it < max_iter) group_iters = last_active_it + 1;
-        }
-        if (row_iters_out)
-            for (int i = 0; i < rows; ++i) row_iters_out[r0 + i] = hsc[i].iters;
-        global_iters = std::max(global_iters, group_iters);
-    }
-    if (iters_out) *iters_out = global_iters;
-    return EFGP_OK;
+    return solve_multi_launch(op, promised, iters_out, row_iters_out, stream);
 }
 
-static int cg_solve_async_impl(efgp_toeplitz_t* op, const void* ws, double sigmasq, int variant, const double* precond_diag,
-                               const void* b, void* x, int nbatch, double tol, int max_iter, int early_stop,
-                               int batched_semantics, int* row_iters_dev, void* stream_, int hermitian, int zero_x0);
-
-int efgp_cg_solve_async(efgp_toeplitz_t* op, const void* ws, double sigmasq, int variant, const double* precond_diag,
-                        const void* b, void* x, int nbatch, double tol, int max_iter, int early_stop,
-                        int batched_semantics, int* row_iters_dev, void* stream_) {
-    return cg_solve_async_impl(op, ws, sigmasq, variant, precond_diag, b, x, nbatch, tol, max_iter, early_stop, batched_semantics,
-                               row_iters_dev, stream_, 0, 0);
+int efgp_cg_solve(efgp_toeplitz_t* op, const void* ws, double sigmasq, int variant, const double* precond_diag,
+                  const void* b, void* x, int nbatch, double tol, int max_iter, int early_stop,
+                  int batched_semantics, int* iters_out, int* row_iters_out, void* stream_) {
+    return cg_solve_sync(op, ws, sigmasq, variant, precond_diag, b, x, nbatch, tol, max_iter, early_stop, batched_semantics, iters_out,
+                         row_iters_out, stream_, 0);
 }
 
-int efgp_cg_solve_hermitian_async(efgp_toeplitz_t* op, const void* ws, double sigmasq, int variant, const double* precond_diag,
-                                  const void* b, void* x, int nbatch, double tol, int max_iter, int early_stop,
-                                  int batched_semantics, int* row_iters_dev, void* stream_) {
-    return cg_solve_async_impl(op, ws, sigmasq, variant, precond_diag, b, x, nbatch, tol, max_iter, early_stop, batched_semantics,
-                               row_iters_dev, stream_, 1, 0);
+int efgp_cg_solve_hermitian(efgp_toeplitz_t* op, const void* ws, double sigmasq, int variant, const double* precond_diag,
+                            const void* b, void* x, int nbatch, double tol, int max_iter, int early_stop,
+                            int batched_semantics, int* iters_out, int* row_iters_out, void* stream_) {
+    return cg_solve_sync(op, ws, sigmasq, variant, precond_diag, b, x, nbatch, tol, max_iter, early_stop, batched_semantics, iters_out,
+                         row_iters_out, stream_, 1);
 }
 
-int efgp_cg_solve_from_zero_async(efgp_toeplitz_t* op, const void* ws, double sigmasq, int variant, const double* precond_diag,
-                                  const void* b, void* x, int nbatch, double tol, int max_iter, int early_stop, int batched_semantics,
-                                  int hermitian, int* row_iters_dev, void* stream_) {
-    return cg_solve_async_impl(op, ws, sigmasq, variant, precond_diag, b, x, nbatch, tol, max_iter, early_stop, batched_semantics,
-                               row_iters_dev, stream_, hermitian ? 1 : 0, 1);
-}
-
-static int cg_solve_async_impl(efgp_toeplitz_t* op, const void* ws, double sigmasq, int variant, const double* precond_diag,
-                               const void* b, void* x, int nbatch, double tol, int max_iter, int early_stop,
-                               int batched_semantics, int* row_iters_dev, void* stream_, int hermitian, int zero_x0) {
+// the asynchronous entries: the persistent kernel, else the cooperative launches -- neither needs the host (a row whose grid barrier
+// died -- workgroups not co-resident -- reports -3 iterations and keeps x0; the synchronous entry retries those through the
+// multi-launch path)
+static int cg_solve_async(efgp_toeplitz_t* op, const void* ws, double sigmasq, int variant, const double* precond_diag,
+                          const void* b, void* x, int nbatch, double tol, int max_iter, int early_stop,
+                          int batched_semantics, int* row_iters_dev, void* stream_, int hermitian, int zero_x0) {
     EFGP_REQUIRE(op && ws && b && x && row_iters_dev, "efgp_cg_solve_async: null argument");
     EFGP_REQUIRE(nbatch >= 1, "efgp_cg_solve_async: nbatch must be >= 1");
     EFGP_REQUIRE(variant == 0 || variant == 1, "efgp_cg_solve_async: variant must be 0 or 1");
     EFGP_REQUIRE(batched_semantics || nbatch == 1, "efgp_cg_solve_async: single-system semantics need nbatch == 1");
     EFGP_REQUIRE(sigmasq > 0.0 || variant == 0, "efgp_cg_solve_async: sigmasq must be positive for A_var");
-    if (!op->persistent_ok || std::getenv("EFGP_NO_PERSISTENT_CG") != nullptr) {
-        // 2-D 128^2..512^2: the cooperative launches need no host either (a row whose grid barrier died -- workgroups not
-        // co-resident -- reports -3 iterations and keeps x0; the synchronous entry retries those through the multi-launch path)
-        if (op->lines_ok && std::getenv("EFGP_NO_CG_COOP") == nullptr && std::getenv("EFGP_NO_CG_LINES") == nullptr) {
-            hipStream_t stream_c = (hipStream_t)stream_;
-            DeviceGuard guard_c(op->device, (hipStream_t)stream_);
-            if (max_iter <= 0) max_iter = (int)std::min<int64_t>(2 * op->g.M, 2000000000);
-            return coop_enqueue(op, ws, sigmasq, variant, precond_diag, b, x, nbatch, tol, max_iter, early_stop, batched_semantics,
-                                row_iters_dev, stream_c, nullptr, /*nan_on_dead*/ 1, hermitian, nullptr, 0, zero_x0);
-        }
+    if (!persistent_usable(op) && !coop_usable(op)) {
         set_error("efgp_cg_solve_async: grid does not fit the persistent kernel");
         return EFGP_EUNSUPPORTED;
     }
     hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard guard(op->device, (hipStream_t)stream_);
-    if (max_iter <= 0) max_iter = (int)std::min<int64_t>(2 * op->g.M, 2000000000);
-    KernelTimer timer("cg_persistent", stream);
-    const ToepGeom* gq;
-    const double2* const* twq;
-    const double2* vq;
-    if (const int rc_ops = cg_operands(op, stream, &gq, &twq, &vq)) return rc_ops;
-    return persistent_cg_launch(*gq, twq, vq, (const double2*)ws, precond_diag, sigmasq,
-                                variant, tol, early_stop, batched_semantics, max_iter, (const double2*)b, (double2*)x, nbatch,
-                                row_iters_dev, stream, nullptr, 0, zero_x0, nullptr, hermitian, op->h48.vhat ? &op->h48 : nullptr);
+    DeviceGuard guard(op->device, stream);
+    CgSolve s = make_solve(op, ws, sigmasq, variant, precond_diag, b, x, nbatch, tol, max_iter, early_stop, batched_semantics);
+    s.hermitian = hermitian;
+    s.zero_x0 = zero_x0;
+    if (persistent_usable(op)) return enqueue_persistent(op, s, row_iters_dev, stream);
+    return coop_enqueue(op, s, row_iters_dev, stream, nullptr, /*nan_on_dead*/ 1);
+}
+
+int efgp_cg_solve_async(efgp_toeplitz_t* op, const void* ws, double sigmasq, int variant, const double* precond_diag,
+                        const void* b, void* x, int nbatch, double tol, int max_iter, int early_stop,
+                        int batched_semantics, int* row_iters_dev, void* stream_) {
+    return cg_solve_async(op, ws, sigmasq, variant, precond_diag, b, x, nbatch, tol, max_iter, early_stop, batched_semantics,
+                          row_iters_dev, stream_, 0, 0);
+}
+
+int efgp_cg_solve_hermitian_async(efgp_toeplitz_t* op, const void* ws, double sigmasq, int variant, const double* precond_diag,
+                                  const void* b, void* x, int nbatch, double tol, int max_iter, int early_stop,
+                                  int batched_semantics, int* row_iters_dev, void* stream_) {
+    return cg_solve_async(op, ws, sigmasq, variant, precond_diag, b, x, nbatch, tol, max_iter, early_stop, batched_semantics,
+                          row_iters_dev, stream_, 1, 0);
+}
+
+int efgp_cg_solve_from_zero_async(efgp_toeplitz_t* op, const void* ws, double sigmasq, int variant, const double* precond_diag,
+                                  const void* b, void* x, int nbatch, double tol, int max_iter, int early_stop, int batched_semantics,
+                                  int hermitian, int* row_iters_dev, void* stream_) {
+    return cg_solve_async(op, ws, sigmasq, variant, precond_diag, b, x, nbatch, tol, max_iter, early_stop, batched_semantics,
+                          row_iters_dev, stream_, hermitian ? 1 : 0, 1);
 }
 
 int efgp_lanczos(efgp_toeplitz_t* op, const void* ws, double sigmasq, int variant, const void* z, int nprobes, int steps,
@@ -3721,48 +3785,45 @@ int efgp_lanczos(efgp_toeplitz_t* op, const void* ws, double sigmasq, int varian
     EFGP_REQUIRE(nprobes >= 1 && steps >= 1, "efgp_lanczos: nprobes and steps must be >= 1");
     EFGP_REQUIRE(variant == 0 || variant == 1, "efgp_lanczos: variant must be 0 or 1");
     EFGP_REQUIRE(sigmasq > 0.0 || variant == 0, "efgp_lanczos: sigmasq must be positive for A_var");
-    if (!op->persistent_ok || std::getenv("EFGP_NO_PERSISTENT_CG") != nullptr) {
+    if (!persistent_usable(op)) {
         set_error("efgp_lanczos: grid does not fit the persistent kernel");
         return EFGP_EUNSUPPORTED;
     }
     hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard guard(op->device, (hipStream_t)stream_);
+    DeviceGuard guard(op->device, stream);
     const LanczosOut lz{steps, alpha_dev, beta_dev, norm2_dev};
-    const ToepGeom* gq;
-    const double2* const* twq;
-    const double2* vq;
-    if (const int rc_ops = cg_operands(op, stream, &gq, &twq, &vq)) return rc_ops;
-    return persistent_cg_launch(*gq, twq, vq, (const double2*)ws, nullptr, sigmasq, variant, 0.0, 0,
-                                1, steps, (const double2*)z, nullptr, nprobes, steps_taken_dev, stream, nullptr, 0, 1, &lz);
+    // `steps` recurrences from z with a zero start, no stopping test, no solution written
+    CgSolve s = make_solve(op, ws, sigmasq, variant, nullptr, z, nullptr, nprobes, 0.0, steps, 0, 1);
+    s.zero_x0 = 1;
+    return enqueue_persistent(op, s, steps_taken_dev, stream, &lz);
+}
+
+// The mean system of a fit: variant 0, one system, single-system stopping rule; the kernel forms the right-hand side ws .* fy, the
+// Jacobi diagonal (*diag_scale_dev) |ws|^2 + sigmasq and the zero start itself.  Hermitian: F*y of a real y, Toeplitz vector of
+// real weights.
+static CgSolve mean_solve(efgp_toeplitz_s* op, const void* ws, double sigmasq, const double* diag_scale_dev, const void* fy, void* x,
+                          double tol, int max_iter, int early_stop) {
+    CgSolve s = make_solve(op, ws, sigmasq, 0, nullptr, fy, x, 1, tol, max_iter, early_stop, 0);
+    s.diag_scale = diag_scale_dev;
+    s.b_times_ws = 1;
+    s.zero_x0 = 1;
+    s.hermitian = 1;
+    return s;
 }
 
 int efgp_cg_solve_mean_async(efgp_toeplitz_t* op, const void* ws, double sigmasq, const double* diag_scale_dev, const void* fy,
                              void* x, double tol, int max_iter, int early_stop, int* iters_dev, void* stream_) {
     EFGP_REQUIRE(op && ws && fy && x && iters_dev, "efgp_cg_solve_mean_async: null argument");
-    if (!op->persistent_ok || std::getenv("EFGP_NO_PERSISTENT_CG") != nullptr) {
-        // 2-D 128^2..512^2: the cooperative launch forms the right-hand side, the diagonal and the zero start itself as well (no
-        // prepare launch, no fill, no initial operator application); a dead grid barrier leaves iters = -3 and NaN
-        if (op->lines_ok && std::getenv("EFGP_NO_CG_COOP") == nullptr && std::getenv("EFGP_NO_CG_LINES") == nullptr) {
-            DeviceGuard guard_c(op->device, (hipStream_t)stream_);
-            if (max_iter <= 0) max_iter = (int)std::min<int64_t>(2 * op->g.M, 2000000000);
-            return coop_enqueue(op, ws, sigmasq, 0, nullptr, fy, x, 1, tol, max_iter, early_stop, 0, iters_dev, (hipStream_t)stream_, nullptr,
-                                /*nan_on_dead*/ 1, /*hermitian*/ 1, diag_scale_dev, /*b_times_ws*/ 1, /*zero_x0*/ 1);
-        }
+    if (!persistent_usable(op) && !coop_usable(op)) {
         set_error("efgp_cg_solve_mean_async: grid does not fit the persistent kernel");
         return EFGP_EUNSUPPORTED;
     }
     hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard guard(op->device, (hipStream_t)stream_);
-    if (max_iter <= 0) max_iter = (int)std::min<int64_t>(2 * op->g.M, 2000000000);
-    KernelTimer timer("cg_persistent", stream);
-    const ToepGeom* gq;
-    const double2* const* twq;
-    const double2* vq;
-    if (const int rc_ops = cg_operands(op, stream, &gq, &twq, &vq)) return rc_ops;
-    return persistent_cg_launch(*gq, twq, vq, (const double2*)ws, nullptr, sigmasq, 0, tol,
-                                early_stop, 0, max_iter, (const double2*)fy, (double2*)x, 1, iters_dev, stream, diag_scale_dev,
-                                1, 1, nullptr, /*hermitian: F*y of a real y, Toeplitz vector of real weights*/ 1,
-                                op->h48.vhat ? &op->h48 : nullptr);
+    DeviceGuard guard(op->device, stream);
+    const CgSolve s = mean_solve(op, ws, sigmasq, diag_scale_dev, fy, x, tol, max_iter, early_stop);
+    if (persistent_usable(op)) return enqueue_persistent(op, s, iters_dev, stream);
+    // 2-D 128^2..512^2: no prepare launch, no fill, no initial operator application; a dead grid barrier leaves iters = -3 and NaN
+    return coop_enqueue(op, s, iters_dev, stream, nullptr, /*nan_on_dead*/ 1);
 }
 
 int efgp_cg_solve_mean_fused(efgp_toeplitz_t* op, int kind, double nu, double lengthscale, double c0, double h, int mtot, void* ws_out,
@@ -3771,21 +3832,16 @@ int efgp_cg_solve_mean_fused(efgp_toeplitz_t* op, int kind, double nu, double le
     EFGP_REQUIRE(op && ws_out && fy && x && iters_dev, "efgp_cg_solve_mean_fused: null argument");
     EFGP_REQUIRE(kind == 0 || kind == 1, "efgp_cg_solve_mean_fused: kernel kind %d not built in", kind);
     // only an operator whose 48 x 48 spectrum is still to be made (efgp_toeplitz_create_ex, deferred) on a block of mtot^2 modes
-    if (!op->pair_pending || op->vhat48_ready || op->h48.vhat == nullptr || !op->persistent_ok || op->g.d != 2 || op->g.n[0] != mtot ||
-        op->g.n[1] != mtot || std::getenv("EFGP_NO_PERSISTENT_CG") != nullptr || std::getenv("EFGP_NO_CG_FUSED_MEAN") != nullptr) {
+    if (!op->pair_pending || op->vhat48_ready || op->h48.vhat == nullptr || !persistent_usable(op) || op->g.d != 2 || op->g.n[0] != mtot ||
+        op->g.n[1] != mtot || std::getenv("EFGP_NO_CG_FUSED_MEAN") != nullptr) {
         set_error("efgp_cg_solve_mean_fused: the operator is not a deferred 48 x 48 Hermitian one of this grid");
         return EFGP_EUNSUPPORTED;
     }
     hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard guard(op->device, (hipStream_t)stream_);
-    if (max_iter <= 0) max_iter = (int)std::min<int64_t>(2 * op->g.M, 2000000000);
-    KernelTimer timer("cg_persistent", stream);
-    const ToepGeom* gq = op->cg64 ? &op->g_cg : &op->g;
-    const double2* const* twq = (const double2* const*)(op->cg64 ? op->tw_cg : op->tw);
+    DeviceGuard guard(op->device, stream);
     const MeanFusedOperands fuse{kind, mtot, nu, lengthscale, c0, h, (double2*)ws_out, op->v_ref, (int)op->Ls[0], (int)op->Ls[1], op->vhat48};
-    const int rc = persistent_cg_launch(*gq, twq, nullptr, (const double2*)ws_out, nullptr, sigmasq, 0, tol, early_stop, 0, max_iter,
-                                        (const double2*)fy, (double2*)x, 1, iters_dev, stream, diag_scale_dev, 1, 1, nullptr, 1, &op->h48,
-                                        nullptr, &fuse);
+    const int rc = enqueue_persistent(op, mean_solve(op, ws_out, sigmasq, diag_scale_dev, fy, x, tol, max_iter, early_stop), iters_dev, stream,
+                                      nullptr, &fuse);
     if (rc == EFGP_OK) op->vhat48_ready = true;        // the 64 x 64 spectrum stays deferred: nothing on the fit path reads it
     return rc;
 }

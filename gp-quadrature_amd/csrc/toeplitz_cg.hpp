@@ -41,16 +41,38 @@ struct MeanFusedOperands {
     double2* vhat48_out;
 };
 
-// single-launch CG with the FFT in LDS (cg_persistent.hip)
+// One CG solve as every path takes it (persistent, cooperative, multi-launch): the system, the data and the stopping rule.  Plain
+// parameter grouping: a path ignores the fields it has no use for (x0 outside the persistent kernels, diag_scale / b_times_ws /
+// zero_x0 in the multi-launch solver).
+struct CgSolve {
+    const double2* ws = nullptr;
+    double sigmasq = 0.0;
+    int variant = 0;                       // 0 A_mean, 1 A_var
+    const double* diag = nullptr;          // Jacobi diagonal (device), or null
+    const double* diag_scale = nullptr;    // device scalar: the diagonal (*diag_scale) |ws|^2 + sigmasq is formed in the kernel
+    const double2* b = nullptr;
+    int b_times_ws = 0;                    // the right-hand side is ws .* b
+    double2* x = nullptr;
+    const double2* x0 = nullptr;           // start vectors when they are not in x (read before x is written)
+    int zero_x0 = 0;                       // x is output only
+    int nbatch = 1;
+    double tol = 0.0;
+    int max_iter = 0;
+    int early_stop = 0;
+    int batched = 0;                       // per-row stopping and the batched count (cg.py:190-243)
+    int hermitian = 0;                     // b, x0 and the Toeplitz vector are coefficient arrays of real functions
+    // no cap given: the reference's 2 M
+    void default_max_iter(int64_t M) {
+        if (max_iter <= 0) max_iter = (int)(2 * M < 2000000000 ? 2 * M : 2000000000);
+    }
+};
+
+// single-launch CG with the FFT in LDS (cg_persistent.hip).  h48 (may be null): 2-D blocks <= 23 x 23, Hermitian solves run on the
+// 48 x 48 grid.  lz: Lanczos mode.  fuse: 48 x 48 Hermitian mean solve only, ws and the spectrum made in the kernel.
 bool persistent_cg_eligible(const ToepGeom& g);
-int persistent_cg_launch(const ToepGeom& g, const double2* const* twiddles, const double2* vhat, const double2* ws,
-                         const double* diag, double sigmasq, int variant, double tol, int early_stop, int batched,
-                         int max_iter, const double2* b, double2* x, int rows, int* d_iters, hipStream_t stream,
-                         const double* diag_scale = nullptr, int b_times_ws = 0, int zero_x0 = 0, const LanczosOut* lz = nullptr,
-                         int hermitian = 0 /* b, x0 and the Toeplitz vector are coefficient arrays of real functions */,
-                         const Herm48Operands* h48 = nullptr /* 2-D blocks <= 23 x 23: Hermitian solves run on the 48 x 48 grid */,
-                         const double2* x0 = nullptr /* start vectors when they are not in x (read before x is written) */,
-                         const MeanFusedOperands* fuse = nullptr /* 48 x 48 Hermitian mean solve only: ws and the spectrum made in the kernel */);
+int persistent_cg_launch(const ToepGeom& g, const double2* const* twiddles, const double2* vhat, const Herm48Operands* h48,
+                         const CgSolve& s, int* d_iters, hipStream_t stream, const LanczosOut* lz = nullptr,
+                         const MeanFusedOperands* fuse = nullptr);
 
 // spectrum of the Toeplitz vector on the 64 x 64 circulant grid in one launch (cg_persistent.hip)
 bool toeplitz_vhat_fused_eligible(const ToepGeom& g);

@@ -384,3 +384,54 @@ def test_cooperative_solves_on_the_smallest_grid_equal_the_power_of_two_grid(n0,
         assert float(torch.linalg.norm(Ax - rhs) / torch.linalg.norm(rhs)) < 1.05e-8
     assert len(set(runs[True][2][2])) > 1             # per-row stopping happened in the batch
     assert runs[True][0][1] < 2 * n0 * n1            # the preconditioned mean system converged before its iteration cap
+
+
+def _replay_system(d, mtot, hermitian):
+    """Five right-hand sides on a (mtot,)*d block; Hermitian: conjugate-even rows and a real even ws (tests/test_gpu_cg_hermitian.py)."""
+    x, v, T = _setup(d, mtot, N=300, seed=9)
+    M = T.size
+    g = torch.Generator().manual_seed(21)
+    shape = (mtot,) * d
+    dims = tuple(range(d))
+    w = torch.exp(-2.5 * torch.rand(*shape, generator=g, dtype=torch.float64))
+    b = torch.complex(torch.randn(5, *shape, generator=g, dtype=torch.float64), torch.randn(5, *shape, generator=g, dtype=torch.float64))
+    if hermitian:
+        w = 0.5 * (w + torch.flip(w, dims=dims))
+        b = 0.5 * (b + torch.flip(b, dims=tuple(1 + a for a in dims)).conj())
+    b = 1e3 * b.reshape(5, M)                                       # (batched rows also stop at |r| < 1e-12: keep the capped run clear of it)
+    b[0] = 0.0                                                      # stops at once
+    return v, w.reshape(-1).to(torch.complex128), b
+
+
+@pytest.mark.parametrize("d,mtot,hook,hermitian", [(1, 35, "EFGP_NO_PERSISTENT_CG", False), (3, 7, "EFGP_NO_PERSISTENT_CG", False),
+                                                   (2, 41, "EFGP_NO_CG_COOP", False), (3, 17, None, False), (3, 17, None, True)],
+                         ids=["fft-1d", "fft-3d", "lines-2d", "lines-3d", "lines-3d-hermitian"])
+def test_graph_replay_equals_direct_enqueue(d, mtot, hook, hermitian, monkeypatch):
+    """The multi-launch iteration replays bursts of 8 iterations as a hipGraph per (slots, row map) state; EFGP_NO_CG_GRAPH enqueues
+    the same kernels one by one, as does the tail of a solve (fewer than 8 iterations left).  Both enqueue the same kernels in the
+    same order and every reduction has a fixed order, so counts and solutions are bit-equal -- on each of the four ways an
+    iteration applies the operator, with rows that leave in different polls (a 5 -> 3 compaction behind a slot map)."""
+    from efgp_hip import ToeplitzOp, cg_solve
+    v, ws, b = _replay_system(d, mtot, hermitian)
+    op = ToeplitzOp(v.cuda())
+    if hook:
+        monkeypatch.setenv(hook, "1")
+    args = (op, ws.cuda(), 0.3, 0, b.cuda())
+    x0 = torch.zeros_like(b).cuda()
+    x0[1] = cg_solve(*args, x0.clone(), 1e-9, batched=True, hermitian=hermitian)[0][1]     # row 1 starts from its own solution
+    res = {}
+    for mode in ("graph", "direct"):
+        if mode == "direct":
+            monkeypatch.setenv("EFGP_NO_CG_GRAPH", "1")
+        res[mode] = cg_solve(*args, x0.clone(), 1e-9, batched=True, hermitian=hermitian)
+        res[mode + "_cap"] = cg_solve(*args, x0.clone(), 1e-30, max_iter=13, batched=True, hermitian=hermitian)
+    rows = res["graph"][2]
+    print(f"\nd={d} mtot={mtot} hermitian={hermitian}: rows {rows} total {res['graph'][1]}; capped rows {res['graph_cap'][2]}")
+    assert any(abs(p - q) > 8 for p in rows for q in rows), rows       # rows left in different polls: compaction happened
+    assert res["graph_cap"][2][1:] == [13] * 4, res["graph_cap"][2]     # one replayed burst of 8, then a direct tail of 5
+    for key in ("", "_cap"):
+        xg, itg, rows_g = res["graph" + key]
+        xd, itd, rows_d = res["direct" + key]
+        assert rows_g == rows_d, (key, rows_g, rows_d)
+        assert itg == itd, (key, itg, itd)
+        assert torch.equal(xg, xd), (key, _rel(xg, xd))
