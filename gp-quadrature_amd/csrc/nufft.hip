@@ -16,6 +16,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <optional>
 #include <vector>
 
 #include "common.hpp"
@@ -1763,6 +1764,7 @@ struct InterpArgs {
     const double2* fine;     // [batch][cells]
     void* out;               // [batch][npts] complex or real
     const int* order;        // interp_real_halo_kernel: bank-balanced processing order over global 4096-point windows (or null)
+    const double* image;     // interp_real2_pair_kernel: its LDS contents ready-made in memory (modes_to_grid_real_kernel), or null
 };
 
 template <int D, int W, bool CPLX, bool USE_LDS>
@@ -1946,6 +1948,9 @@ __global__ __launch_bounds__(kInterpThreads) void interp_real_halo_kernel(Interp
 // ds_read2_b64 (8-byte alignment): twice the LDS cycles per byte (MI355X_MICROARCH section LDS), and the gather is
 // LDS-bound (PMC, round 1).  No processing order is needed: points are streamed as the caller holds them, so x
 // loads and result stores stay coalesced and no per-plan ordering pass exists.
+// 160 KiB of LDS hold 10240 16-byte elements: at most ten per thread in the image fill.
+constexpr int kPairFillTrips = (160 * 1024 / 16 + kInterpThreads - 1) / kInterpThreads;
+
 template <int W>
 __global__ __launch_bounds__(kInterpThreads) void interp_real2_pair_kernel(InterpArgs a) {
     extern __shared__ double lds[];
@@ -1955,12 +1960,30 @@ __global__ __launch_bounds__(kInterpThreads) void interp_real2_pair_kernel(Inter
     const int nf0 = (int)a.g.nf[0], nf1 = (int)a.g.nf[1];
     const int p0 = nf0 + W - 1, p1 = (nf1 + 2 * WP + 1) & ~1;            // even row pitch, room for the pair overhang
     const int plane = p0 * p1;
-    for (int i = threadIdx.x; i < 2 * plane; i += kInterpThreads) {
-        const int cp = i >= plane ? 1 : 0;
-        const int r = (i - cp * plane) / p1, c = (i - cp * plane) - r * p1 + cp;      // copy 1 holds column c + 1
-        int i0 = r >= nf0 ? r - nf0 : r;
-        int i1 = c % nf1;
-        lds[i] = F[(int64_t)i0 * nf1 + i1].x;
+    if (a.image) {
+        // The grid kernel has written both copies as they lie here: a flat copy of `plane` 16-byte elements, every load
+        // of a thread in flight before the first LDS store (the fill is one L2 round trip, not one per element).  A
+        // trip past the end copies the last element onto itself once more: with a branch round it the compiler sinks
+        // each load into its store's block and waits for it there, which is the serial fill again.
+        // Byte offsets in 32 bits serve both sides: scalar base + offset loads, and the same offsets into LDS.
+        const char* src = reinterpret_cast<const char*>(a.image);
+        char* dst = reinterpret_cast<char*>(lds);
+        const unsigned last = (unsigned)(plane - 1) * (unsigned)sizeof(double2);
+        double2 v[kPairFillTrips];
+#pragma unroll
+        for (int k = 0; k < kPairFillTrips; ++k)
+            v[k] = *reinterpret_cast<const double2*>(src + min((threadIdx.x + k * kInterpThreads) * (unsigned)sizeof(double2), last));
+#pragma unroll
+        for (int k = 0; k < kPairFillTrips; ++k)
+            *reinterpret_cast<double2*>(dst + min((threadIdx.x + k * kInterpThreads) * (unsigned)sizeof(double2), last)) = v[k];
+    } else {
+        for (int i = threadIdx.x; i < 2 * plane; i += kInterpThreads) {
+            const int cp = i >= plane ? 1 : 0;
+            const int r = (i - cp * plane) / p1, c = (i - cp * plane) - r * p1 + cp;      // copy 1 holds column c + 1
+            int i0 = r >= nf0 ? r - nf0 : r;
+            int i1 = c % nf1;
+            lds[i] = F[(int64_t)i0 * nf1 + i1].x;
+        }
     }
     __syncthreads();
     double* out = reinterpret_cast<double*>(a.out) + (int64_t)batch * a.npts;
@@ -2428,9 +2451,12 @@ static hipError_t launch_interp_halo_d(int W, dim3 grid, size_t lds_bytes, hipSt
     return hipErrorInvalidValue;
 }
 
+// Rows and even row pitch of one parity copy of interp_real2_pair_kernel, and the bytes of the two copies: the size of its
+// LDS and of the image that modes_to_grid_real_kernel writes for it.
+static int interp_pair_rows(int nf0, int W) { return nf0 + W - 1; }
+static int interp_pair_pitch(int nf1, int W) { return (nf1 + 2 * ((W + 1) / 2) + 1) & ~1; }
 static size_t interp_pair_lds_bytes(int nf0, int nf1, int W) {
-    const int wp = (W + 1) / 2;
-    return 2 * (size_t)(nf0 + W - 1) * (size_t)((nf1 + 2 * wp + 1) & ~1) * sizeof(double);
+    return 2 * (size_t)interp_pair_rows(nf0, W) * (size_t)interp_pair_pitch(nf1, W) * sizeof(double);
 }
 
 static hipError_t launch_interp_pair(int W, dim3 grid, size_t lds_bytes, hipStream_t s, const InterpArgs& a) {
@@ -3572,15 +3598,34 @@ static int type2_impl(efgp_nufft_t* plan, const void* f, const void* mode_scale,
     int rc = get_window(plan, n_modes, stream, &w);
     if (rc != EFGP_OK) return rc;
     const GridGeom g = make_geom(plan, w);
-    double2* fine = (double2*)scratch(ctx, SLOT_FINE, (size_t)nbatch * (size_t)g.cells * sizeof(double2));
-    if (!fine) return EFGP_ENOMEM;
-    ModeGeom m = make_modes(plan, w, n_modes, modeord);
     // small 2-D real-output transforms: the real fine grid by ONE dense-DFT launch instead of precorrect + two rocFFT kernels
     const bool direct_grid = real_only && nbatch == 1 && plan->dim == 2 &&
                              modes_to_grid_real_eligible((int)g.nf[0], (int)g.nf[1], (int)n_modes[0], (int)n_modes[1]);
+    const bool cplx = !real_only;
+    size_t lds_bytes = (size_t)g.cells * (cplx ? sizeof(double2) : sizeof(double));
+    // real outputs: halo-padded LDS copy when it fits (no wrap arithmetic in the gather)
+    size_t halo_cells = 1;
+    for (int a_ = 0; a_ < plan->dim; ++a_) halo_cells *= (size_t)(g.nf[a_] + w->p.w - 1);
+    const bool use_halo = !cplx && halo_cells * sizeof(double) <= (size_t)ctx->max_lds && std::getenv("EFGP_NO_HALO") == nullptr;
+    if (use_halo) lds_bytes = halo_cells * sizeof(double);
+    // 2-D real outputs whose two parity copies fit LDS: aligned 16-byte reads, no processing order
+    const size_t pair_bytes = plan->dim == 2 ? interp_pair_lds_bytes((int)g.nf[0], (int)g.nf[1], w->p.w) : 0;
+    const bool use_pair = use_halo && plan->dim == 2 && pair_bytes <= (size_t)ctx->max_lds && std::getenv("EFGP_NO_PAIR_GATHER") == nullptr;
+    if (use_pair) lds_bytes = pair_bytes;
+    // ... and the grid kernel writes those two copies itself, laid out as the gather holds them: the gather's fill is a flat copy
+    const bool use_image = direct_grid && use_pair && pair_bytes <= (size_t)kPairFillTrips * kInterpThreads * sizeof(double2) &&
+                           std::getenv("EFGP_NO_GATHER_IMAGE") == nullptr;
+    const size_t fine_bytes = (size_t)nbatch * (size_t)g.cells * sizeof(double2);
+    double2* fine = (double2*)scratch(ctx, SLOT_FINE, use_image ? std::max(fine_bytes, pair_bytes) : fine_bytes);
+    if (!fine) return EFGP_ENOMEM;
+    ModeGeom m = make_modes(plan, w, n_modes, modeord);
     if (direct_grid) {
+        const int img_p0 = interp_pair_rows((int)g.nf[0], w->p.w), img_p1 = interp_pair_pitch((int)g.nf[1], w->p.w);
+        std::optional<KernelTimer> grid_timer;          // names the route for whoever has to tell them apart (tests)
+        if (use_image) grid_timer.emplace("grid_image", stream);
         rc = modes_to_grid_real_launch(ctx, (const double2*)f, (const double2*)mode_scale, (int)n_modes[0], (int)n_modes[1], modeord, isign,
-                                       w->d_fac[0], w->d_fac[1], (int)g.nf[0], (int)g.nf[1], fine, stream);
+                                       w->d_fac[0], w->d_fac[1], (int)g.nf[0], (int)g.nf[1], fine, use_image ? (double*)fine : nullptr,
+                                       img_p0, img_p1, stream);
         if (rc != EFGP_OK) return rc;
     } else {
         int threads = 256;
@@ -3614,17 +3659,6 @@ static int type2_impl(efgp_nufft_t* plan, const void* f, const void* mode_scale,
             if (rc != EFGP_OK) return rc;
         }
     }
-    const bool cplx = !real_only;
-    size_t lds_bytes = (size_t)g.cells * (cplx ? sizeof(double2) : sizeof(double));
-    // real outputs: halo-padded LDS copy when it fits (no wrap arithmetic in the gather)
-    size_t halo_cells = 1;
-    for (int a_ = 0; a_ < plan->dim; ++a_) halo_cells *= (size_t)(g.nf[a_] + w->p.w - 1);
-    const bool use_halo = !cplx && halo_cells * sizeof(double) <= (size_t)ctx->max_lds && std::getenv("EFGP_NO_HALO") == nullptr;
-    if (use_halo) lds_bytes = halo_cells * sizeof(double);
-    // 2-D real outputs whose two parity copies fit LDS: aligned 16-byte reads, no processing order
-    const size_t pair_bytes = plan->dim == 2 ? interp_pair_lds_bytes((int)g.nf[0], (int)g.nf[1], w->p.w) : 0;
-    const bool use_pair = use_halo && plan->dim == 2 && pair_bytes <= (size_t)ctx->max_lds && std::getenv("EFGP_NO_PAIR_GATHER") == nullptr;
-    if (use_pair) lds_bytes = pair_bytes;
     const bool use_lds = lds_bytes <= (size_t)ctx->max_lds;
     // grids beyond LDS: tile-sorted points + LDS tiles (the binning is shared with the tiled spreader when the
     // tile geometry coincides, and cached in the plan otherwise)
@@ -3668,6 +3702,7 @@ static int type2_impl(efgp_nufft_t* plan, const void* f, const void* mode_scale,
     a.coef = w->d_coef;
     a.degree = w->p.degree;
     a.fine = fine;
+    a.image = use_image ? (const double*)fine : nullptr;
     a.out = out;
     const int thr = use_lds ? kInterpThreads : kInterpThreadsGlobal;
     int64_t want = (plan->npts + thr - 1) / thr;

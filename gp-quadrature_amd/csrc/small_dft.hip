@@ -2,8 +2,8 @@
 //
 // At N = 1e6 the fit + mean step spends ~45 us in nine dependent small launches around the two N-scale kernels, each
 // 4.4-5 us, i.e. launch latency, for ~1 MFLOP of work.  On the type-2 side (precorrect + two rocFFT kernels, 14 us) a
-// separable dense DFT from the 23 x 23 modes to the 48 x 48 real fine grid is ONE launch of 5.4 us (and sums in a fixed
-// order in double: at least as accurate as the FFT route).  The same idea on the type-1 side (int64 grid 96 x 96 x 2 ->
+// separable dense DFT from the 23 x 23 modes to the real fine grid (the headline's: 64 x 64 cells at tolerance 1e-7) is
+// ONE launch of about 6 us (and sums in a fixed order in double: at least as accurate as the FFT route).  The same idea on the type-1 side (int64 grid 96 x 96 x 2 ->
 // two mode boxes, replacing reduce + two rocFFT kernels + deconvolve = 19 us) measured 16.7-21 us in one launch: every
 // workgroup has to pull the 147-KB grid through L2 and walk 96-term sums serially -- not kept.
 // Reference operation replaced: the mode placement / correction + FFT inside finufft type 2 (efgpnd.py:1533-1536).
@@ -24,11 +24,16 @@ struct M2GArgs {
     const double *fac0, *fac1;
     int nf0, nf1;
     double2* fine;
+    double* image;      // non-null: write the pair gather's LDS image (nufft.hip, interp_real2_pair_kernel) instead of `fine`
+    int p0, p1;         // image rows and row pitch
 };
 
 // One workgroup per fine-grid row x0.  The corrected modes c = fac f mul go to LDS first (coalesced, CMCL order);
 // t[k1] = sum_k0 c[k0][k1] e(k0 x0) with all threads (k1 x a slice of k0, combined through LDS); then
 // fine[x0][x1] = Re sum_k1 t[k1] e(k1 x1).  Phases advance by addition.
+// Image mode: the same doubles go straight to every place they hold in the gather's two halo-padded parity copies
+// (copy cp at [r][c] is Re fine[r mod nf0][(c + cp) mod nf1]), so the gather's workgroups fill their LDS with a flat copy
+// instead of each redoing the wrap, the real/imaginary split and the parity shift.
 __global__ __launch_bounds__(kDftThreads) void modes_to_grid_real_kernel(M2GArgs a) {
     __shared__ double2 tw0[kDftMaxNf], tw1[kDftMaxNf], t[64], part[4][64];
     extern __shared__ double2 cm[];                                   // [nm0][nm1] corrected modes, CMCL order
@@ -93,7 +98,16 @@ __global__ __launch_bounds__(kDftThreads) void modes_to_grid_real_kernel(M2GArgs
             ph += x1;
             ph = ph >= nf1 ? ph - nf1 : ph;
         }
-        a.fine[(int64_t)x0 * nf1 + x1] = make_double2(re, 0.0);
+        if (a.image == nullptr) {
+            a.fine[(int64_t)x0 * nf1 + x1] = make_double2(re, 0.0);
+            continue;
+        }
+        const int p1 = a.p1, plane = a.p0 * p1;
+        for (int r = x0; r < a.p0; r += nf0) {
+            double* row = a.image + r * p1;
+            for (int c = x1; c < p1; c += nf1) row[c] = re;
+            for (int c = x1 == 0 ? nf1 - 1 : x1 - 1; c < p1; c += nf1) row[plane + c] = re;      // copy 1 holds column c + 1
+        }
     }
 }
 
@@ -102,9 +116,10 @@ bool modes_to_grid_real_eligible(int nf0, int nf1, int nm0, int nm1) {
 }
 
 int modes_to_grid_real_launch(DeviceCtx* ctx, const double2* f, const double2* mul, int nm0, int nm1, int modeord, int isign,
-                              const double* fac0, const double* fac1, int nf0, int nf1, double2* fine, hipStream_t stream) {
+                              const double* fac0, const double* fac1, int nf0, int nf1, double2* fine, double* image, int p0, int p1,
+                              hipStream_t stream) {
     (void)ctx;
-    M2GArgs a{f, mul, nm0, nm1, modeord, isign, fac0, fac1, nf0, nf1, fine};
+    M2GArgs a{f, mul, nm0, nm1, modeord, isign, fac0, fac1, nf0, nf1, fine, image, p0, p1};
     const size_t lds = (size_t)nm0 * nm1 * sizeof(double2);
     if (lds > 32 * 1024) EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)modes_to_grid_real_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(modes_to_grid_real_kernel, dim3(nf0), dim3(kDftThreads), lds, stream, a);

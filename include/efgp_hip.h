@@ -49,7 +49,8 @@ int efgp_release_workspaces(int device);
 
 /* ---- per-kernel timing (HIP events recorded on the launch stream around selected kernels) -----
  * enable != 0 starts recording (and clears previous records).  Names: "spread", "interp",
- * "cg_iteration" (one pad+FFT+multiply+FFT+update group).  efgp_kernel_timing_read synchronises the
+ * "cg_iteration" (one pad+FFT+multiply+FFT+update group), "grid_image" (the dense-DFT grid launch of a
+ * type 2 when it writes the pair gather's LDS image).  efgp_kernel_timing_read synchronises the
  * device and returns the summed duration (ms) and launch count of `name` since enabling. */
 int efgp_kernel_timing(int enable);
 /* Restrict the timers to the launches of one name (NULL or "": all names): two event records per timed launch sit in the
