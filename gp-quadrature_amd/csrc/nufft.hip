@@ -2921,225 +2921,334 @@ static int transform_fine(efgp_nufft_s* plan, const GridGeom& g, double2* fine, 
     return EFGP_OK;
 }
 
-// spread + reduce + FFT; leaves the transformed fine grids in SLOT_FINE
-static int spread_and_fft(efgp_nufft_s* plan, WindowSet* w, const double* c, int mode, int nbatch, int isign,
-                          hipStream_t stream, double2** fine_out, unsigned long long seed = 0, int64_t index_offset = 0,
-                          const double** scale_out = nullptr, G2MRequest* req = nullptr, const double* point_scale = nullptr) {
-    DeviceCtx* ctx = plan->ctx;
-    const GridGeom g = make_geom(plan, w);
-    if (scale_out) *scale_out = nullptr;
+// What one type-1 pass spreads: where the strengths come from and what that means for the channel count and the fixed-point
+// scale.  make_spread_job fills it once per pass; what a strength mode implies on the host is decided there and nowhere else.
+struct SpreadJob {
+    StrengthSrc src;
+    int channels;            // real channels per fine grid: 2 for complex strengths and for two real rows sharing one grid
+    bool need_max;           // the scale follows max|max_src[0 .. nvals)|, found by a pass over memory
+    double floor_bound;      // bound on the strengths that is known without looking (0: none)
+    const double* max_src;
+    double max_mult;         // the strengths are bounded by max_mult * max|max_src|
+    int64_t nvals;
+    int ones_channel;        // channel 1 is the implicit all-ones channel of the fused fit pass: it keeps a scale of its own
+};
+
+static SpreadJob make_spread_job(int mode, const double* c, const double* point_scale, int nbatch, int64_t npts,
+                                 unsigned long long seed = 0, int64_t index_offset = 0) {
+    const bool normal = strength_is_normal(mode);
     // generated normals times a per-point factor (point_scale, npts doubles by original index): |c| <= kNormalBound * max(point_scale),
     // so the max pass runs over the N factors and its result is multiplied by the normals' bound on the device
-    const bool scaled = point_scale != nullptr && strength_is_normal(mode);
-    const int channels = (mode == STR_COMPLEX || mode == STR_REAL_AND_ONES || mode == STR_REAL_PAIR || mode == STR_RNG_PAIR ||
-                          mode == STR_NORMAL_PAIR) ? 2 : 1;
+    const bool scaled = point_scale != nullptr && normal;
+    const bool from_memory = mode == STR_REAL || mode == STR_COMPLEX || mode == STR_REAL_AND_ONES || mode == STR_REAL_PAIR;
+    const bool two_channels = mode == STR_COMPLEX || mode == STR_REAL_AND_ONES || mode == STR_REAL_PAIR || mode == STR_RNG_PAIR ||
+                              mode == STR_NORMAL_PAIR;
+    const bool unit = mode == STR_REAL_AND_ONES || mode == STR_ONES || mode == STR_RNG || mode == STR_RNG_PAIR;
+    const bool two_per_point = mode == STR_COMPLEX || mode == STR_REAL_PAIR;
+    SpreadJob j;
+    j.src = StrengthSrc{c, npts, mode, seed, index_offset, scaled ? point_scale : nullptr};
+    j.channels = two_channels ? 2 : 1;
     // strengths read from memory need a max|c| pass for the fixed-point scale; generated / implicit ones are +-1
-    const bool need_max = (mode == STR_REAL || mode == STR_COMPLEX || mode == STR_REAL_AND_ONES || mode == STR_REAL_PAIR) || scaled;
+    j.need_max = from_memory || scaled;
     // generated normals are bounded by construction (kNormalBound): the scale is sized for that bound, no pass over data
-    const double floor_bound = scaled ? 0.0 : strength_is_normal(mode) ? kNormalBound
-                               : (mode == STR_REAL_AND_ONES || mode == STR_ONES || mode == STR_RNG || mode == STR_RNG_PAIR) ? 1.0 : 0.0;
-    const double* max_src = scaled ? point_scale : c;
-    const double max_mult = scaled ? kNormalBound : 1.0;
-    const int64_t nvals = (mode == STR_REAL_AND_ONES || scaled) ? plan->npts
-                          : (int64_t)nbatch * plan->npts * ((mode == STR_COMPLEX || mode == STR_REAL_PAIR) ? 2 : 1);
-    StrengthSrc src;
-    src.c = c;
-    src.npts = plan->npts;
-    src.mode = mode;
-    src.seed = seed;
-    src.index_offset = index_offset;
-    src.scale = scaled ? point_scale : nullptr;
-    const size_t lds_bytes = (size_t)channels * (size_t)g.cells * sizeof(double);
-    const bool use_lds = lds_bytes <= (size_t)ctx->max_lds && plan->npts > 0;
-    // 2-D plans made on a per-model point layout (efgp_nufft_create_on): MFMA register accumulation over
-    // (band, x_0)-sorted points, no per-plan sorting (spread_mfma.hip)
-    int band_cells = 8;
-    if (SortedLevel* lvl = pick_level(plan, w, g, stream, &band_cells)) {
-        const double* ys = nullptr;
-        if (c && c == plan->points->values && (mode == STR_REAL_AND_ONES || (mode == STR_REAL && nbatch == 1))) {
-            int rc = points_level_values(plan->points, lvl, stream);
-            if (rc != EFGP_OK) return rc;
-            ys = lvl->ys;
-        }
-        const size_t acc_bytes = (size_t)nbatch * channels * (size_t)g.cells * sizeof(long long);
-        const size_t known_zero = ctx->slabs_zero_bytes;
-        const void* slabs_before = ctx->buf[SLOT_SLABS];
-        unsigned long long* gacc = (unsigned long long*)scratch(ctx, SLOT_SLABS, acc_bytes);
-        double2* fine = (double2*)scratch(ctx, SLOT_FINE, (size_t)nbatch * (size_t)g.cells * sizeof(double2));
-        char* misc = scale_slot(ctx, stream);
-        if (!gacc || !fine || !misc) return EFGP_ENOMEM;
-        double* d_scale = (double*)misc;
-        unsigned long long* d_cmax = (unsigned long long*)(misc + 56);
-        if (scale_out) *scale_out = d_scale;
-        // the converting kernel below zeroes what it reads: back-to-back passes of this path need no memset launch
-        if (known_zero < acc_bytes || slabs_before != (const void*)gacc) EFGP_HIP_CHECK(hipMemsetAsync(gacc, 0, acc_bytes, stream));
-        // the global int64 grid sums over ALL points: the scale is bounded with N
-        ScaleJob job{floor_bound, mode == STR_REAL_AND_ONES ? 1 : 0, plan->npts, d_scale, 61, max_mult};
-        if (need_max && ys && plan->points->d_values_max && mode == STR_REAL_AND_ONES) {
-            // the fit-time pair on the attached targets: max|y|, N and the bit budget are fixed per model, so the scale block is
-            // computed once per attach and kept with the layout (one launch less per fit)
-            efgp_points_s* pts = plan->points;
-            d_scale = pts->d_pair_scale;
-            job.scale = d_scale;
-            if (scale_out) *scale_out = d_scale;
-            if (!pts->pair_scale_ready) {
-                hipLaunchKernelGGL(fixed_scale_cached_kernel, dim3(1), dim3(64), 0, stream, (const unsigned long long*)pts->d_values_max, job);
-                pts->pair_scale_ready = true;
-            }
-        } else if (need_max && ys && plan->points->d_values_max) {
-            hipLaunchKernelGGL(fixed_scale_cached_kernel, dim3(1), dim3(64), 0, stream,
-                               (const unsigned long long*)plan->points->d_values_max, job);
-        } else if (need_max) {
-            const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((nvals + 8191) / 8192, 256));
-            hipLaunchKernelGGL(maxabs_kernel, dim3(blocks), dim3(1024), 0, stream, max_src, nvals, d_cmax,
-                               (unsigned int*)(misc + 48), job);
-        } else {
-            // generated +-1 probes / implicit ones: the block depends on (floor, N, bit budget) only -- constant for the layout
-            efgp_points_s* pts = plan->points;
-            if (floor_bound == 1.0 && job.ones_channel == 0) {
-                if (!pts->d_fixed_scale) EFGP_HIP_CHECK(hipMalloc((void**)&pts->d_fixed_scale, 64));
-                d_scale = pts->d_fixed_scale;
-                job.scale = d_scale;
-                if (scale_out) *scale_out = d_scale;
-            }
-            if (job.scale != pts->d_fixed_scale || !pts->fixed_scale_ready) {
-                hipLaunchKernelGGL(fixed_scale_kernel, dim3(1), dim3(64), 0, stream, job.floor_bound, job.ones_channel, job.per,
-                                   job.scale, job.sum_bits);
-                if (job.scale == pts->d_fixed_scale) pts->fixed_scale_ready = true;
-            }
-        }
-        EFGP_HIP_CHECK(hipGetLastError());
-        int rc = spread_mfma_launch(ctx, lvl, band_cells, ys, src, g, w->p.w, w->d_coef, w->p.degree, channels, nbatch, gacc, d_scale, stream);
-        if (rc != EFGP_OK) return rc;
-        if (g2m_eligible(plan, g, req)) {
-            rc = g2m_launch(ctx, g, req, (long long*)gacc, nullptr, d_scale, channels, nbatch, isign, (unsigned int*)(misc + 40),
-                            (long long)(acc_bytes / sizeof(long long)), stream);
-            if (rc != EFGP_OK) return rc;
-            ctx->slabs_zero_bytes = zero_extent_after(acc_bytes, known_zero, slabs_before == (const void*)gacc);
-            *fine_out = nullptr;
-            return EFGP_OK;
-        }
-        const FftAccSource accsrc{(long long*)gacc, channels, g.cells, (const double*)d_scale, 1};     // converted (and cleared) by whoever reads it
-        ctx->slabs_zero_bytes = zero_extent_after(acc_bytes, known_zero, slabs_before == (const void*)gacc);
-        return transform_fine(plan, g, fine, nbatch, isign, stream, req, scale_out ? *scale_out : nullptr, fine_out, &accsrc);
+    j.floor_bound = scaled ? 0.0 : normal ? kNormalBound : unit ? 1.0 : 0.0;
+    j.max_src = scaled ? point_scale : c;
+    j.max_mult = scaled ? kNormalBound : 1.0;
+    j.nvals = (mode == STR_REAL_AND_ONES || scaled) ? npts : (int64_t)nbatch * npts * (two_per_point ? 2 : 1);
+    j.ones_channel = mode == STR_REAL_AND_ONES ? 1 : 0;
+    return j;
+}
+
+// `per` = the most points whose strengths one integer sum adds up, sum_bits = the bits that sum may take
+static ScaleJob scale_job(const SpreadJob& job, int64_t per, int sum_bits, double* scale) {
+    return ScaleJob{job.floor_bound, job.ones_channel, per, scale, sum_bits, job.max_mult};
+}
+
+// The fixed-point scale block of a pass, computed on the device (no host round trip): maxabs_kernel over the job's values when
+// the bound has to be looked for, fixed_scale_kernel when it is known.  `misc` is scale_slot's block.
+static void enqueue_scale(const SpreadJob& job, const ScaleJob& sj, char* misc, hipStream_t stream) {
+    if (job.need_max) {
+        const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((job.nvals + 8191) / 8192, 256));
+        hipLaunchKernelGGL(maxabs_kernel, dim3(blocks), dim3(1024), 0, stream, job.max_src, job.nvals, (unsigned long long*)(misc + 56),
+                           (unsigned int*)(misc + 48), sj);
+    } else {
+        hipLaunchKernelGGL(fixed_scale_kernel, dim3(1), dim3(64), 0, stream, sj.floor_bound, sj.ones_channel, sj.per, sj.scale,
+                           sj.sum_bits);
     }
-    // 2-D with many points per fine-grid cell: register accumulation over base-cell-sorted points
+}
+
+// f(std::integral_constant<int, D>) for the plan's dimension: the launchers are templates on it
+template <class F>
+static inline hipError_t by_dim(int dim, F&& f) {
+    if (dim == 1) return f(std::integral_constant<int, 1>{});
+    if (dim == 2) return f(std::integral_constant<int, 2>{});
+    return f(std::integral_constant<int, 3>{});
+}
+
+// The plan's bank-balanced processing order for this fine grid and window (class_order_kernel), computed on first use and kept
+// with the plan.  nwg > 0: for the padded spreader's launch of nwg workgroups with `per` points each; nwg == 0 marks the halo
+// gather's layout, global windows of kOrderWindow points (same classes: row pitch nf + W - 1).  d >= 2 only.
+static int get_class_order(efgp_nufft_s* plan, const WindowSet* w, const GridGeom& g, int nwg, int64_t per, hipStream_t stream,
+                           const int** out) {
+    ClassOrder* co = nullptr;
+    for (ClassOrder* o : plan->orders)
+        if (o->W == w->p.w && o->nwg == nwg && o->nf[0] == g.nf[0] && o->nf[1] == g.nf[1] && o->nf[2] == g.nf[2]) co = o;
+    if (!co) {
+        co = new ClassOrder();
+        for (int q = 0; q < 3; ++q) co->nf[q] = g.nf[q];
+        co->W = w->p.w;
+        co->nwg = nwg;
+        co->bytes = (size_t)plan->npts * sizeof(int);
+        co->order = (int*)pool_alloc(plan->ctx, co->bytes);
+        if (!co->order) {
+            delete co;
+            return EFGP_ENOMEM;
+        }
+        const unsigned blocks = nwg > 0 ? (unsigned)nwg : (unsigned)((plan->npts + kOrderWindow - 1) / kOrderWindow);
+        if (nwg == 0) per = kOrderWindow;
+        KernelTimer order_timer("order", stream);
+        if (plan->dim == 2)
+            hipLaunchKernelGGL((class_order_kernel<2, 16>), dim3(blocks), dim3(kSpreadThreads), 0, stream, g, w->p.w, plan->x, plan->npts, per,
+                               co->order);
+        else
+            hipLaunchKernelGGL((class_order_kernel<3, 16>), dim3(blocks), dim3(kSpreadThreads), 0, stream, g, w->p.w, plan->x, plan->npts, per,
+                               co->order);
+        EFGP_HIP_CHECK(hipGetLastError());
+        plan->orders.push_back(co);
+    }
+    *out = co->order;
+    return EFGP_OK;
+}
+
+struct SpreadCall {           // one spread_and_fft call as its four routes see it
+    efgp_nufft_s* plan;
+    WindowSet* w;
+    GridGeom g;
+    const SpreadJob& job;
+    int nbatch, isign;
+    hipStream_t stream;
+    G2MRequest* req;
+    double2** fine_out;
+    bool want_scale;                  // the caller asked where the pass's scale block is (type1_pair: deconvolve_pair_kernel reads it)
+    const double* scale = nullptr;    // ... and this is the answer; stays null for a caller that did not ask
+    void publish_scale(const double* d_scale) {
+        if (want_scale) scale = d_scale;
+    }
+};
+
+// The single int64 fine-grid accumulator of the layout and the tiled route in SLOT_SLABS, with the pass's other two buffers.
+// Whoever converts the accumulator (reduce_slabs_kernel with reset_source, the grid-to-modes kernels, the pruned transform's
+// first pass) clears what it reads, so back-to-back passes need no memset launch: the context remembers how long a prefix of the
+// slot is known to be zero, acquire_int64_grid clears only when that is too short, int64_grid_converted renews it.
+struct Int64Grid {
+    long long* gacc = nullptr;
+    double2* fine = nullptr;
+    char* misc = nullptr;             // scale_slot's block
+    size_t acc_bytes = 0;
+    size_t known_zero = 0;            // zero prefix of the slot before this pass
+    bool same_buffer = false;         // the slot did not move when this pass asked for its size
+};
+static int acquire_int64_grid(const SpreadCall& s, Int64Grid* a) {
+    DeviceCtx* ctx = s.plan->ctx;
+    hipStream_t stream = s.stream;
+    const size_t acc_bytes = a->acc_bytes = (size_t)s.nbatch * s.job.channels * (size_t)s.g.cells * sizeof(long long);
+    // scratch(SLOT_SLABS) resets the context's zero extent -- every other user of the slot (LDS slabs, the cell-sorted route's
+    // doubles) leaves it dirty -- so the extent and the buffer it speaks of are read BEFORE the call that asks for this pass's size
+    a->known_zero = ctx->slabs_zero_bytes;
+    const void* slabs_before = ctx->buf[SLOT_SLABS];
+    long long* gacc = a->gacc = (long long*)scratch(ctx, SLOT_SLABS, acc_bytes);
+    a->fine = (double2*)scratch(ctx, SLOT_FINE, (size_t)s.nbatch * (size_t)s.g.cells * sizeof(double2));
+    a->misc = scale_slot(ctx, stream);
+    if (!gacc || !a->fine || !a->misc) return EFGP_ENOMEM;
+    a->same_buffer = slabs_before == (const void*)gacc;
+    if (a->known_zero < acc_bytes || !a->same_buffer) EFGP_HIP_CHECK(hipMemsetAsync(gacc, 0, acc_bytes, stream));
+    return EFGP_OK;
+}
+// once the pass's converting kernel is enqueued (or about to be: nothing else touches the slot in between)
+static void int64_grid_converted(DeviceCtx* ctx, const Int64Grid& a) {
+    ctx->slabs_zero_bytes = zero_extent_after(a.acc_bytes, a.known_zero, a.same_buffer);
+}
+
+// 2-D plans made on a per-model point layout (efgp_nufft_create_on): MFMA register accumulation over
+// (band, x_0)-sorted points, no per-plan sorting (spread_mfma.hip)
+static int spread_on_layout(SpreadCall& s, SortedLevel* lvl, int band_cells) {
+    efgp_nufft_s* plan = s.plan;
+    efgp_points_s* pts = plan->points;
+    const SpreadJob& job = s.job;
+    hipStream_t stream = s.stream;
+    const double* ys = nullptr;
+    if (job.src.c && job.src.c == pts->values && (job.ones_channel || (job.src.mode == STR_REAL && s.nbatch == 1))) {
+        int rc = points_level_values(pts, lvl, stream);
+        if (rc != EFGP_OK) return rc;
+        ys = lvl->ys;
+    }
+    Int64Grid a;
+    int rc = acquire_int64_grid(s, &a);
+    if (rc != EFGP_OK) return rc;
+    double* d_scale = (double*)a.misc;
+    // the global int64 grid sums over ALL points: the scale is bounded with N
+    ScaleJob sj = scale_job(job, plan->npts, 61, d_scale);
+    const bool cached_max = job.need_max && ys && pts->d_values_max;
+    if (cached_max && job.ones_channel) {
+        // the fit-time pair on the attached targets: max|y|, N and the bit budget are fixed per model, so the scale block is
+        // computed once per attach and kept with the layout (one launch less per fit)
+        sj.scale = d_scale = pts->d_pair_scale;
+        if (!pts->pair_scale_ready) {
+            hipLaunchKernelGGL(fixed_scale_cached_kernel, dim3(1), dim3(64), 0, stream, (const unsigned long long*)pts->d_values_max, sj);
+            pts->pair_scale_ready = true;
+        }
+    } else if (cached_max) {
+        hipLaunchKernelGGL(fixed_scale_cached_kernel, dim3(1), dim3(64), 0, stream, (const unsigned long long*)pts->d_values_max, sj);
+    } else if (!job.need_max && job.floor_bound == 1.0 && !job.ones_channel) {
+        // generated +-1 probes / implicit ones: the block depends on (floor, N, bit budget) only -- constant for the layout
+        if (!pts->d_fixed_scale) EFGP_HIP_CHECK(hipMalloc((void**)&pts->d_fixed_scale, 64));
+        sj.scale = d_scale = pts->d_fixed_scale;
+        if (!pts->fixed_scale_ready) {
+            enqueue_scale(job, sj, a.misc, stream);
+            pts->fixed_scale_ready = true;
+        }
+    } else {
+        enqueue_scale(job, sj, a.misc, stream);
+    }
+    EFGP_HIP_CHECK(hipGetLastError());
+    s.publish_scale(d_scale);
+    rc = spread_mfma_launch(plan->ctx, lvl, band_cells, ys, job.src, s.g, s.w->p.w, s.w->d_coef, s.w->p.degree, job.channels, s.nbatch,
+                            (unsigned long long*)a.gacc, d_scale, stream);
+    if (rc != EFGP_OK) return rc;
+    if (g2m_eligible(plan, s.g, s.req)) {
+        rc = g2m_launch(plan->ctx, s.g, s.req, a.gacc, nullptr, d_scale, job.channels, s.nbatch, s.isign, (unsigned int*)(a.misc + 40),
+                        (long long)(a.acc_bytes / sizeof(long long)), stream);
+        if (rc != EFGP_OK) return rc;
+        int64_grid_converted(plan->ctx, a);
+        *s.fine_out = nullptr;
+        return EFGP_OK;
+    }
+    const FftAccSource accsrc{a.gacc, job.channels, s.g.cells, (const double*)d_scale, 1};     // converted (and cleared) by whoever reads it
+    int64_grid_converted(plan->ctx, a);
+    return transform_fine(plan, s.g, a.fine, s.nbatch, s.isign, stream, s.req, s.scale, s.fine_out, &accsrc);
+}
+
+// 2-D with many points per fine-grid cell: register accumulation over base-cell-sorted points.
+// Opt-in (EFGP_CELLSORT=1): the kernel itself is 1.2-1.7x faster than the LDS-atomic spreader at >= 250 points
+// per cell, but the per-plan counting sort it needs (0.15 ms at N=1e6, 0.6 ms at N=1e7) only pays off after
+// several passes over the same plan; see LABNOTES.md section 4.1.
+static bool cell_sort_wanted(const SpreadCall& s, TileGeom* cg) {
+    const efgp_nufft_s* plan = s.plan;
+    const EsParams& p = s.w->p;
+    const char* force = std::getenv("EFGP_CELLSORT");
+    const bool use_cells = force && force[0] == '1' && !strength_is_normal(s.job.src.mode) && plan->dim == 2 && p.w <= kCellMaxW &&
+                           p.degree <= p.w + 4 && s.g.cells <= 16384 && plan->npts > 0;
+    return use_cells && make_tile_geom(plan, s.w, s.job.channels, (size_t)plan->ctx->max_lds - 4096, cg, 1);
+}
+static int spread_cell_sorted(SpreadCall& s, const TileGeom& cg) {
+    efgp_nufft_s* plan = s.plan;
+    DeviceCtx* ctx = plan->ctx;
+    const WindowSet* w = s.w;
+    const GridGeom& g = s.g;
+    const int channels = s.job.channels, nbatch = s.nbatch;
+    hipStream_t stream = s.stream;
+    BinSet* bins = nullptr;
+    int rc = get_bins(plan, cg, channels, stream, &bins);
+    if (rc != EFGP_OK) return rc;
+    const size_t acc_bytes = (size_t)nbatch * channels * (size_t)g.cells * sizeof(double);
+    double* gacc = (double*)scratch(ctx, SLOT_SLABS, acc_bytes);
+    double2* fine = (double2*)scratch(ctx, SLOT_FINE, (size_t)nbatch * (size_t)g.cells * sizeof(double2));
+    if (!gacc || !fine) return EFGP_ENOMEM;
+    EFGP_HIP_CHECK(hipMemsetAsync(gacc, 0, acc_bytes, stream));
+    CellSpreadArgs ca;
+    ca.t = cg;
+    ca.xs = bins->xs;
+    ca.order = bins->order;
+    ca.start = bins->start;
+    ca.src = s.job.src;
+    ca.coef = w->d_coef;
+    ca.channels = channels;
+    ca.gacc = gacc;
+    ca.cells = g.cells;
+    // enough wavefronts for a few rounds of the chip's resident waves, chunks long enough to amortise the flushes
+    // one chunk per resident wave slot (2 per SIMD) when N is large: balanced, one prologue per wave
+    int64_t chunk = (plan->npts + 8 * (int64_t)ctx->num_cu - 1) / (8 * (int64_t)ctx->num_cu);
+    chunk = std::max<int64_t>(256, (chunk + 63) / 64 * 64);
+    if (const char* ce = std::getenv("EFGP_CELL_CHUNK")) chunk = std::max(64, std::atoi(ce) / 64 * 64);   // diagnostics
+    ca.npts = (int)plan->npts;
+    ca.chunk = (int)chunk;
+    const int64_t nwaves = (plan->npts + chunk - 1) / chunk;
+    const int blocks = (int)((nwaves + 3) / 4);
+    hipError_t e;
     {
-        // Opt-in (EFGP_CELLSORT=1): the kernel itself is 1.2-1.7x faster than the LDS-atomic spreader at >= 250 points
-        // per cell, but the per-plan counting sort it needs (0.15 ms at N=1e6, 0.6 ms at N=1e7) only pays off after
-        // several passes over the same plan; see LABNOTES.md section 4.1.
-        const char* force = std::getenv("EFGP_CELLSORT");
-        const bool use_cells = force && force[0] == '1' && !strength_is_normal(mode) && plan->dim == 2 && w->p.w <= kCellMaxW &&
-                               w->p.degree <= w->p.w + 4 && g.cells <= 16384 && plan->npts > 0;
-        TileGeom cg;
-        if (use_cells && make_tile_geom(plan, w, channels, (size_t)ctx->max_lds - 4096, &cg, 1)) {
-            BinSet* bins = nullptr;
-            int rc = get_bins(plan, cg, channels, stream, &bins);
-            if (rc != EFGP_OK) return rc;
-            const size_t acc_bytes = (size_t)nbatch * channels * (size_t)g.cells * sizeof(double);
-            double* gacc = (double*)scratch(ctx, SLOT_SLABS, acc_bytes);
-            double2* fine = (double2*)scratch(ctx, SLOT_FINE, (size_t)nbatch * (size_t)g.cells * sizeof(double2));
-            if (!gacc || !fine) return EFGP_ENOMEM;
-            EFGP_HIP_CHECK(hipMemsetAsync(gacc, 0, acc_bytes, stream));
-            CellSpreadArgs ca;
-            ca.t = cg;
-            ca.xs = bins->xs;
-            ca.order = bins->order;
-            ca.start = bins->start;
-            ca.src = src;
-            ca.coef = w->d_coef;
-            ca.channels = channels;
-            ca.gacc = gacc;
-            ca.cells = g.cells;
-            // enough wavefronts for a few rounds of the chip's resident waves, chunks long enough to amortise the flushes
-            // one chunk per resident wave slot (2 per SIMD) when N is large: balanced, one prologue per wave
-            int64_t chunk = (plan->npts + 8 * (int64_t)ctx->num_cu - 1) / (8 * (int64_t)ctx->num_cu);
-            chunk = std::max<int64_t>(256, (chunk + 63) / 64 * 64);
-            if (const char* ce = std::getenv("EFGP_CELL_CHUNK")) chunk = std::max(64, std::atoi(ce) / 64 * 64);   // diagnostics
-            ca.npts = (int)plan->npts;
-            ca.chunk = (int)chunk;
-            const int64_t nwaves = (plan->npts + chunk - 1) / chunk;
-            const int blocks = (int)((nwaves + 3) / 4);
-            hipError_t e;
-            {
-                KernelTimer timer("spread", stream);
-                e = launch_cell(w->p.w, channels, w->p.degree, dim3(blocks, nbatch), stream, ca);
-            }
-            if (e != hipSuccess) {
-                set_error("cell-sorted spread kernel launch failed: %s", hipGetErrorString(e));
-                return EFGP_EHIP;
-            }
-            const int rb = (int)((g.cells + 63) / 64);
-            hipLaunchKernelGGL((reduce_slabs_kernel<false>), dim3(rb, nbatch), dim3(512), 0, stream, (const double*)gacc, 1,
-                               channels, g.cells, (const double*)nullptr, fine);
-            EFGP_HIP_CHECK(hipGetLastError());
-            return transform_fine(plan, g, fine, nbatch, isign, stream, req, scale_out ? *scale_out : nullptr, fine_out);
-        }
+        KernelTimer timer("spread", stream);
+        e = launch_cell(w->p.w, channels, w->p.degree, dim3(blocks, nbatch), stream, ca);
     }
-    // grids beyond LDS: tile-sorted points + LDS tiles (large N), else global atomics (small N)
-    TileGeom tg;
-    const bool use_tiles = !use_lds && plan->npts >= 32768 && std::getenv("EFGP_NO_TILES") == nullptr &&
-                           make_tile_geom(plan, w, channels, (size_t)ctx->max_lds - 4096, &tg);
-    if (use_tiles) {
-        BinSet* bins = nullptr;
-        int rc = get_bins(plan, tg, channels, stream, &bins);
-        if (rc != EFGP_OK) return rc;
-        const size_t acc_bytes = (size_t)nbatch * channels * (size_t)g.cells * sizeof(long long);
-        const size_t known_zero = ctx->slabs_zero_bytes;
-        const void* slabs_before = ctx->buf[SLOT_SLABS];
-        long long* gacc = (long long*)scratch(ctx, SLOT_SLABS, acc_bytes);
-        double2* fine = (double2*)scratch(ctx, SLOT_FINE, (size_t)nbatch * (size_t)g.cells * sizeof(double2));
-        char* misc = scale_slot(ctx, stream);
-        if (!gacc || !fine || !misc) return EFGP_ENOMEM;
-        double* d_scale = (double*)misc;
-        unsigned long long* d_cmax = (unsigned long long*)(misc + 56);
-        if (scale_out) *scale_out = d_scale;
-        // the kernel that converts the accumulator clears what it reads: back-to-back passes need no memset launch
-        if (known_zero < acc_bytes || slabs_before != (const void*)gacc) EFGP_HIP_CHECK(hipMemsetAsync(gacc, 0, acc_bytes, stream));
-        // the global int64 grid sums over ALL points: bound the scale with N instead of points per workgroup
-        const ScaleJob job{floor_bound, mode == STR_REAL_AND_ONES ? 1 : 0, plan->npts, d_scale, 61, max_mult};
-        if (need_max) {
-            const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((nvals + 8191) / 8192, 256));
-            hipLaunchKernelGGL(maxabs_kernel, dim3(blocks), dim3(1024), 0, stream, max_src, nvals, d_cmax,
-                               (unsigned int*)(misc + 48), job);
-        } else {
-            hipLaunchKernelGGL(fixed_scale_kernel, dim3(1), dim3(64), 0, stream, job.floor_bound, job.ones_channel, job.per,
-                               job.scale, job.sum_bits);
-        }
-        EFGP_HIP_CHECK(hipGetLastError());
-        TileSpreadArgs ta;
-        ta.t = tg;
-        ta.xs = bins->xs;
-        ta.order = bins->order;
-        ta.start = bins->start;
-        ta.src = src;
-        ta.npts = plan->npts;
-        // enough chunks to fill the chip, but long enough to amortise the tile flushes
-        int64_t chunk = std::max<int64_t>(4096, (plan->npts + 4 * ctx->num_cu - 1) / (4 * (int64_t)ctx->num_cu));
-        ta.chunk = chunk;
-        ta.coef = w->d_coef;
-        ta.degree = w->p.degree;
-        ta.channels = channels;
-        ta.gacc = gacc;
-        ta.cells = g.cells;
-        ta.scale = d_scale;
-        const size_t tile_lds = (size_t)channels * tg.ext[0] * tg.ext[1] * tg.ext[2] * sizeof(double);
-        dim3 grid((unsigned)((plan->npts + chunk - 1) / chunk), nbatch);
-        hipError_t e;
-        {
-            KernelTimer timer("spread", stream);
-            if (plan->dim == 1) e = launch_tile_d<1>(w->p.w, grid, tile_lds, stream, ta);
-            else if (plan->dim == 2) e = launch_tile_d<2>(w->p.w, grid, tile_lds, stream, ta);
-            else e = launch_tile_d<3>(w->p.w, grid, tile_lds, stream, ta);
-        }
-        if (e != hipSuccess) {
-            set_error("tiled spread kernel launch failed: %s", hipGetErrorString(e));
-            return EFGP_EHIP;
-        }
-        const FftAccSource accsrc{gacc, channels, g.cells, (const double*)d_scale, 1};     // converted (and cleared) by whoever reads it
-        ctx->slabs_zero_bytes = zero_extent_after(acc_bytes, known_zero, slabs_before == (const void*)gacc);
-        return transform_fine(plan, g, fine, nbatch, isign, stream, req, scale_out ? *scale_out : nullptr, fine_out, &accsrc);
+    if (e != hipSuccess) {
+        set_error("cell-sorted spread kernel launch failed: %s", hipGetErrorString(e));
+        return EFGP_EHIP;
     }
+    const int rb = (int)((g.cells + 63) / 64);
+    hipLaunchKernelGGL((reduce_slabs_kernel<false>), dim3(rb, nbatch), dim3(512), 0, stream, (const double*)gacc, 1,
+                       channels, g.cells, (const double*)nullptr, fine);
+    EFGP_HIP_CHECK(hipGetLastError());
+    return transform_fine(plan, g, fine, nbatch, s.isign, stream, s.req, s.scale, s.fine_out);
+}
+
+// grids beyond LDS with many points: tile-sorted points + LDS tiles, added to one global int64 grid
+static int spread_tiled(SpreadCall& s, const TileGeom& tg) {
+    efgp_nufft_s* plan = s.plan;
+    DeviceCtx* ctx = plan->ctx;
+    const WindowSet* w = s.w;
+    const int channels = s.job.channels;
+    hipStream_t stream = s.stream;
+    BinSet* bins = nullptr;
+    int rc = get_bins(plan, tg, channels, stream, &bins);
+    if (rc != EFGP_OK) return rc;
+    Int64Grid a;
+    rc = acquire_int64_grid(s, &a);
+    if (rc != EFGP_OK) return rc;
+    double* d_scale = (double*)a.misc;
+    s.publish_scale(d_scale);
+    // the global int64 grid sums over ALL points: bound the scale with N instead of points per workgroup
+    enqueue_scale(s.job, scale_job(s.job, plan->npts, 61, d_scale), a.misc, stream);
+    EFGP_HIP_CHECK(hipGetLastError());
+    TileSpreadArgs ta;
+    ta.t = tg;
+    ta.xs = bins->xs;
+    ta.order = bins->order;
+    ta.start = bins->start;
+    ta.src = s.job.src;
+    ta.npts = plan->npts;
+    // enough chunks to fill the chip, but long enough to amortise the tile flushes
+    int64_t chunk = std::max<int64_t>(4096, (plan->npts + 4 * ctx->num_cu - 1) / (4 * (int64_t)ctx->num_cu));
+    ta.chunk = chunk;
+    ta.coef = w->d_coef;
+    ta.degree = w->p.degree;
+    ta.channels = channels;
+    ta.gacc = a.gacc;
+    ta.cells = s.g.cells;
+    ta.scale = d_scale;
+    const size_t tile_lds = (size_t)channels * tg.ext[0] * tg.ext[1] * tg.ext[2] * sizeof(double);
+    dim3 grid((unsigned)((plan->npts + chunk - 1) / chunk), s.nbatch);
+    hipError_t e;
+    {
+        KernelTimer timer("spread", stream);
+        e = by_dim(plan->dim, [&](auto D) { return launch_tile_d<decltype(D)::value>(w->p.w, grid, tile_lds, stream, ta); });
+    }
+    if (e != hipSuccess) {
+        set_error("tiled spread kernel launch failed: %s", hipGetErrorString(e));
+        return EFGP_EHIP;
+    }
+    const FftAccSource accsrc{a.gacc, channels, s.g.cells, (const double*)d_scale, 1};     // converted (and cleared) by whoever reads it
+    int64_grid_converted(ctx, a);
+    return transform_fine(plan, s.g, a.fine, s.nbatch, s.isign, stream, s.req, s.scale, s.fine_out, &accsrc);
+}
+
+// fine grids inside LDS: one slab per workgroup, summed by reduce_slabs_kernel; grids beyond LDS with few points: global atomics
+// on one slab.  Also the route of a plan without points (zeroed slab, plain reduction).
+static int spread_lds_or_global(SpreadCall& s, bool use_lds, size_t lds_bytes) {
+    efgp_nufft_s* plan = s.plan;
+    DeviceCtx* ctx = plan->ctx;
+    const WindowSet* w = s.w;
+    const GridGeom& g = s.g;
+    const int channels = s.job.channels, nbatch = s.nbatch, mode = s.job.src.mode;
+    hipStream_t stream = s.stream;
     int nwg = 1;
     if (use_lds) {
         int per_cu = std::max(1, std::min(2, (int)((size_t)ctx->max_lds / std::max<size_t>(lds_bytes, 1))));
@@ -3158,7 +3267,6 @@ static int spread_and_fft(efgp_nufft_s* plan, WindowSet* w, const double* c, int
     char* misc = scale_slot(ctx, stream);
     if (!slabs || !fine || !misc) return EFGP_ENOMEM;
     double* d_scale = (double*)misc;                                  // [0] S0, [1] 1/S0, [2] S1, [3] 1/S1
-    unsigned long long* d_cmax = (unsigned long long*)(misc + 56);
     if (!use_lds) EFGP_HIP_CHECK(hipMemsetAsync(slabs, 0, slab_bytes, stream));
 
     const int64_t per = (plan->npts + nwg - 1) / std::max(nwg, 1);
@@ -3170,27 +3278,19 @@ static int spread_and_fft(efgp_nufft_s* plan, WindowSet* w, const double* c, int
     const bool raw48 = use_pad && (double)per * std::ldexp(1.0, -47) <= 0.01 * plan->tol && std::getenv("EFGP_NO_RAW48") == nullptr &&
                        !strength_is_normal(mode);     // normals: max|c| is 8.6 typical magnitudes, the raw floor would be that much coarser
     if (plan->npts > 0) {      // (both forms: LDS tiles per workgroup, or one global int64 grid)
-        if (scale_out) *scale_out = d_scale;
+        s.publish_scale(d_scale);
         // fixed-point scale from max |c| (device side, no host round trip)
         // raw48: every workgroup's sums stay below 2^46 and reduce_slabs_kernel adds at most 512 of them in int64.
         // Otherwise the bound must hold for the SUM OVER ALL SLABS (reduce_slabs_kernel adds them in plain int64):
         // bounding only one workgroup's share let same-sign strengths (the all-ones channel, clustered points) wrap
         // the total, e.g. 1-D, N = 1e6, tol <= 1e-9: 512 slabs x 2^61 / 1954 points each.
-        const ScaleJob job{floor_bound, mode == STR_REAL_AND_ONES ? 1 : 0, raw48 ? per : plan->npts, d_scale, raw48 ? 46 : 61, max_mult};
-        if (need_max) {
-            const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((nvals + 8191) / 8192, 256));
-            hipLaunchKernelGGL(maxabs_kernel, dim3(blocks), dim3(1024), 0, stream, max_src, nvals, d_cmax,
-                               (unsigned int*)(misc + 48), job);
-        } else {
-            hipLaunchKernelGGL(fixed_scale_kernel, dim3(1), dim3(64), 0, stream, job.floor_bound, job.ones_channel, job.per,
-                               job.scale, job.sum_bits);
-        }
+        enqueue_scale(s.job, scale_job(s.job, raw48 ? per : plan->npts, raw48 ? 46 : 61, d_scale), misc, stream);
         EFGP_HIP_CHECK(hipGetLastError());
     }
 
     SpreadArgs a;
     a.x = plan->x;
-    a.src = src;
+    a.src = s.job.src;
     a.npts = plan->npts;
     a.g = g;
     a.coef = w->d_coef;
@@ -3202,44 +3302,19 @@ static int spread_and_fft(efgp_nufft_s* plan, WindowSet* w, const double* c, int
     a.order = nullptr;
     // per-plan bank-balanced order (d >= 2, enough points for the one-off pass to pay)
     if (use_pad && plan->dim >= 2 && plan->npts >= (int64_t)kOrderWindow * 64 && std::getenv("EFGP_NO_CLASS_ORDER") == nullptr) {
-        ClassOrder* co = nullptr;
-        for (ClassOrder* o : plan->orders)
-            if (o->W == w->p.w && o->nwg == nwg && o->nf[0] == g.nf[0] && o->nf[1] == g.nf[1] && o->nf[2] == g.nf[2]) co = o;
-        if (!co) {
-            co = new ClassOrder();
-            for (int q = 0; q < 3; ++q) co->nf[q] = g.nf[q];
-            co->W = w->p.w;
-            co->nwg = nwg;
-            co->bytes = (size_t)plan->npts * sizeof(int);
-            co->order = (int*)pool_alloc(ctx, co->bytes);
-            if (!co->order) {
-                delete co;
-                return EFGP_ENOMEM;
-            }
-            KernelTimer order_timer("order", stream);
-            if (plan->dim == 2)
-                hipLaunchKernelGGL((class_order_kernel<2, 16>), dim3(nwg), dim3(kSpreadThreads), 0, stream, g, w->p.w, plan->x, plan->npts, per,
-                                   co->order);
-            else
-                hipLaunchKernelGGL((class_order_kernel<3, 16>), dim3(nwg), dim3(kSpreadThreads), 0, stream, g, w->p.w, plan->x, plan->npts, per,
-                                   co->order);
-            EFGP_HIP_CHECK(hipGetLastError());
-            plan->orders.push_back(co);
-        }
-        a.order = co->order;
+        int rc = get_class_order(plan, w, g, nwg, per, stream, &a.order);
+        if (rc != EFGP_OK) return rc;
     }
     dim3 grid(nwg, nbatch);
     hipError_t e = hipSuccess;
     if (plan->npts > 0 && use_pad) {
         KernelTimer timer("spread", stream);
-        if (plan->dim == 1) e = launch_spread_pad_d<1>(w->p.w, raw48, grid, pad_bytes, stream, a);
-        else if (plan->dim == 2) e = launch_spread_pad_d<2>(w->p.w, raw48, grid, pad_bytes, stream, a);
-        else e = launch_spread_pad_d<3>(w->p.w, raw48, grid, pad_bytes, stream, a);
+        e = by_dim(plan->dim, [&](auto D) { return launch_spread_pad_d<decltype(D)::value>(w->p.w, raw48, grid, pad_bytes, stream, a); });
     } else if (plan->npts > 0) {
         KernelTimer timer("spread", stream);
-        if (plan->dim == 1) e = launch_spread_d<1>(w->p.w, use_lds, grid, use_lds ? lds_bytes : 0, stream, a);
-        else if (plan->dim == 2) e = launch_spread_d<2>(w->p.w, use_lds, grid, use_lds ? lds_bytes : 0, stream, a);
-        else e = launch_spread_d<3>(w->p.w, use_lds, grid, use_lds ? lds_bytes : 0, stream, a);
+        e = by_dim(plan->dim, [&](auto D) {
+            return launch_spread_d<decltype(D)::value>(w->p.w, use_lds, grid, use_lds ? lds_bytes : 0, stream, a);
+        });
     } else {
         EFGP_HIP_CHECK(hipMemsetAsync(slabs, 0, slab_bytes, stream));
     }
@@ -3247,22 +3322,44 @@ static int spread_and_fft(efgp_nufft_s* plan, WindowSet* w, const double* c, int
         set_error("spread kernel launch failed: %s", hipGetErrorString(e));
         return EFGP_EHIP;
     }
-    {
-        const int blocks = (int)((g.cells + 63) / 64);
-        if (plan->npts > 0)
-            hipLaunchKernelGGL((reduce_slabs_kernel<true>), dim3(blocks, nbatch), dim3(nslab >= 64 ? 1024 : 512), 0, stream,
-                               slabs, nslab, channels, g.cells, (const double*)d_scale, fine);
-        else
-            hipLaunchKernelGGL((reduce_slabs_kernel<false>), dim3(blocks, nbatch), dim3(512), 0, stream, slabs, nslab,
-                               channels, g.cells, (const double*)d_scale, fine);
-        EFGP_HIP_CHECK(hipGetLastError());
-    }
-    return transform_fine(plan, g, fine, nbatch, isign, stream, req, scale_out ? *scale_out : nullptr, fine_out);
+    const int blocks = (int)((g.cells + 63) / 64);
+    if (plan->npts > 0)
+        hipLaunchKernelGGL((reduce_slabs_kernel<true>), dim3(blocks, nbatch), dim3(nslab >= 64 ? 1024 : 512), 0, stream,
+                           slabs, nslab, channels, g.cells, (const double*)d_scale, fine);
+    else
+        hipLaunchKernelGGL((reduce_slabs_kernel<false>), dim3(blocks, nbatch), dim3(512), 0, stream, slabs, nslab,
+                           channels, g.cells, (const double*)d_scale, fine);
+    EFGP_HIP_CHECK(hipGetLastError());
+    return transform_fine(plan, g, fine, nbatch, s.isign, stream, s.req, s.scale, s.fine_out);
 }
 
-static int run_deconvolve(efgp_nufft_s* plan, WindowSet* w, const double2* fine, const int64_t* nm, int modeord,
-                          int part, int nbatch, void* out, hipStream_t stream, int rows_limit = 1 << 30, const G2MRequest* req = nullptr) {
-    ModeGeom m = make_modes(plan, w, nm, modeord);
+// spread + reduce + FFT; leaves the transformed fine grids in SLOT_FINE (*fine_out), or the requested modes in the request's
+// outputs (req->done).  The routes are tried in this order; the first whose predicate holds runs the pass.
+static int spread_and_fft(efgp_nufft_s* plan, WindowSet* w, const SpreadJob& job, int nbatch, int isign, hipStream_t stream,
+                          double2** fine_out, G2MRequest* req, const double** scale_out = nullptr) {
+    SpreadCall s{plan, w, make_geom(plan, w), job, nbatch, isign, stream, req, fine_out, scale_out != nullptr};
+    const size_t lds_bytes = (size_t)job.channels * (size_t)s.g.cells * sizeof(double);
+    const bool use_lds = lds_bytes <= (size_t)plan->ctx->max_lds && plan->npts > 0;
+    int band_cells = 8;
+    TileGeom tg;
+    int rc;
+    if (SortedLevel* lvl = pick_level(plan, w, s.g, stream, &band_cells)) {
+        rc = spread_on_layout(s, lvl, band_cells);
+    } else if (cell_sort_wanted(s, &tg)) {
+        rc = spread_cell_sorted(s, tg);
+    } else if (!use_lds && plan->npts >= 32768 && std::getenv("EFGP_NO_TILES") == nullptr &&
+               make_tile_geom(plan, w, job.channels, (size_t)plan->ctx->max_lds - 4096, &tg)) {
+        rc = spread_tiled(s, tg);         // else global atomics (small N)
+    } else {
+        rc = spread_lds_or_global(s, use_lds, lds_bytes);
+    }
+    if (scale_out) *scale_out = s.scale;
+    return rc;
+}
+
+// the modes `m` out of the transformed fine grid (or out of its cropped spectrum, when the request says the transform pruned it)
+static int deconvolve(const WindowSet* w, const double2* fine, ModeGeom m, int part, int nbatch, void* out, hipStream_t stream,
+                      int rows_limit = 1 << 30, const G2MRequest* req = nullptr) {
     int64_t cells = 1;
     for (int a = 0; a < 3; ++a) cells *= w->nf[a];
     apply_crop(req, m, cells);
@@ -3272,6 +3369,17 @@ static int run_deconvolve(efgp_nufft_s* plan, WindowSet* w, const double2* fine,
                        (double2*)out, rows_limit);
     EFGP_HIP_CHECK(hipGetLastError());
     return EFGP_OK;
+}
+static int run_deconvolve(efgp_nufft_s* plan, WindowSet* w, const double2* fine, const int64_t* nm, int modeord,
+                          int part, int nbatch, void* out, hipStream_t stream, int rows_limit = 1 << 30, const G2MRequest* req = nullptr) {
+    return deconvolve(w, fine, make_modes(plan, w, nm, modeord), part, nbatch, out, stream, rows_limit, req);
+}
+
+// The window's correction factors are built for one mode box; a smaller box centred in it indexes them with an offset.
+static ModeGeom make_modes_in_box(const efgp_nufft_s* plan, const WindowSet* w, const int64_t* nm, const int64_t* box) {
+    ModeGeom m = make_modes(plan, w, nm, 0);
+    for (int a = 0; a < plan->dim; ++a) m.fac[a] = w->d_fac[a] + (box[a] / 2 - nm[a] / 2);
+    return m;
 }
 
 }  // namespace efgp
@@ -3341,8 +3449,9 @@ static int type1_real_rows(efgp_nufft_s* plan, WindowSet* w, const double* c, Ro
         req.rows_limit = nbatch;
         req.ma = make_modes(plan, w, n_modes, modeord);
         req.out_a = out;
-        int rc = spread_and_fft(plan, w, c, rows == ROWS_NORMAL ? STR_NORMAL_PAIR : (rng ? STR_RNG_PAIR : STR_REAL_PAIR), npair, isign, stream, &fine, seed, index_offset, nullptr,
-                                &req, point_scale);
+        const int mode = rows == ROWS_NORMAL ? STR_NORMAL_PAIR : (rng ? STR_RNG_PAIR : STR_REAL_PAIR);
+        int rc = spread_and_fft(plan, w, make_spread_job(mode, c, point_scale, npair, plan->npts, seed, index_offset), npair, isign, stream,
+                                &fine, &req);
         if (rc != EFGP_OK) return rc;
         // for isign = +1 the roles of k and -k swap in the Hermitian split; conjugating H handles both signs:
         // the split below assumes the forward (isign = -1) transform, which is what the reference uses for type 1
@@ -3351,27 +3460,27 @@ static int type1_real_rows(efgp_nufft_s* plan, WindowSet* w, const double* c, Ro
     }
     if ((nbatch & 1) && !pad_odd) {
         const int last = nbatch - 1;
-        int rc;
+        // the lone row as a one-grid pass: from memory it is row `last` of c.  Generated rows are keyed by the fine-grid index (0
+        // here) at the point index, in wrapping 64-bit arithmetic: Rademacher row `last` is row 0 at the index shifted by last *
+        // kRowStride (efgp_rademacher); normal row `last` (even) is element 0 of pair last / 2, i.e. pair 0 shifted by (last / 2) strides
+        int mode = STR_REAL;
+        const double* row = c ? c + (int64_t)last * plan->npts : nullptr;
+        unsigned long long row_seed = 0, shift = 0;
+        if (rng) {
+            mode = rows == ROWS_NORMAL ? STR_NORMAL : STR_RNG;
+            row = nullptr;
+            row_seed = seed;
+            shift = (unsigned long long)index_offset + (unsigned long long)(rows == ROWS_NORMAL ? last >> 1 : last) * kRademacherRowStride;
+        }
+        void* row_out = (double2*)out + (int64_t)last * total;
         G2MRequest req;
         req.part = 0;
         req.ma = make_modes(plan, w, n_modes, modeord);
-        req.out_a = (double2*)out + (int64_t)last * total;
-        if (rows == ROWS_NORMAL) {
-            // row `last` (even) is element 0 of pair last / 2: pair 0 at the point index shifted by (last / 2) * kRowStride
-            rc = spread_and_fft(plan, w, nullptr, STR_NORMAL, 1, isign, stream, &fine, seed,
-                                (int64_t)((unsigned long long)index_offset + (unsigned long long)(last >> 1) * kRademacherRowStride), nullptr,
-                                &req, point_scale);
-        } else if (rng) {
-            // STR_RNG takes the fine-grid index (0 here) as the row: row `last` of the same seed is row 0 at the point index shifted
-            // by last * kRowStride (efgp_rademacher hashes row * kRowStride + index in wrapping 64-bit arithmetic)
-            rc = spread_and_fft(plan, w, nullptr, STR_RNG, 1, isign, stream, &fine, seed,
-                                (int64_t)((unsigned long long)index_offset + (unsigned long long)last * kRademacherRowStride), nullptr,
-                                &req);
-        } else {
-            rc = spread_and_fft(plan, w, c + (int64_t)last * plan->npts, STR_REAL, 1, isign, stream, &fine, 0, 0, nullptr, &req);
-        }
+        req.out_a = row_out;
+        int rc = spread_and_fft(plan, w, make_spread_job(mode, row, point_scale, 1, plan->npts, row_seed, (int64_t)shift), 1, isign, stream,
+                                &fine, &req);
         if (rc != EFGP_OK) return rc;
-        if (!req.done) rc = run_deconvolve(plan, w, fine, n_modes, modeord, 0, 1, (double2*)out + (int64_t)last * total, stream, 1 << 30, &req);
+        if (!req.done) rc = run_deconvolve(plan, w, fine, n_modes, modeord, 0, 1, row_out, stream, 1 << 30, &req);
         if (rc != EFGP_OK) return rc;
     }
     return EFGP_OK;
@@ -3396,17 +3505,21 @@ int efgp_nufft_type1(efgp_nufft_t* plan, const void* c, int c_is_complex, int nb
     req.part = 0;
     req.ma = make_modes(plan, w, n_modes, modeord);
     req.out_a = out;
-    rc = spread_and_fft(plan, w, (const double*)c, c_is_complex ? STR_COMPLEX : STR_REAL, nbatch, isign, stream, &fine, 0, 0, nullptr, &req);
+    const SpreadJob job = make_spread_job(c_is_complex ? STR_COMPLEX : STR_REAL, (const double*)c, nullptr, nbatch, plan->npts);
+    rc = spread_and_fft(plan, w, job, nbatch, isign, stream, &fine, &req);
     if (rc != EFGP_OK) return rc;
     if (req.done) return EFGP_OK;
     return run_deconvolve(plan, w, fine, n_modes, modeord, 0, nbatch, out, stream, 1 << 30, &req);
 }
 
-int efgp_nufft_type1_rademacher(efgp_nufft_t* plan, uint64_t seed, int64_t index_offset, int nbatch,
-                                const int64_t* n_modes, int modeord, void* out, void* stream_) {
-    EFGP_REQUIRE(plan && n_modes && out, "efgp_nufft_type1_rademacher: null argument");
-    EFGP_REQUIRE(nbatch >= 1, "efgp_nufft_type1_rademacher: nbatch must be >= 1");
-    for (int a = 0; a < plan->dim; ++a) EFGP_REQUIRE(n_modes[a] >= 1, "efgp_nufft_type1_rademacher: n_modes[%d] < 1", a);
+// The three entries whose rows are generated in the spread kernels; `entry` is the exported name, for the messages.
+// A plan without points gives zeros without running a pass.
+static int type1_generated_rows(const char* entry, efgp_nufft_t* plan, RowSource rows, uint64_t seed, int64_t index_offset, int nbatch,
+                                bool scaled, const double* point_scale, const int64_t* n_modes, int modeord, void* out, void* stream_) {
+    EFGP_REQUIRE(plan && n_modes && out, "%s: null argument", entry);
+    EFGP_REQUIRE(nbatch >= 1, "%s: nbatch must be >= 1", entry);
+    for (int a = 0; a < plan->dim; ++a) EFGP_REQUIRE(n_modes[a] >= 1, "%s: n_modes[%d] < 1", entry, a);
+    EFGP_REQUIRE(!scaled || plan->npts == 0 || point_scale, "%s: null point_scale", entry);
     hipStream_t stream = (hipStream_t)stream_;
     DeviceGuard guard(plan->device, (hipStream_t)stream_);
     WindowSet* w = nullptr;
@@ -3418,50 +3531,27 @@ int efgp_nufft_type1_rademacher(efgp_nufft_t* plan, uint64_t seed, int64_t index
         EFGP_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)nbatch * total * sizeof(double2), stream));
         return EFGP_OK;
     }
-    return type1_real_rows(plan, w, nullptr, ROWS_RADEMACHER, (unsigned long long)seed, index_offset, nbatch, n_modes, -1, modeord, out,
-                           stream);
+    return type1_real_rows(plan, w, nullptr, rows, (unsigned long long)seed, index_offset, nbatch, n_modes, -1, modeord, out, stream,
+                           point_scale);
+}
+
+int efgp_nufft_type1_rademacher(efgp_nufft_t* plan, uint64_t seed, int64_t index_offset, int nbatch,
+                                const int64_t* n_modes, int modeord, void* out, void* stream_) {
+    return type1_generated_rows("efgp_nufft_type1_rademacher", plan, ROWS_RADEMACHER, seed, index_offset, nbatch, false, nullptr, n_modes,
+                                modeord, out, stream_);
 }
 
 int efgp_nufft_type1_normal(efgp_nufft_t* plan, uint64_t seed, int64_t index_offset, int nbatch,
                             const int64_t* n_modes, int modeord, void* out, void* stream_) {
-    EFGP_REQUIRE(plan && n_modes && out, "efgp_nufft_type1_normal: null argument");
-    EFGP_REQUIRE(nbatch >= 1, "efgp_nufft_type1_normal: nbatch must be >= 1");
-    for (int a = 0; a < plan->dim; ++a) EFGP_REQUIRE(n_modes[a] >= 1, "efgp_nufft_type1_normal: n_modes[%d] < 1", a);
-    hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard guard(plan->device, (hipStream_t)stream_);
-    WindowSet* w = nullptr;
-    int rc = get_window(plan, n_modes, stream, &w);
-    if (rc != EFGP_OK) return rc;
-    if (plan->npts == 0) {
-        int64_t total = 1;
-        for (int a = 0; a < plan->dim; ++a) total *= n_modes[a];
-        EFGP_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)nbatch * total * sizeof(double2), stream));
-        return EFGP_OK;
-    }
-    return type1_real_rows(plan, w, nullptr, ROWS_NORMAL, (unsigned long long)seed, index_offset, nbatch, n_modes, -1, modeord, out,
-                           stream);
+    return type1_generated_rows("efgp_nufft_type1_normal", plan, ROWS_NORMAL, seed, index_offset, nbatch, false, nullptr, n_modes, modeord,
+                                out, stream_);
 }
 
+// an all-zero scale: max = 0 sizes the accumulators as for |c| <= 1, every contribution is an exact zero
 int efgp_nufft_type1_normal_scaled(efgp_nufft_t* plan, uint64_t seed, int64_t index_offset, int nbatch, const double* point_scale,
                                    const int64_t* n_modes, int modeord, void* out, void* stream_) {
-    EFGP_REQUIRE(plan && n_modes && out, "efgp_nufft_type1_normal_scaled: null argument");
-    EFGP_REQUIRE(nbatch >= 1, "efgp_nufft_type1_normal_scaled: nbatch must be >= 1");
-    for (int a = 0; a < plan->dim; ++a) EFGP_REQUIRE(n_modes[a] >= 1, "efgp_nufft_type1_normal_scaled: n_modes[%d] < 1", a);
-    EFGP_REQUIRE(plan->npts == 0 || point_scale, "efgp_nufft_type1_normal_scaled: null point_scale");
-    hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard guard(plan->device, (hipStream_t)stream_);
-    WindowSet* w = nullptr;
-    int rc = get_window(plan, n_modes, stream, &w);
-    if (rc != EFGP_OK) return rc;
-    if (plan->npts == 0) {
-        int64_t total = 1;
-        for (int a = 0; a < plan->dim; ++a) total *= n_modes[a];
-        EFGP_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)nbatch * total * sizeof(double2), stream));
-        return EFGP_OK;
-    }
-    // an all-zero scale: max = 0 sizes the accumulators as for |c| <= 1, every contribution is an exact zero
-    return type1_real_rows(plan, w, nullptr, ROWS_NORMAL, (unsigned long long)seed, index_offset, nbatch, n_modes, -1, modeord, out,
-                           stream, point_scale);
+    return type1_generated_rows("efgp_nufft_type1_normal_scaled", plan, ROWS_NORMAL, seed, index_offset, nbatch, true, point_scale, n_modes,
+                                modeord, out, stream_);
 }
 
 int efgp_normal_fill(int device, uint64_t seed, int64_t index_offset, int nbatch, int64_t npts, double* out, void* stream_) {
@@ -3516,57 +3606,36 @@ int efgp_nufft_type1_pair(efgp_nufft_t* plan, const double* y, const int64_t* n_
     WindowSet* w = nullptr;
     int rc = get_window(plan, box, stream, &w);
     if (rc != EFGP_OK) return rc;
-    int mode = (out_y && out_ones) ? STR_REAL_AND_ONES : (out_y ? STR_REAL : STR_ONES);
+    const bool both = out_y && out_ones;
     double2* fine = nullptr;
     const double* pair_scale = nullptr;
     G2MRequest req;
-    G2MRequest* reqp = nullptr;
-    if (mode == STR_REAL_AND_ONES) {
+    if (both) {
         req.part = 4;
-        req.ma = make_modes(plan, w, n_modes_y, 0);
-        req.mb = make_modes(plan, w, n_modes_one, 0);
-        for (int a = 0; a < plan->dim; ++a) {
-            req.ma.fac[a] = w->d_fac[a] + (box[a] / 2 - n_modes_y[a] / 2);
-            req.mb.fac[a] = w->d_fac[a] + (box[a] / 2 - n_modes_one[a] / 2);
-        }
+        req.ma = make_modes_in_box(plan, w, n_modes_y, box);
+        req.mb = make_modes_in_box(plan, w, n_modes_one, box);
         req.out_a = out_y;
         req.out_b = out_ones;
-        reqp = &req;
     }
-    rc = spread_and_fft(plan, w, y, mode, 1, -1, stream, &fine, 0, 0, &pair_scale, reqp);
+    const SpreadJob job = make_spread_job(both ? STR_REAL_AND_ONES : (out_y ? STR_REAL : STR_ONES), y, nullptr, 1, plan->npts);
+    rc = spread_and_fft(plan, w, job, 1, -1, stream, &fine, both ? &req : nullptr, &pair_scale);
     if (rc != EFGP_OK) return rc;
     if (req.done) return EFGP_OK;
-    // correction factors were built for `box`; a smaller centred box indexes them with an offset
-    auto sub = [&](const int64_t* nm, int part, void* out) -> int {
-        ModeGeom m = make_modes(plan, w, nm, 0);
-        for (int a = 0; a < plan->dim; ++a) m.fac[a] = w->d_fac[a] + (box[a] / 2 - nm[a] / 2);
-        int64_t cells = 1;
-        for (int a = 0; a < 3; ++a) cells *= w->nf[a];
-        int threads = 256;
-        int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((m.total + threads - 1) / threads, 2048));
-        hipLaunchKernelGGL(deconvolve_kernel, dim3(blocks, 1), dim3(threads), 0, stream, (const double2*)fine, cells, m,
-                           part, (double2*)out, 1 << 30);
-        EFGP_HIP_CHECK(hipGetLastError());
-        return EFGP_OK;
-    };
-    if (mode == STR_REAL_AND_ONES) {
-        ModeGeom ma = make_modes(plan, w, n_modes_y, 0), mb = make_modes(plan, w, n_modes_one, 0);
-        for (int a = 0; a < plan->dim; ++a) {
-            ma.fac[a] = w->d_fac[a] + (box[a] / 2 - n_modes_y[a] / 2);
-            mb.fac[a] = w->d_fac[a] + (box[a] / 2 - n_modes_one[a] / 2);
-        }
-        int64_t cells = 1;
-        for (int a = 0; a < 3; ++a) cells *= w->nf[a];
-        apply_crop(reqp, ma, cells);
-        apply_crop(reqp, mb, cells);
-        const int64_t most = std::max(ma.total, mb.total);
-        const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((most + 255) / 256, 2048));
-        hipLaunchKernelGGL(deconvolve_pair_kernel, dim3(blocks, 2), dim3(256), 0, stream, (const double2*)fine, cells, ma,
-                           (double2*)out_y, mb, (double2*)out_ones, pair_scale);
-        EFGP_HIP_CHECK(hipGetLastError());
-        return EFGP_OK;
+    if (!both) {
+        const int64_t* nm = out_y ? n_modes_y : n_modes_one;
+        return deconvolve(w, fine, make_modes_in_box(plan, w, nm, box), 0, 1, out_y ? out_y : out_ones, stream);
     }
-    return out_y ? sub(n_modes_y, 0, out_y) : sub(n_modes_one, 0, out_ones);
+    ModeGeom ma = req.ma, mb = req.mb;
+    int64_t cells = 1;
+    for (int a = 0; a < 3; ++a) cells *= w->nf[a];
+    apply_crop(&req, ma, cells);
+    apply_crop(&req, mb, cells);
+    const int64_t most = std::max(ma.total, mb.total);
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((most + 255) / 256, 2048));
+    hipLaunchKernelGGL(deconvolve_pair_kernel, dim3(blocks, 2), dim3(256), 0, stream, (const double2*)fine, cells, ma,
+                       (double2*)out_y, mb, (double2*)out_ones, pair_scale);
+    EFGP_HIP_CHECK(hipGetLastError());
+    return EFGP_OK;
 }
 
 static int type2_impl(efgp_nufft_t* plan, const void* f, const void* mode_scale, int nbatch, const int64_t* n_modes, int isign,
@@ -3583,118 +3652,133 @@ int efgp_nufft_type2_scaled(efgp_nufft_t* plan, const void* f, const void* mode_
     return type2_impl(plan, f, mode_scale, nbatch, n_modes, isign, modeord, out, real_only, stream_);
 }
 
-static int type2_impl(efgp_nufft_t* plan, const void* f, const void* mode_scale, int nbatch, const int64_t* n_modes, int isign,
-                      int modeord, void* out, int real_only, void* stream_) {
+static int type2_check(const efgp_nufft_t* plan, const void* f, int nbatch, const int64_t* n_modes, int isign, const void* out) {
     EFGP_REQUIRE(plan && f && n_modes, "efgp_nufft_type2: null argument");
     EFGP_REQUIRE(nbatch >= 1, "efgp_nufft_type2: nbatch must be >= 1");
     EFGP_REQUIRE(plan->npts == 0 || out, "efgp_nufft_type2: null out");
     for (int a = 0; a < plan->dim; ++a) EFGP_REQUIRE(n_modes[a] >= 1, "efgp_nufft_type2: n_modes[%d] < 1", a);
     EFGP_REQUIRE(isign == 1 || isign == -1, "efgp_nufft_type2: isign must be +-1");
-    if (plan->npts == 0) return EFGP_OK;
-    hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard guard(plan->device, (hipStream_t)stream_);
-    DeviceCtx* ctx = plan->ctx;
-    WindowSet* w = nullptr;
-    int rc = get_window(plan, n_modes, stream, &w);
-    if (rc != EFGP_OK) return rc;
-    const GridGeom g = make_geom(plan, w);
-    // small 2-D real-output transforms: the real fine grid by ONE dense-DFT launch instead of precorrect + two rocFFT kernels
-    const bool direct_grid = real_only && nbatch == 1 && plan->dim == 2 &&
-                             modes_to_grid_real_eligible((int)g.nf[0], (int)g.nf[1], (int)n_modes[0], (int)n_modes[1]);
-    const bool cplx = !real_only;
-    size_t lds_bytes = (size_t)g.cells * (cplx ? sizeof(double2) : sizeof(double));
-    // real outputs: halo-padded LDS copy when it fits (no wrap arithmetic in the gather)
+    return EFGP_OK;
+}
+
+// How the gather will hold the fine grid in LDS.  Decided before the grid is filled: the grid kernel may write the gather's image.
+struct GatherRoute {
+    bool cplx;
+    bool direct_grid;     // small 2-D real-output transforms: the real fine grid by ONE dense-DFT launch instead of precorrect + two FFT kernels
+    bool use_halo;        // real outputs: halo-padded LDS copy when it fits (no wrap arithmetic in the gather)
+    bool use_pair;        // 2-D real outputs whose two parity copies fit LDS: aligned 16-byte reads, no processing order
+    bool use_image;       // ... and the grid kernel writes those two copies itself, laid out as the gather holds them: the fill is a flat copy
+    size_t lds_bytes, pair_bytes;
+};
+static GatherRoute pick_gather(const efgp_nufft_s* plan, const WindowSet* w, const GridGeom& g, int nbatch, const int64_t* n_modes,
+                               int real_only) {
+    const size_t max_lds = (size_t)plan->ctx->max_lds;
+    GatherRoute r;
+    r.direct_grid = real_only && nbatch == 1 && plan->dim == 2 &&
+                    modes_to_grid_real_eligible((int)g.nf[0], (int)g.nf[1], (int)n_modes[0], (int)n_modes[1]);
+    r.cplx = !real_only;
+    r.lds_bytes = (size_t)g.cells * (r.cplx ? sizeof(double2) : sizeof(double));
     size_t halo_cells = 1;
     for (int a_ = 0; a_ < plan->dim; ++a_) halo_cells *= (size_t)(g.nf[a_] + w->p.w - 1);
-    const bool use_halo = !cplx && halo_cells * sizeof(double) <= (size_t)ctx->max_lds && std::getenv("EFGP_NO_HALO") == nullptr;
-    if (use_halo) lds_bytes = halo_cells * sizeof(double);
-    // 2-D real outputs whose two parity copies fit LDS: aligned 16-byte reads, no processing order
-    const size_t pair_bytes = plan->dim == 2 ? interp_pair_lds_bytes((int)g.nf[0], (int)g.nf[1], w->p.w) : 0;
-    const bool use_pair = use_halo && plan->dim == 2 && pair_bytes <= (size_t)ctx->max_lds && std::getenv("EFGP_NO_PAIR_GATHER") == nullptr;
-    if (use_pair) lds_bytes = pair_bytes;
-    // ... and the grid kernel writes those two copies itself, laid out as the gather holds them: the gather's fill is a flat copy
-    const bool use_image = direct_grid && use_pair && pair_bytes <= (size_t)kPairFillTrips * kInterpThreads * sizeof(double2) &&
-                           std::getenv("EFGP_NO_GATHER_IMAGE") == nullptr;
-    const size_t fine_bytes = (size_t)nbatch * (size_t)g.cells * sizeof(double2);
-    double2* fine = (double2*)scratch(ctx, SLOT_FINE, use_image ? std::max(fine_bytes, pair_bytes) : fine_bytes);
-    if (!fine) return EFGP_ENOMEM;
-    ModeGeom m = make_modes(plan, w, n_modes, modeord);
-    if (direct_grid) {
+    r.use_halo = !r.cplx && halo_cells * sizeof(double) <= max_lds && std::getenv("EFGP_NO_HALO") == nullptr;
+    if (r.use_halo) r.lds_bytes = halo_cells * sizeof(double);
+    r.pair_bytes = plan->dim == 2 ? interp_pair_lds_bytes((int)g.nf[0], (int)g.nf[1], w->p.w) : 0;
+    r.use_pair = r.use_halo && plan->dim == 2 && r.pair_bytes <= max_lds && std::getenv("EFGP_NO_PAIR_GATHER") == nullptr;
+    if (r.use_pair) r.lds_bytes = r.pair_bytes;
+    r.use_image = r.direct_grid && r.use_pair && r.pair_bytes <= (size_t)kPairFillTrips * kInterpThreads * sizeof(double2) &&
+                  std::getenv("EFGP_NO_GATHER_IMAGE") == nullptr;
+    return r;
+}
+
+// the fine grid from the modes: one dense-DFT launch (with or without the gather's image), else corrected modes + the in-house
+// pruned transform, else corrected modes on the full grid + the FFT in place
+static int modes_to_fine(efgp_nufft_s* plan, const WindowSet* w, const GridGeom& g, const GatherRoute& r, const void* f,
+                         const void* mode_scale, int nbatch, const int64_t* n_modes, int isign, int modeord, int real_only, double2* fine,
+                         hipStream_t stream) {
+    DeviceCtx* ctx = plan->ctx;
+    if (r.direct_grid) {
         const int img_p0 = interp_pair_rows((int)g.nf[0], w->p.w), img_p1 = interp_pair_pitch((int)g.nf[1], w->p.w);
         std::optional<KernelTimer> grid_timer;          // names the route for whoever has to tell them apart (tests)
-        if (use_image) grid_timer.emplace("grid_image", stream);
-        rc = modes_to_grid_real_launch(ctx, (const double2*)f, (const double2*)mode_scale, (int)n_modes[0], (int)n_modes[1], modeord, isign,
-                                       w->d_fac[0], w->d_fac[1], (int)g.nf[0], (int)g.nf[1], fine, use_image ? (double*)fine : nullptr,
-                                       img_p0, img_p1, stream);
-        if (rc != EFGP_OK) return rc;
-    } else {
-        int threads = 256;
-        // In-house pruned transform: the corrected modes go to a compact array (the 2 (nm/2) + 1 lowest bins per axis), the passes
-        // expand it axis by axis, slowest first -- only the last, contiguous pass writes the full grid (line_fft.hip).
-        int64_t nc[3] = {1, 1, 1}, ccells = 1, region = nbatch;
-        bool smaller = false;
-        for (int a = 0; a < plan->dim; ++a) {
-            nc[a] = std::min<int64_t>(2 * (n_modes[a] / 2) + 1, g.nf[a]);
-            smaller = smaller || nc[a] < g.nf[a];
-            ccells *= nc[a];
-            region *= a == plan->dim - 1 ? nc[a] : g.nf[a];
-        }
-        if (smaller && own_fft_supported(plan->dim, g.nf) && std::getenv("EFGP_NO_PRUNED_FFT") == nullptr) {
-            double2* work = (double2*)scratch(ctx, SLOT_FFT_WORK, (size_t)2 * (size_t)region * sizeof(double2));
-            if (!work) return EFGP_ENOMEM;
-            ModeGeom mc = m;
-            for (int a = 0; a < plan->dim; ++a) mc.nf[a] = nc[a];
-            int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((ccells + threads - 1) / threads, 2048));
-            hipLaunchKernelGGL(precorrect_kernel, dim3(blocks, nbatch), dim3(threads), 0, stream, (const double2*)f,
-                               (const double2*)mode_scale, mc, real_only ? 1 : 0, ccells, work);
-            EFGP_HIP_CHECK(hipGetLastError());
-            rc = own_fft_pruned_backward(ctx, plan->dim, nc, g.nf, nbatch, work, fine, work, region, isign < 0, stream);
-            if (rc != EFGP_OK) return rc;
-        } else {
-            int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((g.cells + threads - 1) / threads, 2048));
-            hipLaunchKernelGGL(precorrect_kernel, dim3(blocks, nbatch), dim3(threads), 0, stream, (const double2*)f,
-                               (const double2*)mode_scale, m, real_only ? 1 : 0, g.cells, fine);
-            EFGP_HIP_CHECK(hipGetLastError());
-            rc = fft_c2c(ctx, plan->dim, g.nf, nbatch, fine, isign < 0, stream);
-            if (rc != EFGP_OK) return rc;
-        }
+        if (r.use_image) grid_timer.emplace("grid_image", stream);
+        return modes_to_grid_real_launch(ctx, (const double2*)f, (const double2*)mode_scale, (int)n_modes[0], (int)n_modes[1], modeord, isign,
+                                         w->d_fac[0], w->d_fac[1], (int)g.nf[0], (int)g.nf[1], fine, r.use_image ? (double*)fine : nullptr,
+                                         img_p0, img_p1, stream);
     }
+    const ModeGeom m = make_modes(plan, w, n_modes, modeord);
+    int threads = 256;
+    // In-house pruned transform: the corrected modes go to a compact array (the 2 (nm/2) + 1 lowest bins per axis), the passes
+    // expand it axis by axis, slowest first -- only the last, contiguous pass writes the full grid (line_fft.hip).
+    int64_t nc[3] = {1, 1, 1}, ccells = 1, region = nbatch;
+    bool smaller = false;
+    for (int a = 0; a < plan->dim; ++a) {
+        nc[a] = std::min<int64_t>(2 * (n_modes[a] / 2) + 1, g.nf[a]);
+        smaller = smaller || nc[a] < g.nf[a];
+        ccells *= nc[a];
+        region *= a == plan->dim - 1 ? nc[a] : g.nf[a];
+    }
+    if (smaller && own_fft_supported(plan->dim, g.nf) && std::getenv("EFGP_NO_PRUNED_FFT") == nullptr) {
+        double2* work = (double2*)scratch(ctx, SLOT_FFT_WORK, (size_t)2 * (size_t)region * sizeof(double2));
+        if (!work) return EFGP_ENOMEM;
+        ModeGeom mc = m;
+        for (int a = 0; a < plan->dim; ++a) mc.nf[a] = nc[a];
+        int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((ccells + threads - 1) / threads, 2048));
+        hipLaunchKernelGGL(precorrect_kernel, dim3(blocks, nbatch), dim3(threads), 0, stream, (const double2*)f,
+                           (const double2*)mode_scale, mc, real_only ? 1 : 0, ccells, work);
+        EFGP_HIP_CHECK(hipGetLastError());
+        return own_fft_pruned_backward(ctx, plan->dim, nc, g.nf, nbatch, work, fine, work, region, isign < 0, stream);
+    }
+    int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((g.cells + threads - 1) / threads, 2048));
+    hipLaunchKernelGGL(precorrect_kernel, dim3(blocks, nbatch), dim3(threads), 0, stream, (const double2*)f,
+                       (const double2*)mode_scale, m, real_only ? 1 : 0, g.cells, fine);
+    EFGP_HIP_CHECK(hipGetLastError());
+    return fft_c2c(ctx, plan->dim, g.nf, nbatch, fine, isign < 0, stream);
+}
+
+// grids beyond LDS: tile-sorted points + LDS tiles (the binning is shared with the tiled spreader when the
+// tile geometry coincides, and cached in the plan otherwise)
+static int gather_tiled(efgp_nufft_s* plan, const WindowSet* w, const GridGeom& g, const TileGeom& tg, bool cplx, const double2* fine,
+                        int nbatch, void* out, hipStream_t stream) {
+    DeviceCtx* ctx = plan->ctx;
+    BinSet* bins = nullptr;
+    int rc = get_bins(plan, tg, cplx ? 2 : 1, stream, &bins);
+    if (rc != EFGP_OK) return rc;
+    TileInterpArgs ta;
+    ta.t = tg;
+    ta.xs = bins->xs;
+    ta.order = bins->order;
+    ta.start = bins->start;
+    ta.npts = plan->npts;
+    ta.chunk = std::max<int64_t>(4096, (plan->npts + 4 * ctx->num_cu - 1) / (4 * (int64_t)ctx->num_cu));
+    ta.coef = w->d_coef;
+    ta.degree = w->p.degree;
+    ta.fine = fine;
+    ta.cells = g.cells;
+    ta.out = out;
+    const size_t tile_lds = (size_t)(cplx ? 2 : 1) * tg.ext[0] * tg.ext[1] * tg.ext[2] * sizeof(double);
+    dim3 tgrid((unsigned)((plan->npts + ta.chunk - 1) / ta.chunk), nbatch);
+    hipError_t te;
+    {
+        KernelTimer timer("interp", stream);
+        te = by_dim(plan->dim, [&](auto D) { return launch_interp_tile_d<decltype(D)::value>(w->p.w, cplx, tgrid, tile_lds, stream, ta); });
+    }
+    if (te != hipSuccess) {
+        set_error("tiled interp kernel launch failed: %s", hipGetErrorString(te));
+        return EFGP_EHIP;
+    }
+    return EFGP_OK;
+}
+
+// the fine grid to the points: tiles when the grid is beyond LDS and the points are many; else the pair, the halo or the plain
+// gather, from LDS when the grid fits and through L2 when not
+static int gather(efgp_nufft_s* plan, const WindowSet* w, const GridGeom& g, const GatherRoute& r, const double2* fine, int nbatch,
+                  void* out, hipStream_t stream) {
+    DeviceCtx* ctx = plan->ctx;
+    const size_t lds_bytes = r.lds_bytes;
     const bool use_lds = lds_bytes <= (size_t)ctx->max_lds;
-    // grids beyond LDS: tile-sorted points + LDS tiles (the binning is shared with the tiled spreader when the
-    // tile geometry coincides, and cached in the plan otherwise)
     TileGeom tg;
     if (!use_lds && plan->npts >= 32768 && std::getenv("EFGP_NO_TILES") == nullptr &&
-        make_tile_geom(plan, w, cplx ? 2 : 1, (size_t)ctx->max_lds - 4096, &tg)) {
-        BinSet* bins = nullptr;
-        rc = get_bins(plan, tg, cplx ? 2 : 1, stream, &bins);
-        if (rc != EFGP_OK) return rc;
-        TileInterpArgs ta;
-        ta.t = tg;
-        ta.xs = bins->xs;
-        ta.order = bins->order;
-        ta.start = bins->start;
-        ta.npts = plan->npts;
-        ta.chunk = std::max<int64_t>(4096, (plan->npts + 4 * ctx->num_cu - 1) / (4 * (int64_t)ctx->num_cu));
-        ta.coef = w->d_coef;
-        ta.degree = w->p.degree;
-        ta.fine = fine;
-        ta.cells = g.cells;
-        ta.out = out;
-        const size_t tile_lds = (size_t)(cplx ? 2 : 1) * tg.ext[0] * tg.ext[1] * tg.ext[2] * sizeof(double);
-        dim3 tgrid((unsigned)((plan->npts + ta.chunk - 1) / ta.chunk), nbatch);
-        hipError_t te;
-        {
-            KernelTimer timer("interp", stream);
-            if (plan->dim == 1) te = launch_interp_tile_d<1>(w->p.w, cplx, tgrid, tile_lds, stream, ta);
-            else if (plan->dim == 2) te = launch_interp_tile_d<2>(w->p.w, cplx, tgrid, tile_lds, stream, ta);
-            else te = launch_interp_tile_d<3>(w->p.w, cplx, tgrid, tile_lds, stream, ta);
-        }
-        if (te != hipSuccess) {
-            set_error("tiled interp kernel launch failed: %s", hipGetErrorString(te));
-            return EFGP_EHIP;
-        }
-        return EFGP_OK;
-    }
+        make_tile_geom(plan, w, r.cplx ? 2 : 1, (size_t)ctx->max_lds - 4096, &tg))
+        return gather_tiled(plan, w, g, tg, r.cplx, fine, nbatch, out, stream);
     InterpArgs a;
     a.x = plan->x;
     a.npts = plan->npts;
@@ -3702,7 +3786,7 @@ static int type2_impl(efgp_nufft_t* plan, const void* f, const void* mode_scale,
     a.coef = w->d_coef;
     a.degree = w->p.degree;
     a.fine = fine;
-    a.image = use_image ? (const double*)fine : nullptr;
+    a.image = r.use_image ? (const double*)fine : nullptr;
     a.out = out;
     const int thr = use_lds ? kInterpThreads : kInterpThreadsGlobal;
     int64_t want = (plan->npts + thr - 1) / thr;
@@ -3716,52 +3800,48 @@ static int type2_impl(efgp_nufft_t* plan, const void* f, const void* mode_scale,
         nwg = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)ctx->num_cu * 8, want));
     }
     a.order = nullptr;
-    if (use_halo && !use_pair && plan->dim >= 2 && plan->npts >= (int64_t)kOrderWindow * 64 && std::getenv("EFGP_NO_CLASS_ORDER") == nullptr) {
-        // same classes as the padded spreader (row pitch nf + W - 1), over global windows: nwg = 0 marks that layout
-        ClassOrder* co = nullptr;
-        for (ClassOrder* o : plan->orders)
-            if (o->W == w->p.w && o->nwg == 0 && o->nf[0] == g.nf[0] && o->nf[1] == g.nf[1] && o->nf[2] == g.nf[2]) co = o;
-        if (!co) {
-            co = new ClassOrder();
-            for (int q = 0; q < 3; ++q) co->nf[q] = g.nf[q];
-            co->W = w->p.w;
-            co->nwg = 0;
-            co->bytes = (size_t)plan->npts * sizeof(int);
-            co->order = (int*)pool_alloc(ctx, co->bytes);
-            if (!co->order) {
-                delete co;
-                return EFGP_ENOMEM;
-            }
-            const unsigned nwin = (unsigned)((plan->npts + kOrderWindow - 1) / kOrderWindow);
-            KernelTimer order_timer("order", stream);
-            if (plan->dim == 2)
-                hipLaunchKernelGGL((class_order_kernel<2, 16>), dim3(nwin), dim3(kSpreadThreads), 0, stream, g, w->p.w, plan->x, plan->npts,
-                                   (int64_t)kOrderWindow, co->order);
-            else
-                hipLaunchKernelGGL((class_order_kernel<3, 16>), dim3(nwin), dim3(kSpreadThreads), 0, stream, g, w->p.w, plan->x, plan->npts,
-                                   (int64_t)kOrderWindow, co->order);
-            EFGP_HIP_CHECK(hipGetLastError());
-            plan->orders.push_back(co);
-        }
-        a.order = co->order;
+    if (r.use_halo && !r.use_pair && plan->dim >= 2 && plan->npts >= (int64_t)kOrderWindow * 64 &&
+        std::getenv("EFGP_NO_CLASS_ORDER") == nullptr) {
+        int rc = get_class_order(plan, w, g, 0, 0, stream, &a.order);
+        if (rc != EFGP_OK) return rc;
     }
     dim3 grid(nwg, nbatch);
     hipError_t e;
     KernelTimer timer("interp", stream);
-    if (use_pair) {
+    if (r.use_pair) {
         e = launch_interp_pair(w->p.w, grid, lds_bytes, stream, a);
-    } else if (use_halo) {
-        if (plan->dim == 1) e = launch_interp_halo_d<1>(w->p.w, grid, lds_bytes, stream, a);
-        else if (plan->dim == 2) e = launch_interp_halo_d<2>(w->p.w, grid, lds_bytes, stream, a);
-        else e = launch_interp_halo_d<3>(w->p.w, grid, lds_bytes, stream, a);
-    } else if (plan->dim == 1) e = launch_interp_d<1>(w->p.w, cplx, use_lds, grid, use_lds ? lds_bytes : 0, stream, a);
-    else if (plan->dim == 2) e = launch_interp_d<2>(w->p.w, cplx, use_lds, grid, use_lds ? lds_bytes : 0, stream, a);
-    else e = launch_interp_d<3>(w->p.w, cplx, use_lds, grid, use_lds ? lds_bytes : 0, stream, a);
+    } else if (r.use_halo) {
+        e = by_dim(plan->dim, [&](auto D) { return launch_interp_halo_d<decltype(D)::value>(w->p.w, grid, lds_bytes, stream, a); });
+    } else {
+        e = by_dim(plan->dim, [&](auto D) {
+            return launch_interp_d<decltype(D)::value>(w->p.w, r.cplx, use_lds, grid, use_lds ? lds_bytes : 0, stream, a);
+        });
+    }
     if (e != hipSuccess) {
         set_error("interp kernel launch failed: %s", hipGetErrorString(e));
         return EFGP_EHIP;
     }
     return EFGP_OK;
+}
+
+static int type2_impl(efgp_nufft_t* plan, const void* f, const void* mode_scale, int nbatch, const int64_t* n_modes, int isign,
+                      int modeord, void* out, int real_only, void* stream_) {
+    int rc = type2_check(plan, f, nbatch, n_modes, isign, out);
+    if (rc != EFGP_OK) return rc;
+    if (plan->npts == 0) return EFGP_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    DeviceGuard guard(plan->device, (hipStream_t)stream_);
+    WindowSet* w = nullptr;
+    rc = get_window(plan, n_modes, stream, &w);
+    if (rc != EFGP_OK) return rc;
+    const GridGeom g = make_geom(plan, w);
+    const GatherRoute r = pick_gather(plan, w, g, nbatch, n_modes, real_only);
+    const size_t fine_bytes = (size_t)nbatch * (size_t)g.cells * sizeof(double2);
+    double2* fine = (double2*)scratch(plan->ctx, SLOT_FINE, r.use_image ? std::max(fine_bytes, r.pair_bytes) : fine_bytes);
+    if (!fine) return EFGP_ENOMEM;
+    rc = modes_to_fine(plan, w, g, r, f, mode_scale, nbatch, n_modes, isign, modeord, real_only, fine, stream);
+    if (rc != EFGP_OK) return rc;
+    return gather(plan, w, g, r, fine, nbatch, out, stream);
 }
 
 }  // extern "C"

@@ -311,3 +311,40 @@ def test_nonfinite_strengths_propagate(bad, N, d, layout):
     assert not torch.isfinite(out).any()
     ok = plan.type1(torch.ones(N, dtype=torch.float64).cuda(), (nm,) * d)      # the plan is not left in a bad state
     assert torch.isfinite(ok).all() and abs(float(ok.reshape(-1)[ok.numel() // 2].real) - N) < 1e-6 * N
+
+
+def test_routes_alternating_on_one_device_share_the_accumulator():
+    """The spread routes share one scratch buffer per device and a record of how much of it is known to be zero: the layout
+    (MFMA) and the tiled route leave their int64 accumulator cleared and skip the memset on the next pass, the LDS route
+    writes its slabs there without clearing them.  Alternating the routes on one device -- a longer accumulator after a
+    shorter one, an int64 pass after slabs -- must give every call the bits its first occurrence gave (all of these routes
+    sum exact integers, so this is equality).  2-D, N = 40000 (>= the 32768 the layout and tile routes require)."""
+    from efgp_hip import NufftPlan, PointSet
+    N, h, tol = 40000, 0.31, 1e-7
+    x = _points(N, 2, 91).cuda()
+    g = torch.Generator().manual_seed(12)
+    y = torch.randn(N, generator=g, dtype=torch.float64).cuda()
+    c = torch.complex(torch.randn(N, generator=g, dtype=torch.float64), torch.randn(N, generator=g, dtype=torch.float64)).cuda()
+    on_layout = NufftPlan(x, h, tol, points=PointSet(x, values=y))
+    plain = NufftPlan(x, h, tol)
+
+    def pair():
+        return torch.cat([t.reshape(-1) for t in on_layout.type1_pair(y, (23, 23), (45, 45))])
+
+    def tiled():
+        return plain.type1(c, (141, 141))
+
+    def probes():
+        return on_layout.type1_rademacher(2024, 3, (45, 45))
+
+    p1 = pair()                                  # 1. layout: int64 accumulator, 2 channels of the (45, 45) grid
+    r2 = plain.type1(y, (23, 23))                # 2. fine grid inside LDS: the buffer now holds slabs, nothing known zero
+    t3 = tiled()                                 # 3. grid beyond LDS: the tiled int64 accumulator, larger than the layout's
+    p4 = pair()                                  # 4. the layout again, on a prefix of what 3 left cleared
+    z5 = probes()                                # 5. two pair grids: longer than the prefix 4 left known zero
+    assert torch.isfinite(p1).all() and torch.isfinite(r2).all() and torch.isfinite(t3).all() and torch.isfinite(z5).all()
+    assert float(p1.abs().max()) > 0 and float(t3.abs().max()) > 0 and float(z5.abs().max()) > 0
+    assert torch.equal(p4, p1)
+    assert torch.equal(pair(), p1)               # 6. calls 1, 3 and 5 once more
+    assert torch.equal(tiled(), t3)
+    assert torch.equal(probes(), z5)
