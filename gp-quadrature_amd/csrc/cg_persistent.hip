@@ -1255,6 +1255,11 @@ __global__ __launch_bounds__(h64::kThreadsH) void cg_herm64_kernel(Args a) {
 // recurrences and stopping rules (cg.py:86-153 / 155-244); results differ from the 64 x 64 embedding by rounding only.
 // fft_shape / efgp_toeplitz_apply keep the reference's grid.
 //
+// Round 6: a single system applies the operator with ONE transformed dimension -- row transforms A, per-frequency 23 x 23
+// Hermitian Toeplitz products over k0 on 192 lanes with their coefficients in registers (dense48_coeffs), row transforms D --
+// two line-transform phases per application instead of four.  The packed column transforms B / C below remain for batches (the
+// resident coefficients cost the second workgroup per CU: 256 + 16 registers) and behind EFGP_CG48_FFT2D=1.
+//
 // A 48-point line lives in 8 adjacent lanes as 48 = 6 x 8, in two mirrored factorizations so that every pruned stage is a
 // radix-8 butterfly with four live legs (dft8_in4 / dft8_out4 of the 64-point kernel) on SIX lanes holding positions j + 6 t,
 // and every full stage a radix-6 butterfly on EIGHT lanes holding positions j + 8 t:
@@ -1275,6 +1280,12 @@ constexpr int LQ = 82;                   // column lanes' exchange scratch per l
 constexpr int G_ELEMS = NR * LDR, T_ELEMS = 2 * NR * LT, Q_ELEMS = HF * LQ;
 static_assert(NR * LX <= Q_ELEMS, "the row lines' scratch aliases the column lines' scratch");
 constexpr int kLdsElems = G_ELEMS + T_ELEMS + Q_ELEMS;     // 53 KB
+// per-frequency Toeplitz products (round 6, dense48_coeffs below): lane = (f1, three rows k0 = a0 .. a0 + 2), a0 = 0, 3, 6, 9
+constexpr int ND = 4 * F;                // dense lanes (waves 0..2)
+constexpr int NC = 25;                   // lags a0 - 11 .. a0 + 13 of a dense lane
+constexpr int LDV = 49;                  // pitch of the prologue's 48 x 48 grid (vhat48_lines)
+constexpr int kLdsElemsDense = F * LDV + (kThreadsH / 8) * LX;      // the prologue's grid + 32 line slots: 73 KB
+static_assert(2 * G_ELEMS + NR * LX <= kLdsElemsDense, "the iteration's G, Yh and row scratch alias the prologue's grid");
 
 // forward DFT-6 in natural order: even / odd split into two DFT-3
 __device__ __forceinline__ void dft3(double2 b0, double2 b1, double2 b2, double2& x0, double2& x1, double2& x2) {
@@ -1419,13 +1430,73 @@ __device__ __forceinline__ void vhat48_lines(const double2* __restrict__ v, int 
         }
     }
 }
+
+// Coefficients of the per-frequency Toeplitz products (round 6).  After the row transforms of phase A the remaining convolution
+// over k0 is, for every f1, a 23 x 23 Hermitian Toeplitz product
+//     Yh[k0][f1] = sum_{k0' = -11..11} c(k0 - k0', f1) G[k0'][f1],      G[-k0'][f1] = conj G[k0'][f1],
+//     c(l0, f1) = (1 / 48) sum_l1 v(l0, l1) w48^(f1 l1),                c(-l0, f1) = conj c(l0, f1)
+// (the 1 / 48 is the inverse row transform's, the lags are centred).  buf = lds2[f0 * LDV + f1] holds the 48 x 48 spectrum
+// (vhat48_lines: factor 1 / 2304, lag l stored at l + n - 1); one inverse pass along f0 in place (the "8x6" lines of
+// vhat48_lines on conjugated data) leaves w48^((n - 1) f1) c(i0 - (n - 1), f1) at [i0][f1].  The dense lane (f1, a0) then takes its
+// 25 lags a0 - 11 .. a0 + 13 into registers for the whole solve: cf[i] = c(a0 - 11 + i, f1), negative lags as conjugates of the
+// positive ones, lag 0 real, lags beyond the Toeplitz vector zero.  NT = 256 threads, tw[t - 1] = w48^((tid & 7) t).
+template <int NT>
+__device__ __forceinline__ void dense48_coeffs(double2* lds2, const double2 (&tw)[5], const double2* __restrict__ twg, int n,
+                                               double2 (&cf)[NC]) {
+    constexpr int SLOTS = NT / 8, PASSES = (F + SLOTS - 1) / SLOTS;
+    double2* const buf = lds2;                       // [48][LDV]
+    double2* const scr = lds2 + F * LDV;             // [SLOTS lines][writer 9 j + value]
+    const int tid = threadIdx.x, slot = tid >> 3, j = tid & 7;
+    double2* const wr = scr + slot * LX + 9 * j;
+    const double2* const rd = scr + slot * LX + j;
+    double2 u6[6], x8[8];
+#pragma unroll
+    for (int ps = 0; ps < PASSES; ++ps) {
+        const int line = slot + ps * SLOTS;
+        const bool act = line < F;
+#pragma unroll
+        for (int t = 0; t < 6; ++t) u6[t] = act ? s64::conjd(buf[(j + 8 * t) * LDV + line]) : make_double2(0.0, 0.0);
+        dft6(u6);
+#pragma unroll
+        for (int t = 1; t < 6; ++t) u6[t] = cmulp(u6[t], tw[t - 1]);
+        wave_sync();
+#pragma unroll
+        for (int t = 0; t < 6; ++t) wr[t] = u6[t];
+        wave_sync();
+        s64::load8_all<9>(rd, x8);
+        dft_fwd<8>(x8);
+        if (act && j < 6) {
+#pragma unroll
+            for (int t = 0; t < 8; ++t) buf[(j + 6 * t) * LDV + line] = s64::conjd(x8[t]);
+        }
+    }
+    __syncthreads();
+    const int f1 = tid % F, a0 = 3 * (tid / F);
+    const bool dense = tid < ND;
+    const double2 wc = twg[((n - 1) * f1) % F];
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+        const int l = a0 - 11 + i, al = l < 0 ? -l : l;
+        double2 c = make_double2(0.0, 0.0);
+        if (dense && al <= n - 1) {
+            const double2 r = buf[(al + n - 1) * LDV + f1];
+            c = make_double2(fma(r.y, wc.y, r.x * wc.x), fma(-r.x, wc.y, r.y * wc.x));       // r conj(wc)
+            if (l < 0) c.y = -c.y;
+            if (l == 0) c.y = 0.0;
+        }
+        cf[i] = c;
+    }
+}
 }  // namespace h48
 
 // FUSED (the fit's cold-start mean solve, efgp_cg_solve_mean_fused): the 48 x 48 spectrum is made in the prologue from the Toeplitz
 // vector (vhat48_lines on the 256 threads, in LDS the iteration reuses afterwards) and ws is evaluated from the built-in kernel's
 // parameters (spectral_weights.hpp) by the row lanes that hold the modes; both are written out for later users.  The iteration is
 // the same code.
-template <int VARIANT, bool FUSED = false>
+// DENSE (round 6): the operator application keeps the row transforms A and D and replaces the packed column transforms B / C by
+// per-frequency Hermitian Toeplitz products over k0 with coefficients resident in registers (h48::dense48_coeffs); !DENSE is the
+// round 4 application (EFGP_CG48_FFT2D=1).
+template <int VARIANT, bool FUSED = false, bool DENSE = true>
 __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
     using namespace h48;
     using h64::block_sum_h;
@@ -1439,8 +1510,8 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
     __shared__ double s_rcp;             // 1 / (<r,z> + 1e-16) for the next beta, computed by an idle wave during A
     __shared__ int s_stop;               // convergence decision of the last completed iteration, taken by an idle wave during A
     double2* const Gb = lds2;                    // G[k0][f1], k0 = 0..11 (rows beyond h are zero), f1 = 0..47
-    double2* const Tb = lds2 + G_ELEMS;          // conj T[row(p)][q]: rows p = 0..11 and 36..47 (stored at p - 24)
-    double2* const Qb = Tb + T_ELEMS;            // exchange scratch: column lines (B/C), aliased by the row lines (A, D)
+    double2* const Tb = lds2 + G_ELEMS;          // conj T[row(p)][q]: rows p = 0..11 and 36..47 (stored at p - 24); DENSE: conj Yh[k0][f1], pitch LDR
+    double2* const Qb = Tb + (DENSE ? G_ELEMS : T_ELEMS);       // exchange scratch: column lines (B/C), aliased by the row lines (A, D)
     const int n = a.g.n[0], h = (n - 1) / 2, M = a.g.M;
     const int row = blockIdx.x;
     const int64_t base = (int64_t)row * M;
@@ -1457,6 +1528,9 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
     const int qs = col_role ? q : 0;
     double2* const qw = Qb + qs * LQ + 9 * jc;
     const double2* const qr = Qb + qs * LQ + jc;
+    // dense role (DENSE, waves 0..2): lane = (f1d, rows k0 = kd, kd + 1, kd + 2)
+    const bool dense_role = tid < ND;
+    const int f1d = tid % F, kd = 3 * (tid / F);
 
     double2 twr[5], twc[5];              // w48^(lane-in-line * t), t = 1..5 (35 at most: no wrap)
 #pragma unroll
@@ -1464,23 +1538,39 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
         twr[t - 1] = a.g.tw[0][j * t];
         twc[t - 1] = a.g.tw[0][jc * t];
     }
-    // real spectrum of the centred lags, halved (the unpacking of D averages two terms): vhat = w^((n-1)(f0+f1)) S
     if (FUSED) {
         vhat48_lines<kThreadsH, true>(a.vsrc, a.vL0, a.vL1, 1.0 / 2304.0, a.vhat_out, lds2);
         __syncthreads();
     }
-    const double2* const vh = FUSED ? lds2 : a.vhat;
-    constexpr int LV = FUSED ? 49 : F;                    // pitch of vh: the prologue's grid, or the operator's spectrum
     double sa[6], sb[6];
+    double2 cf[DENSE ? NC : 1];
+    if constexpr (DENSE) {
+        // the operator's spectrum, from memory or from the prologue's grid (the same numbers), through one inverse pass along f0:
+        // the same statements with and without FUSED
+        if (!FUSED) {
 #pragma unroll
-    for (int t = 0; t < 6; ++t) {
-        const int f0 = jc + 8 * t;
-        const double2 va = vh[f0 * LV + qs], vb = vh[f0 * LV + qs + HF];
-        const double2 wa = a.g.tw[0][((n - 1) * (f0 + qs)) % F], wb = a.g.tw[0][((n - 1) * (f0 + qs + HF)) % F];
-        sa[t] = 0.5 * (va.x * wa.x + va.y * wa.y);
-        sb[t] = -0.5 * (vb.x * wb.x + vb.y * wb.y);      // sign: conjugation in front of the inverse transform
+            for (int k = 0; k < F * F / kThreadsH; ++k) {
+                const int t = tid + k * kThreadsH, i0 = t / F, i1 = t - i0 * F;
+                lds2[i0 * LDV + i1] = a.vhat[t];
+            }
+            __syncthreads();
+        }
+        dense48_coeffs<kThreadsH>(lds2, twr, a.g.tw[0], n, cf);
+        __syncthreads();                                  // the iteration's G / Yh / scratch alias the prologue's grid
+    } else {
+        // real spectrum of the centred lags, halved (the unpacking of D averages two terms): vhat = w^((n-1)(f0+f1)) S
+        const double2* const vh = FUSED ? lds2 : a.vhat;
+        constexpr int LV = FUSED ? LDV : F;               // pitch of vh: the prologue's grid, or the operator's spectrum
+#pragma unroll
+        for (int t = 0; t < 6; ++t) {
+            const int f0 = jc + 8 * t;
+            const double2 va = vh[f0 * LV + qs], vb = vh[f0 * LV + qs + HF];
+            const double2 wa = a.g.tw[0][((n - 1) * (f0 + qs)) % F], wb = a.g.tw[0][((n - 1) * (f0 + qs + HF)) % F];
+            sa[t] = 0.5 * (va.x * wa.x + va.y * wa.y);
+            sb[t] = -0.5 * (vb.x * wb.x + vb.y * wb.y);      // sign: conjugation in front of the inverse transform
+        }
+        if (FUSED) __syncthreads();                           // the iteration's G / T / scratch alias the prologue's grid
     }
-    if (FUSED) __syncthreads();                           // the iteration's G / T / scratch alias the prologue's grid
     const bool z6_ok = jc > 0;                            // row 12 - jc exists
     const int jr = col6 ? jc : 0;                         // rows this lane packs in B (the lanes jc >= 6 only take part in the radix-6 stages)
 
@@ -1544,9 +1634,42 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
         rcp_rz = s_rcp;
         if (stop) return;                                 // uniform: the iteration that just started is abandoned
         EFGP_STAMP(0);
-        // B ("6x8"): packed columns z[k0] = G[k0][q] + i G[k0][q + 24] (k0 >= 0), conj G[-k0][q] + i conj G[-k0][q + 24] (k0 < 0),
-        // rows of lane jc < 6: k0 = jc, jc + 6, jc - 12, jc - 6
-        if (col_role) {
+        if constexpr (DENSE) {
+            // per-frequency Hermitian Toeplitz product over k0: Yh[k0] = c(k0) Re G[0] + sum_m c(k0 - m) G[m] + c(k0 + m) conj G[m],
+            // m = 1..11.  Row 0 holds the modes +k1 and -k1 BOTH: the imaginary parts of G[0] and Yh[0] are dropped (the projection
+            // onto coefficient arrays of real functions that the packed columns make; see cg_herm64_kernel).  All twelve reads of
+            // G are in flight before the first multiply; the accumulators are six independent chains.
+            if (dense_role) {
+                const double2* g0 = Gb + f1d;
+                double2 gm[NR];
+#pragma unroll
+                for (int m = 0; m < NR; ++m) gm[m] = g0[m * LDR];
+                double2 acc[3];
+#pragma unroll
+                for (int o = 0; o < 3; ++o) acc[o] = make_double2(cf[11 + o].x * gm[0].x, cf[11 + o].y * gm[0].x);
+#pragma unroll
+                for (int m = 1; m < NR; ++m) {
+#pragma unroll
+                    for (int o = 0; o < 3; ++o) {
+                        const double2 cm = cf[11 + o - m], cp = cf[11 + o + m];
+                        acc[o].x = fma(cm.x, gm[m].x, acc[o].x);
+                        acc[o].y = fma(cm.x, gm[m].y, acc[o].y);
+                        acc[o].x = fma(-cm.y, gm[m].y, acc[o].x);
+                        acc[o].y = fma(cm.y, gm[m].x, acc[o].y);
+                        acc[o].x = fma(cp.x, gm[m].x, acc[o].x);
+                        acc[o].y = fma(-cp.x, gm[m].y, acc[o].y);
+                        acc[o].x = fma(cp.y, gm[m].y, acc[o].x);
+                        acc[o].y = fma(cp.y, gm[m].x, acc[o].y);
+                    }
+                }
+                double2* t0 = Tb + kd * LDR + f1d;
+                t0[0] = make_double2(acc[0].x, kd == 0 ? 0.0 : -acc[0].y);       // conj Yh: D transforms conjugated inputs
+                t0[LDR] = make_double2(acc[1].x, -acc[1].y);
+                t0[2 * LDR] = make_double2(acc[2].x, -acc[2].y);
+            }
+        } else if (col_role) {
+            // B ("6x8"): packed columns z[k0] = G[k0][q] + i G[k0][q + 24] (k0 >= 0), conj G[-k0][q] + i conj G[-k0][q + 24] (k0 < 0),
+            // rows of lane jc < 6: k0 = jc, jc + 6, jc - 12, jc - 6
             const double2* g0 = Gb + q;
             const double2 a0 = g0[jr * LDR], b0 = g0[jr * LDR + HF];
             const double2 a1 = g0[(jr + 6) * LDR], b1 = g0[(jr + 6) * LDR + HF];
@@ -1576,15 +1699,22 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
         }
         __syncthreads();
         EFGP_STAMP(1);
-        // D ("8x6"): row k0 >= 0 of the result from the packed columns at +k0 and -k0; conjugated inputs, forward transform
+        // D ("8x6"): row k0 >= 0 of the result, from Yh[k0] (DENSE) or from the packed columns at +k0 and -k0; conjugated inputs,
+        // forward transform
         if (row_role) {
-            const double2* tp = Tb + k0 * LT + j;
-            const double2* tm = Tb + (k0 == 0 ? 0 : 2 * NR - k0) * LT + j;
+            if constexpr (DENSE) {
+                const double2* tp = Tb + k0 * LDR + j;
 #pragma unroll
-            for (int u3 = 0; u3 < 3; ++u3) {
-                const double2 P = tp[8 * u3], Mv = tm[8 * u3];
-                u6[u3] = make_double2(P.x + Mv.x, P.y - Mv.y);
-                u6[u3 + 3] = make_double2(-P.y - Mv.y, P.x - Mv.x);
+                for (int t = 0; t < 6; ++t) u6[t] = tp[8 * t];
+            } else {
+                const double2* tp = Tb + k0 * LT + j;
+                const double2* tm = Tb + (k0 == 0 ? 0 : 2 * NR - k0) * LT + j;
+#pragma unroll
+                for (int u3 = 0; u3 < 3; ++u3) {
+                    const double2 P = tp[8 * u3], Mv = tm[8 * u3];
+                    u6[u3] = make_double2(P.x + Mv.x, P.y - Mv.y);
+                    u6[u3 + 3] = make_double2(-P.y - Mv.y, P.x - Mv.x);
+                }
             }
             dft6(u6);
             exchange_6to8(u6, v, xw, xr, twr);            // lanes j < 6: v[k2] = conj Y[k0][j + 6 k2], k2 in {0, 1, 6, 7}
@@ -2523,13 +2653,17 @@ int persistent_cg_launch(const ToepGeom& tg, const double2* const* twiddles, con
         set_error("fused mean solve: the system is not a cold-start 48 x 48 Hermitian mean solve");
         return EFGP_EUNSUPPORTED;
     }
+    // EFGP_CG48_FFT2D=1: the round 4 operator application (packed column transforms) instead of the per-frequency Toeplitz products.
+    // Batches keep it too: the resident coefficients take the kernel to 256 + 16 registers, one workgroup per CU instead of two.
+    const bool dense48 = rows == 1 && std::getenv("EFGP_CG48_FFT2D") == nullptr;
     if (herm48 && fuse != nullptr) {
         // the prologue's grid + 32 line slots of scratch outgrow the iteration's 53 KB; one workgroup, so the extra LDS costs nothing
-        constexpr size_t lds_f = (size_t)(48 * 49 + (h48::kThreadsH / 8) * h48::LX) * sizeof(double2);
-        static_assert(48 * 49 + (h48::kThreadsH / 8) * h48::LX >= h48::kLdsElems, "the fused prologue's LDS covers the iteration's");
+        constexpr size_t lds_f = (size_t)h48::kLdsElemsDense * sizeof(double2);
+        static_assert(h48::kLdsElemsDense >= h48::kLdsElems, "the fused prologue's LDS covers the iteration's");
         bool& attr_f = per_device_flag("cg_herm48_fused");
         if (!attr_f) {
-            hipError_t e2 = hipFuncSetAttribute((const void*)cg_herm48_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f);
+            hipError_t e2 = hipFuncSetAttribute((const void*)cg_herm48_kernel<0, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f);
+            if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)cg_herm48_kernel<0, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f);
             if (e2 != hipSuccess) {
                 set_error("fused mean solve (48x48): hipFuncSetAttribute failed: %s", hipGetErrorString(e2));
                 return EFGP_EHIP;
@@ -2552,13 +2686,18 @@ int persistent_cg_launch(const ToepGeom& tg, const double2* const* twiddles, con
         g.F[0] = g.F[1] = 48;
         g.tw[0] = g.tw[1] = h48->tw;
         KernelTimer timer("cg_solve", stream);
-        hipLaunchKernelGGL((cg_herm48_kernel<0, true>), dim3(1), dim3(h48::kThreadsH), lds_f, stream, a);
+        if (dense48) hipLaunchKernelGGL((cg_herm48_kernel<0, true, true>), dim3(1), dim3(h48::kThreadsH), lds_f, stream, a);
+        else hipLaunchKernelGGL((cg_herm48_kernel<0, true, false>), dim3(1), dim3(h48::kThreadsH), lds_f, stream, a);
     } else if (herm48) {
         bool& attr_h = per_device_flag("cg_herm48");
-        const size_t lds_h = (size_t)h48::kLdsElems * sizeof(double2);
+        // the coefficient prologue works on the 48 x 48 grid: 73 KB, two workgroups per CU still fit
+        const size_t lds_d = (size_t)h48::kLdsElemsDense * sizeof(double2);
+        const size_t lds_h = dense48 ? lds_d : (size_t)h48::kLdsElems * sizeof(double2);
         if (!attr_h) {
-            hipError_t e2 = hipFuncSetAttribute((const void*)cg_herm48_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h);
-            if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)cg_herm48_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h);
+            hipError_t e2 = hipFuncSetAttribute((const void*)cg_herm48_kernel<0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
+            if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)cg_herm48_kernel<1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
+            if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)cg_herm48_kernel<0, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
+            if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)cg_herm48_kernel<1, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
             if (e2 != hipSuccess) {
                 set_error("persistent CG (48x48, Hermitian): hipFuncSetAttribute failed: %s", hipGetErrorString(e2));
                 return EFGP_EHIP;
@@ -2569,8 +2708,10 @@ int persistent_cg_launch(const ToepGeom& tg, const double2* const* twiddles, con
         g.F[0] = g.F[1] = 48;
         g.tw[0] = g.tw[1] = h48->tw;
         KernelTimer timer("cg_solve", stream);
-        if (variant == 0) hipLaunchKernelGGL(cg_herm48_kernel<0>, dim3(rows), dim3(h48::kThreadsH), lds_h, stream, a);
-        else hipLaunchKernelGGL(cg_herm48_kernel<1>, dim3(rows), dim3(h48::kThreadsH), lds_h, stream, a);
+        if (dense48 && variant == 0) hipLaunchKernelGGL((cg_herm48_kernel<0, false, true>), dim3(rows), dim3(h48::kThreadsH), lds_h, stream, a);
+        else if (dense48) hipLaunchKernelGGL((cg_herm48_kernel<1, false, true>), dim3(rows), dim3(h48::kThreadsH), lds_h, stream, a);
+        else if (variant == 0) hipLaunchKernelGGL((cg_herm48_kernel<0, false, false>), dim3(rows), dim3(h48::kThreadsH), lds_h, stream, a);
+        else hipLaunchKernelGGL((cg_herm48_kernel<1, false, false>), dim3(rows), dim3(h48::kThreadsH), lds_h, stream, a);
     } else if (herm64) {
         bool& attr_h = per_device_flag("cg_herm64");
         const size_t lds_h = (size_t)h64::kLdsElems * sizeof(double2);
