@@ -26,3 +26,18 @@ def test_every_random_case_is_within_twice_its_tolerance(seed):
     print(f"\nseed {seed}: worst error / tol = {worst:.2f} over 60 cases")
     assert not failures, failures
     assert worst <= 2.0
+
+
+@pytest.mark.parametrize("seed", [1, 4])
+def test_every_random_case_with_random_options_is_within_twice_its_tolerance(seed):
+    """The same cases with a mode box drawn per axis (even and odd sizes mixed) and isign, modeord, a complex mode_scale and a
+    plan centre drawn too; references from tests/_nudft.py."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import fuzz_nufft
+    finally:
+        sys.path.pop(0)
+    worst, failures = fuzz_nufft.run(40, seed, verbose=False, options=True)
+    print(f"\nseed {seed}: worst error / tol = {worst:.2f} over 40 cases with options")
+    assert not failures, failures
+    assert worst <= 2.0
