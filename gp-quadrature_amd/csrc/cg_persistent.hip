@@ -2447,9 +2447,28 @@ bool persistent_cg_eligible(const ToepGeom& tg) {
     return true;
 }
 
-int persistent_cg_launch(const ToepGeom& tg, const double2* const* twiddles, const double2* vhat, const Herm48Operands* h48,
+int persistent_cg_launch(const ToepGeom& full, const double2* const* tw_full, const double2* vhat, const Herm48Operands* h48,
                          const CgSolve& s, int* d_iters, hipStream_t stream, const LanczosOut* lz, const MeanFusedOperands* fuse) {
     using namespace pcg;
+    // An axis with a single mode has F = 1: no stage to run (radices_for gives nstages = 0).  As axis 0 it would own the fused
+    // middle stage -- the spectral multiply would be skipped and the spectrum registers loaded through radix[-1].  Such an axis has
+    // one lag and one cell: block, padded grid and spectrum keep their row-major order without it, so the kernels get the geometry
+    // of the remaining axes (exact).  A grid of one cell in all never comes here (efgp_toeplitz_create_ex).
+    ToepGeom tg = full;
+    const double2* twiddles[3] = {nullptr, nullptr, nullptr};
+    tg.d = 0;
+    for (int i = 0; i < full.d; ++i) {
+        if (full.F[i] == 1) continue;
+        tg.n[tg.d] = full.n[i];
+        tg.F[tg.d] = full.F[i];
+        twiddles[tg.d] = tw_full[i];
+        ++tg.d;
+    }
+    for (int i = tg.d; i < 3; ++i) tg.n[i] = tg.F[i] = 1;
+    if (tg.d == 0) {
+        set_error("persistent CG: a grid of a single cell has no transform to run");
+        return EFGP_EUNSUPPORTED;
+    }
     Args a;
     a.ws_out = nullptr;
     a.vsrc = nullptr;
@@ -2644,7 +2663,8 @@ int persistent_cg_launch(const ToepGeom& tg, const double2* const* twiddles, con
         }
         attr_set = true;
     }
-    const bool fast64 = tg.d == 2 && g.F[0] == 64 && g.F[1] == 64 && g.n[0] == g.n[1] && g.n[0] <= 32 &&
+    // the specialised kernels are picked by the caller's shape: a block with a unit axis runs the generic kernel on its other axes
+    const bool fast64 = full.d == 2 && g.F[0] == 64 && g.F[1] == 64 && g.n[0] == g.n[1] && g.n[0] <= 32 &&
                         std::getenv("EFGP_NO_CG64") == nullptr;
     const bool herm64 = fast64 && s.hermitian && !lz && (g.n[0] & 1) && g.n[0] <= 31 && std::getenv("EFGP_NO_CG_HERM") == nullptr;
     // blocks of up to 23 x 23 modes: the smallest circulant grid, 48 x 48 (the operator holds a second spectrum for it)
@@ -2727,7 +2747,7 @@ int persistent_cg_launch(const ToepGeom& tg, const double2* const* twiddles, con
         KernelTimer timer("cg_solve", stream);
         if (variant == 0) hipLaunchKernelGGL(cg_herm64_kernel<0>, dim3(rows), dim3(h64::kThreadsH), lds_h, stream, a);
         else hipLaunchKernelGGL(cg_herm64_kernel<1>, dim3(rows), dim3(h64::kThreadsH), lds_h, stream, a);
-    } else if (tg.d == 1 && !lz && g.n[0] <= 64 * l1d::KS - 1 && g.F[0] >= 8 && g.F[0] <= 512 && (g.F[0] & (g.F[0] - 1)) == 0 &&
+    } else if (full.d == 1 && !lz && g.n[0] <= 64 * l1d::KS - 1 && g.F[0] >= 8 && g.F[0] <= 512 && (g.F[0] & (g.F[0] - 1)) == 0 &&
                std::getenv("EFGP_NO_CG_LINE1D") == nullptr) {
         KernelTimer timer("cg_solve", stream);             // 1-D: one wave per system
         hipLaunchKernelGGL(cg_line1d_kernel, dim3(rows), dim3(64), (size_t)4 * g.F[0] * sizeof(double2), stream, a);

@@ -3265,6 +3265,9 @@ int efgp_toeplitz_create_ex(efgp_toeplitz_t** op_out, int device, int dim, const
             op->vhat_cg = nullptr;
         }
     }
+    // a single mode on a grid of one cell (and no 64 x 64 embedding): the single-launch kernels have no transform stage to run
+    // there (persistent_cg_launch); the multi-launch solver skips axes of extent 1 in its transforms and solves the scalar system
+    if (op->g.Ftot == 1 && !op->cg64) op->persistent_ok = false;
     if (op->pair_pending) {
         op->v_ref = (const double2*)v;
         op->vhat48_ready = false;
