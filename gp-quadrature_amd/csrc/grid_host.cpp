@@ -13,6 +13,7 @@
 
 #include "../../include/efgp_hip.h"
 #include "common.hpp"
+#include "spectral_weights.hpp"
 
 namespace {
 
@@ -113,6 +114,35 @@ extern "C" int efgp_spectral_weights_host(int kind, int dim, double nu, double l
             dprime_out[4 * t + 1] = 0.0;
             dprime_out[4 * t + 2] = hd * (S / variance);
             dprime_out[4 * t + 3] = 0.0;
+        }
+    }
+    return EFGP_OK;
+}
+
+// Host twin of efgp_spectral_weights_nd: the ARD weights and their d + 1 derivative rows on the per-axis grid, through the same
+// per-node function as the device launch (spectral_weights.hpp).  What efgp_spectral_weights_host is to the isotropic kernels.
+extern "C" int efgp_spectral_weights_host_nd(int kind, int dim, double nu, const double* lengthscales, double variance, const double* h,
+                                             const int64_t* n_modes, double* ws_out, double* dprime_out) {
+    EFGP_REQUIRE(ws_out, "efgp_spectral_weights_host_nd: null output");
+    efgp::ArdSpec k;
+    double hd;
+    int64_t M;
+    EFGP_REQUIRE(efgp::ard_spec(kind, dim, nu, lengthscales, variance, h, n_modes, &k, &hd, &M),
+                 "efgp_spectral_weights_host_nd: kind 0 | 1 (nu 1/2, 3/2, 5/2), dim 1..3, positive hypers and spacings, odd mode counts");
+    const int H = dim + 1;
+    for (int64_t t = 0; t < M; ++t) {
+        double S, dlog[3];
+        efgp::spectral_density_nd_at(k, t, S, dlog);
+        ws_out[2 * t] = std::sqrt(S * hd);
+        ws_out[2 * t + 1] = 0.0;
+        if (dprime_out) {
+            double* row = dprime_out + 2 * H * t;
+            for (int a = 0; a < dim; ++a) {
+                row[2 * a] = hd * (S * dlog[a]);
+                row[2 * a + 1] = 0.0;
+            }
+            row[2 * dim] = hd * (S / variance);
+            row[2 * dim + 1] = 0.0;
         }
     }
     return EFGP_OK;

@@ -2070,7 +2070,7 @@ struct efgp_nufft_s {
     int64_t npts = 0;
     const double* x = nullptr;
     double xcen[3] = {0, 0, 0};
-    double h = 0.0;
+    double h[3] = {0, 0, 0};      // grid spacing per axis (one value on all axes unless made by efgp_nufft_create_nd)
     double tol = 1e-6;
     DeviceCtx* ctx = nullptr;
     std::vector<efgp::BinSet*> bins;     // tile-sorted copies of the points, per (fine grid, W, tile) geometry
@@ -2176,7 +2176,7 @@ static GridGeom make_geom(const efgp_nufft_s* plan, const WindowSet* w) {
     g.cells = 1;
     for (int a = 0; a < 3; ++a) {
         g.nf[a] = w->nf[a];
-        g.scale[a] = plan->h * (double)w->nf[a];
+        g.scale[a] = plan->h[a] * (double)w->nf[a];
         g.xcen[a] = plan->xcen[a];
         g.cells *= w->nf[a];
     }
@@ -2515,7 +2515,7 @@ static bool make_tile_geom(const efgp_nufft_s* plan, const WindowSet* w, int cha
             t.nt[a] = (t.nf[a] + Tmax - 1) / Tmax;
             t.T[a] = (t.nf[a] + t.nt[a] - 1) / t.nt[a];
             t.ext[a] = t.T[a] + W - 1;
-            t.scale[a] = plan->h * (double)w->nf[a];
+            t.scale[a] = plan->h[a] * (double)w->nf[a];
             t.xcen[a] = plan->xcen[a];
             t.nbins *= t.nt[a];
         } else {
@@ -3400,7 +3400,7 @@ int efgp_nufft_create(efgp_nufft_t** plan_out, int device, int dim, int64_t npts
     p->dim = dim;
     p->npts = npts;
     p->x = x;
-    p->h = h;
+    for (int a = 0; a < 3; ++a) p->h[a] = h;
     p->tol = tol;
     p->ctx = ctx;
     for (int a = 0; a < dim; ++a) p->xcen[a] = xcen_host ? xcen_host[a] : 0.0;
@@ -3411,6 +3411,27 @@ int efgp_nufft_create(efgp_nufft_t** plan_out, int device, int dim, int64_t npts
 int efgp_nufft_create_on(efgp_nufft_t** plan_out, efgp_points_t* pts, const double* xcen_host, double h, double tol) {
     EFGP_REQUIRE(pts, "efgp_nufft_create_on: null point layout");
     int rc = efgp_nufft_create(plan_out, pts->device, pts->dim, pts->npts, pts->x, xcen_host, h, tol);
+    if (rc != EFGP_OK) return rc;
+    (*plan_out)->points = pts;
+    return EFGP_OK;
+}
+
+// Per-axis spacing: phase 2 pi sum_a h_a k_a (x_a - xcen_a).  Host code only -- the kernels take scale[a] = h[a] * nf[a] per axis
+// (nufft_dev.hpp), and every route sizes its tiles, bands and accumulators from nf[a] and scale[a] per axis.
+int efgp_nufft_create_nd(efgp_nufft_t** plan_out, int device, int dim, int64_t npts, const double* x, const double* xcen_host,
+                         const double* h, double tol) {
+    EFGP_REQUIRE(h, "efgp_nufft_create_nd: null h");
+    EFGP_REQUIRE(dim >= 1 && dim <= 3, "efgp_nufft_create_nd: dim must be 1, 2 or 3 (got %d)", dim);
+    for (int a = 0; a < dim; ++a) EFGP_REQUIRE(std::isfinite(h[a]), "efgp_nufft_create_nd: h must be finite");
+    int rc = efgp_nufft_create(plan_out, device, dim, npts, x, xcen_host, h[0], tol);
+    if (rc != EFGP_OK) return rc;
+    for (int a = 0; a < dim; ++a) (*plan_out)->h[a] = h[a];
+    return EFGP_OK;
+}
+
+int efgp_nufft_create_on_nd(efgp_nufft_t** plan_out, efgp_points_t* pts, const double* xcen_host, const double* h, double tol) {
+    EFGP_REQUIRE(pts, "efgp_nufft_create_on_nd: null point layout");
+    int rc = efgp_nufft_create_nd(plan_out, pts->device, pts->dim, pts->npts, pts->x, xcen_host, h, tol);
     if (rc != EFGP_OK) return rc;
     (*plan_out)->points = pts;
     return EFGP_OK;

@@ -162,6 +162,76 @@ __global__ __launch_bounds__(256) void spectral_weights_kernel(int kind, int dim
     }
 }
 
+// ---- per-axis grids (ARD kernels): n[a] modes and spacing h[a] per axis, last axis fastest --------------------------------------
+struct AxisGrid {
+    int d;
+    int n[3];
+    double h[3];
+    int64_t M;
+};
+
+// phase 2 pi sum_a k_a h_a x_a for mode index t of the (n_0, .., n_{d-1}) box, k_a = i_a - (n_a - 1)/2
+__device__ __forceinline__ double mode_phase_nd(const AxisGrid& g, const double* __restrict__ x, int64_t t) {
+    double ph = 0.0;
+    for (int a = g.d - 1; a >= 0; --a) {
+        const int ia = (int)(t % g.n[a]);
+        t /= g.n[a];
+        ph += (double)(ia - (g.n[a] - 1) / 2) * g.h[a] * x[a];
+    }
+    return 2.0 * M_PI * ph;
+}
+
+__global__ __launch_bounds__(256) void variance_rhs_nd_kernel(AxisGrid g, const double* __restrict__ x, const double2* __restrict__ ws,
+                                                              double2* __restrict__ rhs) {
+    const int b = blockIdx.y;
+    const double* xb = x + (int64_t)b * g.d;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < g.M; t += (int64_t)gridDim.x * blockDim.x) {
+        double sn, cs;
+        sincos(mode_phase_nd(g, xb, t), &sn, &cs);
+        const double2 w = ws[t];
+        rhs[(int64_t)b * g.M + t] = make_double2(w.x * cs + w.y * sn, w.y * cs - w.x * sn);      // ws * conj(f)
+    }
+}
+
+__global__ __launch_bounds__(256) void variance_contract_nd_kernel(AxisGrid g, const double* __restrict__ x, const double2* __restrict__ ws,
+                                                                   const double2* __restrict__ gamma, double* __restrict__ out) {
+    __shared__ double part[4];
+    const int b = blockIdx.x;
+    const double* xb = x + (int64_t)b * g.d;
+    double acc = 0.0;
+    for (int64_t t = threadIdx.x; t < g.M; t += blockDim.x) {
+        double sn, cs;
+        sincos(mode_phase_nd(g, xb, t), &sn, &cs);
+        const double2 w = ws[t], gm = gamma[(int64_t)b * g.M + t];
+        const double2 wg = make_double2(w.x * gm.x - w.y * gm.y, w.x * gm.y + w.y * gm.x);
+        acc += cs * wg.x - sn * wg.y;                                                          // Re (f * ws * gamma)
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += part[i];
+        out[b] = s > 0.0 ? s : 0.0;
+    }
+}
+
+// ws[t] = sqrt(S(omega_t) prod_a h_a) and the d + 1 rows prod_a h_a * (dS/dl_0, .., dS/dl_{d-1}, dS/dvariance) of the ARD kernels on
+// the per-axis grid omega_ta = k_a h_a: one launch, the density evaluated once per node (spectral_density_nd_at)
+__global__ __launch_bounds__(256) void spectral_weights_nd_kernel(ArdSpec k, double var, double hd, int64_t M, double2* __restrict__ ws,
+                                                                  double2* __restrict__ dprime) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= M) return;
+    double S, dlog[3];
+    spectral_density_nd_at(k, t, S, dlog);
+    ws[t] = make_double2(sqrt(S * hd), 0.0);
+    if (dprime) {
+        double2* row = dprime + (int64_t)(k.dim + 1) * t;
+        for (int a = 0; a < k.dim; ++a) row[a] = make_double2(hd * (S * dlog[a]), 0.0);
+        row[k.dim] = make_double2(hd * (S / var), 0.0);
+    }
+}
+
 // out[s, j] = a ws[j] fz[s, j] + b e[s, j] on the symmetric mode box (flat index j, negated frequency at M - 1 - j), with
 // e[s, j] = (z0 + i z1) / sqrt 2 of Box-Muller pair s at index j + index_offset below the centre, z0 at the centre (real), and the
 // upper half WRITTEN as the conjugate of the lower: the row is conjugate-even bit for bit.  fz (a transform of real rows) is
@@ -191,6 +261,33 @@ __global__ __launch_bounds__(256) void hermitian_normal_rows_kernel(unsigned lon
 }  // namespace efgp
 
 using namespace efgp;
+
+// The zero-padded correlation on any lag box: pad | forward transforms | multiply and sum over probes | one inverse | crop and scale
+static int lag_sums_general(DeviceCtx* ctx, const LagGeom& g, int dim, const int64_t* sizes, const void* gamma, const double* eta, int nprobes,
+                            void* out, hipStream_t stream) {
+    // probes are processed in slabs so that the padded transforms stay within ~256 MB of scratch
+    const int64_t per = std::max<int64_t>(1, std::min<int64_t>(nprobes, ((int64_t)256 << 20) / (int64_t)(2 * g.P * sizeof(double2))));
+    double2* pad = (double2*)scratch(ctx, SLOT_TOEP_PAD, (size_t)(2 * per + 1) * g.P * sizeof(double2));
+    if (!pad) return EFGP_ENOMEM;
+    double2* acc = pad + (int64_t)2 * per * g.P;
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((g.P + 255) / 256, 1024));
+    for (int64_t j0 = 0; j0 < nprobes; j0 += per) {
+        const int J = (int)std::min<int64_t>(per, nprobes - j0);
+        hipLaunchKernelGGL(lag_pad_kernel, dim3(blocks, J), dim3(256), 0, stream, g, (const double2*)gamma + j0 * g.M, eta + j0 * g.M, pad);
+        EFGP_HIP_CHECK(hipGetLastError());
+        int rc = fft_c2c(ctx, dim, sizes, 2 * J, pad, true, stream);
+        if (rc != EFGP_OK) return rc;
+        hipLaunchKernelGGL(lag_mul_sum_kernel, dim3(blocks), dim3(256), 0, stream, g.P, J, (const double2*)pad, acc, j0 > 0 ? 1 : 0);
+        EFGP_HIP_CHECK(hipGetLastError());
+    }
+    int rc = fft_c2c(ctx, dim, sizes, 1, acc, false, stream);
+    if (rc != EFGP_OK) return rc;
+    const int oblocks = (int)std::max<int64_t>(1, std::min<int64_t>((g.S + 255) / 256, 1024));
+    hipLaunchKernelGGL(lag_scale_kernel, dim3(oblocks), dim3(256), 0, stream, g, 1.0 / ((double)g.P * (double)nprobes), (const double2*)acc,
+                       (double2*)out);
+    EFGP_HIP_CHECK(hipGetLastError());
+    return EFGP_OK;
+}
 
 extern "C" {
 
@@ -247,28 +344,7 @@ int efgp_lag_sums(int device, int dim, int64_t mtot, const void* gamma, const do
         EFGP_HIP_CHECK(hipGetLastError());
         return EFGP_OK;
     }
-    // probes are processed in slabs so that the padded transforms stay within ~256 MB of scratch
-    const int64_t per = std::max<int64_t>(1, std::min<int64_t>(nprobes, ((int64_t)256 << 20) / (int64_t)(2 * g.P * sizeof(double2))));
-    double2* pad = (double2*)scratch(ctx, SLOT_TOEP_PAD, (size_t)(2 * per + 1) * g.P * sizeof(double2));
-    if (!pad) return EFGP_ENOMEM;
-    double2* acc = pad + (int64_t)2 * per * g.P;
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((g.P + 255) / 256, 1024));
-    for (int64_t j0 = 0; j0 < nprobes; j0 += per) {
-        const int J = (int)std::min<int64_t>(per, nprobes - j0);
-        hipLaunchKernelGGL(lag_pad_kernel, dim3(blocks, J), dim3(256), 0, stream, g, (const double2*)gamma + j0 * g.M, eta + j0 * g.M, pad);
-        EFGP_HIP_CHECK(hipGetLastError());
-        int rc = fft_c2c(ctx, dim, sizes, 2 * J, pad, true, stream);
-        if (rc != EFGP_OK) return rc;
-        hipLaunchKernelGGL(lag_mul_sum_kernel, dim3(blocks), dim3(256), 0, stream, g.P, J, (const double2*)pad, acc, j0 > 0 ? 1 : 0);
-        EFGP_HIP_CHECK(hipGetLastError());
-    }
-    int rc = fft_c2c(ctx, dim, sizes, 1, acc, false, stream);
-    if (rc != EFGP_OK) return rc;
-    const int oblocks = (int)std::max<int64_t>(1, std::min<int64_t>((g.S + 255) / 256, 1024));
-    hipLaunchKernelGGL(lag_scale_kernel, dim3(oblocks), dim3(256), 0, stream, g, 1.0 / ((double)g.P * (double)nprobes), (const double2*)acc,
-                       (double2*)out);
-    EFGP_HIP_CHECK(hipGetLastError());
-    return EFGP_OK;
+    return lag_sums_general(ctx, g, dim, sizes, gamma, eta, nprobes, out, stream);
 }
 
 int efgp_hermitian_normal_rows(int device, uint64_t seed, int64_t index_offset, int nrows, int64_t nmodes, double a, const void* ws,
@@ -335,6 +411,102 @@ int efgp_spectral_weights(int device, int kind, int dim, double nu, double lengt
     for (int a = 0; a < dim; ++a) M *= mtot;
     hipLaunchKernelGGL(spectral_weights_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, kind, dim, nu, lengthscale,
                        variance, c0, h, mtot, M, (double2*)ws, (double2*)dprime);
+    EFGP_HIP_CHECK(hipGetLastError());
+    return EFGP_OK;
+}
+
+// ---- per-axis grids: what the entries above do with one mtot and one h, with n_modes[a] and h[a] per axis ----------------------
+static bool axis_grid(int dim, const int64_t* n_modes, const double* h, AxisGrid* g) {
+    if (dim < 1 || dim > 3 || !n_modes) return false;
+    g->d = dim;
+    g->M = 1;
+    for (int a = 0; a < 3; ++a) {
+        g->n[a] = 1;
+        g->h[a] = 0.0;
+    }
+    for (int a = 0; a < dim; ++a) {
+        if (n_modes[a] < 1 || !(n_modes[a] & 1) || n_modes[a] > (1 << 20)) return false;
+        g->n[a] = (int)n_modes[a];
+        g->h[a] = h ? h[a] : 0.0;
+        g->M *= n_modes[a];
+    }
+    return true;
+}
+
+int efgp_lag_sums_nd(int device, int dim, const int64_t* n_modes, const void* gamma, const double* eta, int nprobes, void* out,
+                     void* stream_) {
+    EFGP_REQUIRE(dim >= 1 && dim <= 3 && n_modes, "efgp_lag_sums_nd: dim must be 1, 2 or 3 with a mode count per axis");
+    EFGP_REQUIRE(nprobes >= 1, "efgp_lag_sums_nd: nprobes must be >= 1");
+    for (int a = 0; a < dim; ++a) EFGP_REQUIRE(n_modes[a] >= 1 && n_modes[a] <= (1 << 20), "efgp_lag_sums_nd: bad mode count on axis %d", a);
+    EFGP_REQUIRE(gamma && eta && out, "efgp_lag_sums_nd: null argument");
+    DeviceCtx* ctx = device_ctx(device);
+    if (!ctx) return EFGP_EHIP;
+    DeviceGuard guard(device, (hipStream_t)stream_);
+    LagGeom g;
+    g.d = dim;
+    g.M = 1;
+    g.S = 1;
+    g.P = 1;
+    int64_t sizes[3] = {1, 1, 1};
+    for (int a = 0; a < 3; ++a) {                 // right-aligned slots, as in efgp_lag_sums
+        const bool real = a >= 3 - dim;
+        const int64_t n = real ? n_modes[a - (3 - dim)] : 1;
+        g.n[a] = (int)n;
+        g.s[a] = real ? (int)(2 * n - 1) : 1;
+        g.p[a] = real ? lag_length(g.s[a]) : 1;
+        g.M *= g.n[a];
+        g.S *= g.s[a];
+        g.P *= g.p[a];
+    }
+    for (int a = 0; a < dim; ++a) sizes[a] = lag_length((int)(2 * n_modes[a] - 1));
+    return lag_sums_general(ctx, g, dim, sizes, gamma, eta, nprobes, out, (hipStream_t)stream_);
+}
+
+int efgp_variance_rhs_nd(int device, int dim, const int64_t* n_modes, const double* h, const double* x_new, int64_t npts, const void* ws,
+                         void* rhs, void* stream_) {
+    AxisGrid g;
+    EFGP_REQUIRE(h && axis_grid(dim, n_modes, h, &g) && npts >= 0, "efgp_variance_rhs_nd: bad sizes (odd mode counts, dim 1..3)");
+    if (npts == 0) return EFGP_OK;
+    EFGP_REQUIRE(x_new && ws && rhs, "efgp_variance_rhs_nd: null argument");
+    if (!device_ctx(device)) return EFGP_EHIP;
+    DeviceGuard guard(device, (hipStream_t)stream_);
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((g.M + 255) / 256, 256));
+    for (int64_t b0 = 0; b0 < npts; b0 += 65535) {
+        const int nb = (int)std::min<int64_t>(65535, npts - b0);
+        hipLaunchKernelGGL(variance_rhs_nd_kernel, dim3(blocks, nb), dim3(256), 0, (hipStream_t)stream_, g, x_new + b0 * dim,
+                           (const double2*)ws, (double2*)rhs + b0 * g.M);
+    }
+    EFGP_HIP_CHECK(hipGetLastError());
+    return EFGP_OK;
+}
+
+int efgp_variance_contract_nd(int device, int dim, const int64_t* n_modes, const double* h, const double* x_new, int64_t npts,
+                              const void* ws, const void* gamma, double* out, void* stream_) {
+    AxisGrid g;
+    EFGP_REQUIRE(h && axis_grid(dim, n_modes, h, &g) && npts >= 0, "efgp_variance_contract_nd: bad sizes (odd mode counts, dim 1..3)");
+    if (npts == 0) return EFGP_OK;
+    EFGP_REQUIRE(x_new && ws && gamma && out, "efgp_variance_contract_nd: null argument");
+    EFGP_REQUIRE(npts <= 0x7fffffff, "efgp_variance_contract_nd: too many points for one launch");
+    if (!device_ctx(device)) return EFGP_EHIP;
+    DeviceGuard guard(device, (hipStream_t)stream_);
+    hipLaunchKernelGGL(variance_contract_nd_kernel, dim3((unsigned)npts), dim3(256), 0, (hipStream_t)stream_, g, x_new, (const double2*)ws,
+                       (const double2*)gamma, out);
+    EFGP_HIP_CHECK(hipGetLastError());
+    return EFGP_OK;
+}
+
+int efgp_spectral_weights_nd(int device, int kind, int dim, double nu, const double* lengthscales, double variance, const double* h,
+                             const int64_t* n_modes, void* ws, void* dprime, void* stream_) {
+    EFGP_REQUIRE(ws, "efgp_spectral_weights_nd: null output");
+    ArdSpec k;
+    double hd;
+    int64_t M;
+    EFGP_REQUIRE(ard_spec(kind, dim, nu, lengthscales, variance, h, n_modes, &k, &hd, &M),
+                 "efgp_spectral_weights_nd: kind 0 | 1 (nu 1/2, 3/2, 5/2), dim 1..3, positive hypers and spacings, odd mode counts");
+    if (!device_ctx(device)) return EFGP_EHIP;
+    DeviceGuard guard(device, (hipStream_t)stream_);
+    hipLaunchKernelGGL(spectral_weights_nd_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, k, variance, hd, M,
+                       (double2*)ws, (double2*)dprime);
     EFGP_HIP_CHECK(hipGetLastError());
     return EFGP_OK;
 }

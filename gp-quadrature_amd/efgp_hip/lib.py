@@ -52,6 +52,8 @@ _SIGNATURES = {
     "efgp_points_bounds": (_I, [_VP, C.POINTER(_D), C.POINTER(_D)]),
     "efgp_points_attach_values": (_I, [_VP, _VP, _VP]),
     "efgp_nufft_create_on": (_I, [C.POINTER(_VP), _VP, C.POINTER(_D), _D, _D]),
+    "efgp_nufft_create_nd": (_I, [C.POINTER(_VP), _I, _I, _I64, _VP, C.POINTER(_D), C.POINTER(_D), _D]),
+    "efgp_nufft_create_on_nd": (_I, [C.POINTER(_VP), _VP, C.POINTER(_D), C.POINTER(_D), _D]),
     "efgp_nufft_type1": (_I, [_VP, _VP, _I, _I, _PI64, _I, _I, _VP, _VP]),
     "efgp_nufft_type1_rademacher": (_I, [_VP, C.c_uint64, _I64, _I, _PI64, _I, _VP, _VP]),
     "efgp_rademacher_fill": (_I, [_I, C.c_uint64, _I64, _I, _I64, _VP, _VP]),
@@ -76,6 +78,8 @@ _SIGNATURES = {
     "efgp_grid_bounds": (_I, [_I, _I, _D, _D, _D, _D, _D, _D, _D, _VP, _VP]),
     "efgp_spectral_weights_host": (_I, [_I, _I, _D, _D, _D, _D, _D, _I, _VP, _VP]),
     "efgp_spectral_weights": (_I, [_I, _I, _I, _D, _D, _D, _D, _D, _I, _VP, _VP, _VP]),
+    "efgp_spectral_weights_host_nd": (_I, [_I, _I, _D, C.POINTER(_D), _D, C.POINTER(_D), _PI64, _VP, _VP]),
+    "efgp_spectral_weights_nd": (_I, [_I, _I, _I, _D, C.POINTER(_D), _D, C.POINTER(_D), _PI64, _VP, _VP, _VP]),
     "efgp_gradient_prepare": (_I, [_I, _I64, _VP, _VP, _VP, _D, _VP, _VP, _VP]),
     "efgp_gradient_assemble": (_I, [_I, _I64, _I, _I, _I, _I, C.POINTER(_I), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _D, _D, _D, _D, _VP, _VP]),
     "efgp_gradient_step": (_I, [_VP, _I, _I, _I64, _VP, _VP, _D, _I, _I, _D, _D, _D, _D, _D, _D, _D, _D, _I, _I, C.c_uint64, C.c_uint64,
@@ -89,6 +93,9 @@ _SIGNATURES = {
     "efgp_lag_sums": (_I, [_I, _I, _I64, _VP, _VP, _I, _VP, _VP]),
     "efgp_variance_rhs": (_I, [_I, _I, _I64, _D, _VP, _I64, _VP, _VP, _VP]),
     "efgp_variance_contract": (_I, [_I, _I, _I64, _D, _VP, _I64, _VP, _VP, _VP, _VP]),
+    "efgp_lag_sums_nd": (_I, [_I, _I, _PI64, _VP, _VP, _I, _VP, _VP]),
+    "efgp_variance_rhs_nd": (_I, [_I, _I, _PI64, C.POINTER(_D), _VP, _I64, _VP, _VP, _VP]),
+    "efgp_variance_contract_nd": (_I, [_I, _I, _PI64, C.POINTER(_D), _VP, _I64, _VP, _VP, _VP, _VP]),
     "efgp_hermitian_normal_rows": (_I, [_I, C.c_uint64, _I64, _I, _I64, _D, _VP, _VP, _D, _VP, _VP]),
     "efgp_pg_estep_update": (_I, [_I, _I64, _I, _VP, _VP, C.c_uint64, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
     "efgp_pg_nb_estep_update": (_I, [_I, _I64, _I, _VP, _VP, C.c_uint64, _VP, _D, _D, _VP, _VP, _VP, _VP, _VP, _VP]),

@@ -100,6 +100,15 @@ def normal_row_offset(first_row, index_offset=0):
     return _wrap_i64(int(index_offset) + (int(first_row) // 2) * NORMAL_ROW_STRIDE)
 
 
+def _per_axis(v):
+    """None for one number (Python or numpy scalar, 0-dim tensor), else the values of a sequence / array / tensor as a tuple."""
+    if torch.is_tensor(v):
+        return None if v.ndim == 0 else tuple(v.reshape(-1).tolist())
+    if hasattr(v, "__len__"):
+        return tuple(v.tolist()) if hasattr(v, "tolist") else tuple(v)
+    return None
+
+
 def _i64(vals):
     return (C.c_int64 * len(vals))(*[int(v) for v in vals])
 
@@ -148,7 +157,8 @@ class PointSet:
 
 class NufftPlan:
     """Type-1 / type-2 transforms for a fixed point set (C ABI: efgp_nufft_*).  With `points` (a PointSet over the
-    same x) the plan is made on the model's layout (efgp_nufft_create_on)."""
+    same x) the plan is made on the model's layout (efgp_nufft_create_on).  `h`: one grid spacing, or a sequence of d for a
+    per-axis grid (efgp_nufft_create_nd / efgp_nufft_create_on_nd)."""
 
     def __init__(self, x, h, tol, xcen=None, points=None):
         assert x.is_cuda and x.dtype == _RD and x.ndim == 2 and x.is_contiguous()
@@ -156,7 +166,11 @@ class NufftPlan:
         self.points = points          # the layout must outlive the plan
         self.dev = x.device
         self.npts, self.dim = x.shape
-        self.h = float(h)
+        hv = _per_axis(h)
+        per_axis = hv is not None
+        self.h = tuple(float(v) for v in hv) if per_axis else float(h)
+        if per_axis and len(self.h) != self.dim:
+            raise ValueError(f"NufftPlan: {len(self.h)} spacings for {self.dim}-dimensional points")
         self.tol = float(tol)
         xc = None
         if xcen is not None:
@@ -166,6 +180,14 @@ class NufftPlan:
         self._h = C.c_void_p()
         if points is not None:
             assert points.x.data_ptr() == x.data_ptr() and points.npts == self.npts
+        if per_axis:
+            hs = (C.c_double * self.dim)(*self.h)
+            if points is not None:
+                check(lib().efgp_nufft_create_on_nd(C.byref(self._h), points._h, xc, hs, self.tol), "efgp_nufft_create_on_nd")
+            else:
+                check(lib().efgp_nufft_create_nd(C.byref(self._h), self.dev.index, self.dim, self.npts, _ptr(x), xc, hs, self.tol),
+                      "efgp_nufft_create_nd")
+        elif points is not None:
             check(lib().efgp_nufft_create_on(C.byref(self._h), points._h, xc, self.h, self.tol), "efgp_nufft_create_on")
         else:
             check(lib().efgp_nufft_create(C.byref(self._h), self.dev.index, self.dim, self.npts, _ptr(x), xc,
@@ -651,9 +673,26 @@ def lanczos(op, ws, sigmasq, variant, z, steps):
     return alpha, beta, norm2, taken
 
 
+def _f64(vals):
+    return (C.c_double * len(vals))(*[float(v) for v in vals])
+
+
 def lag_sums(gamma, eta, mtot, dim):
-    """c[r] = mean_j sum_{k-l=r} gamma[j,k] eta[j,l] on the (2 mtot - 1)^d lag box in FFT order (efgp_lag_sums)."""
+    """c[r] = mean_j sum_{k-l=r} gamma[j,k] eta[j,l] on the (2 mtot - 1)^d lag box in FFT order (efgp_lag_sums); `mtot` a sequence
+    of d mode counts: the box (2 mtot[a] - 1) per axis (efgp_lag_sums_nd)."""
     dev = gamma.device
+    if _per_axis(mtot) is not None:
+        shape = tuple(int(n) for n in _per_axis(mtot))
+        if len(shape) != int(dim):
+            raise ValueError(f"lag_sums: {len(shape)} mode counts for dimension {dim}")
+        M = math.prod(shape)
+        gg = gamma.reshape(-1, M).to(_CD).contiguous()
+        ee = _dc(eta.reshape(-1, M), dev, _RD)
+        out = torch.empty(tuple(2 * n - 1 for n in shape), dtype=_CD, device=dev)
+        with _on(dev):
+            check(lib().efgp_lag_sums_nd(dev.index, int(dim), _i64(shape), _ptr(gg), _ptr(ee), gg.shape[0], _ptr(out), _stream(dev)),
+                  "efgp_lag_sums_nd")
+        return out
     M = int(mtot) ** int(dim)
     gg = gamma.reshape(-1, M).to(_CD).contiguous()
     ee = _dc(eta.reshape(-1, M), dev, _RD)
@@ -665,20 +704,29 @@ def lag_sums(gamma, eta, mtot, dim):
 
 
 def variance_rhs(x_new, h, mtot, ws):
-    """rhs[b, k] = ws[k] conj(f_k(x*_b)) for the 'regular' variance solves (efgp_variance_rhs)."""
+    """rhs[b, k] = ws[k] conj(f_k(x*_b)) for the 'regular' variance solves (efgp_variance_rhs); `h` and `mtot` sequences of d:
+    the per-axis grid (efgp_variance_rhs_nd)."""
     dev = ws.device
     xn = _dc(x_new, dev, _RD)
     B, d = xn.shape
     wsd = ws.to(_CD).contiguous()
     out = torch.empty((B, wsd.numel()), dtype=_CD, device=dev)
     with _on(dev):
-        check(lib().efgp_variance_rhs(dev.index, d, int(mtot), float(h), _ptr(xn), B, _ptr(wsd), _ptr(out), _stream(dev)),
-              "efgp_variance_rhs")
+        if _per_axis(mtot) is None:
+            check(lib().efgp_variance_rhs(dev.index, d, int(mtot), float(h), _ptr(xn), B, _ptr(wsd), _ptr(out), _stream(dev)),
+                  "efgp_variance_rhs")
+        else:
+            mtot, h = _per_axis(mtot), _per_axis(h) or ()
+            if len(mtot) != d or len(h) != d or math.prod(int(n) for n in mtot) != wsd.numel():
+                raise ValueError("variance_rhs: per-axis h and mode counts must match the points and ws")
+            check(lib().efgp_variance_rhs_nd(dev.index, d, _i64(mtot), _f64(h), _ptr(xn), B, _ptr(wsd), _ptr(out), _stream(dev)),
+                  "efgp_variance_rhs_nd")
     return out
 
 
 def variance_contract(x_new, h, mtot, ws, gamma):
-    """s^2[b] = max(0, Re sum_k f_k(x*_b) ws[k] gamma[b, k]) (efgp_variance_contract)."""
+    """s^2[b] = max(0, Re sum_k f_k(x*_b) ws[k] gamma[b, k]) (efgp_variance_contract; per-axis `h`, `mtot`:
+    efgp_variance_contract_nd)."""
     dev = ws.device
     xn = _dc(x_new, dev, _RD)
     B, d = xn.shape
@@ -686,9 +734,45 @@ def variance_contract(x_new, h, mtot, ws, gamma):
     gg = gamma.reshape(B, -1).to(_CD).contiguous()
     out = torch.empty(B, dtype=_RD, device=dev)
     with _on(dev):
-        check(lib().efgp_variance_contract(dev.index, d, int(mtot), float(h), _ptr(xn), B, _ptr(wsd), _ptr(gg), _ptr(out),
-                                           _stream(dev)), "efgp_variance_contract")
+        if _per_axis(mtot) is None:
+            check(lib().efgp_variance_contract(dev.index, d, int(mtot), float(h), _ptr(xn), B, _ptr(wsd), _ptr(gg), _ptr(out),
+                                               _stream(dev)), "efgp_variance_contract")
+        else:
+            mtot, h = _per_axis(mtot), _per_axis(h) or ()
+            if len(mtot) != d or len(h) != d or math.prod(int(n) for n in mtot) != wsd.numel() or gg.shape[1] != wsd.numel():
+                raise ValueError("variance_contract: per-axis h and mode counts must match the points, ws and gamma")
+            check(lib().efgp_variance_contract_nd(dev.index, d, _i64(mtot), _f64(h), _ptr(xn), B, _ptr(wsd), _ptr(gg), _ptr(out),
+                                                  _stream(dev)), "efgp_variance_contract_nd")
     return out
+
+
+def spectral_weights_nd(dev, kind, nu, lengthscales, variance, hs, shape, want_grad=False):
+    """(ws (M,), dprime (M, d + 1) or None) of an ARD kernel on the per-axis grid, complex128 on `dev`, in one launch
+    (efgp_spectral_weights_nd)."""
+    d = len(shape)
+    if len(lengthscales) != d or len(hs) != d:
+        raise ValueError("spectral_weights_nd: one lengthscale, spacing and mode count per axis")
+    M = math.prod(int(n) for n in shape)
+    ws = torch.empty(M, dtype=_CD, device=dev)
+    dp = torch.empty((M, d + 1), dtype=_CD, device=dev) if want_grad else None
+    with _on(dev):
+        check(lib().efgp_spectral_weights_nd(dev.index, int(kind), d, float(nu), _f64(lengthscales), float(variance), _f64(hs),
+                                             _i64(shape), _ptr(ws), _ptr(dp) if want_grad else None, _stream(dev)),
+              "efgp_spectral_weights_nd")
+    return ws, dp
+
+
+def spectral_weights_host_nd(kind, nu, lengthscales, variance, hs, shape, want_grad=False):
+    """The host twin (efgp_spectral_weights_host_nd): CPU complex128 tensors, no device involved."""
+    d = len(shape)
+    if len(lengthscales) != d or len(hs) != d:
+        raise ValueError("spectral_weights_host_nd: one lengthscale, spacing and mode count per axis")
+    M = math.prod(int(n) for n in shape)
+    ws = torch.empty(M, dtype=_CD)
+    dp = torch.empty((M, d + 1), dtype=_CD) if want_grad else None
+    check(lib().efgp_spectral_weights_host_nd(int(kind), d, float(nu), _f64(lengthscales), float(variance), _f64(hs), _i64(shape),
+                                              _ptr(ws), _ptr(dp) if want_grad else None), "efgp_spectral_weights_host_nd")
+    return ws, dp
 
 
 def pg_estep_update(s_rows, delta, targets, rho, *, probes=None, seed=0, pg_b=None):

@@ -30,10 +30,11 @@ from torch.optim import Adam
 
 from cg import ConjugateGradients
 from kernels.kernel_params import GPParams
-from utils.kernels import get_xis
+from utils.kernels import get_xis, get_xis_nd
 
-from efgp_hip import NufftPlan, PointSet, ToeplitzOp, lanczos, lag_sums, variance_rhs, variance_contract, cg_solve, cg_solve_lazy, cg_solve_mean_async, cg_solve_mean_fused, vdot_real, compute_device, rademacher_fill, gradient_prepare, gradient_assemble, hermitian_normal_rows, normal_row_offset
+from efgp_hip import NufftPlan, PointSet, ToeplitzOp, lanczos, lag_sums, variance_rhs, variance_contract, cg_solve, cg_solve_lazy, cg_solve_mean_async, cg_solve_mean_fused, vdot_real, compute_device, rademacher_fill, gradient_prepare, gradient_assemble, hermitian_normal_rows, normal_row_offset, spectral_weights_nd
 from efgp_hip.dist import PointShards
+from efgp_hip.ops import _per_axis
 
 TWO_PI = 2.0 * math.pi
 _CONV_TOL = 6e-8       # tolerance the reference hard-codes for the Toeplitz vector (efgpnd.py:1418)
@@ -116,7 +117,7 @@ class NUFFT:
         self.dtype = x.dtype
         self.cdtype = cdtype or _cmplx(self.dtype)
         self.eps = eps
-        self._hval = float(h)
+        self._hval = tuple(float(v) for v in _per_axis(h)) if _per_axis(h) is not None else float(h)      # per-axis spacings: a sequence of d
         x2 = _as2d(x)
         self.d = x2.shape[1]
         if torch.is_tensor(xcen):
@@ -136,7 +137,8 @@ class NUFFT:
     def phi(self) -> torch.Tensor:
         """(d,N) phases, as the reference exposes them (efgpnd.py:1451)."""
         xc = torch.tensor(self._xcen, dtype=self._x_ref.dtype, device=self._x_ref.device)
-        return (TWO_PI * self._hval * (self._x_ref - xc)).T.contiguous().to(device=self.device, dtype=self.dtype)
+        hv = torch.tensor(self._hval, dtype=self._x_ref.dtype, device=self._x_ref.device) if isinstance(self._hval, tuple) else self._hval
+        return (TWO_PI * hv * (self._x_ref - xc)).T.contiguous().to(device=self.device, dtype=self.dtype)
 
     # device-level entry points (cuda tensors in, cuda complex128 out) used inside this module
     def _type1_dev(self, vals, out_shape):
@@ -352,13 +354,29 @@ class _Grid:
         so what the host does before the first big launch is dead time on the device: ~35 us of a 0.4-ms step).
         trunc_eps: tolerance of the frequency truncation when it differs from `eps` (get_xis; the PG classifier passes its
         spectral_eps and trunc_eps separately, pg_classifier.py:326-333); None keeps trunc_eps = eps."""
-        xis_1d, h, mtot = get_xis(kernel_obj=kernel, eps=eps, L=L, use_integral=True, l2scaled=False, trunc_eps=trunc_eps)
-        self.h = float(h)
-        self.mtot = int(mtot)
+        self.ard = hasattr(kernel, "ard_kind")
         self.d = d
-        self.shape = (self.mtot,) * d
-        self.M = self.mtot ** d
-        self.xis_1d = xis_1d
+        if self.ard:
+            # one lengthscale per axis (kernels/ard.py): a spacing and a mode count per axis, L = the d sides of the bounding box
+            if not isinstance(L, (tuple, list)):
+                raise ValueError(f"{type(kernel).__name__} needs the box side of every axis, got one length")
+            self.hs, self.shape = get_xis_nd(kernel, eps, L, trunc_eps=trunc_eps)
+            self.h = self.mtot = None       # scalars of the isotropic grid only; `hs` / `shape` describe every grid
+            self.plan_h = self.hs
+            self.M = prod(self.shape)
+            self.hprod = prod(self.hs)
+            self.xis_axes = [torch.arange(-(n // 2), n // 2 + 1, dtype=torch.float64) * hj for hj, n in zip(self.hs, self.shape)]
+        else:
+            xis_1d, h, mtot = get_xis(kernel_obj=kernel, eps=eps, L=L, use_integral=True, l2scaled=False, trunc_eps=trunc_eps)
+            self.h = float(h)
+            self.mtot = int(mtot)
+            self.hs = (self.h,) * d
+            self.shape = (self.mtot,) * d
+            self.M = self.mtot ** d
+            self.hprod = self.h ** d
+            self.plan_h = self.h            # what a NufftPlan takes: one spacing here, the d spacings of an ARD grid
+            self.xis_1d = xis_1d
+            self.xis_axes = [xis_1d] * d
         self._xis = None                                                         # (M,d) host float64, built on first use
         # Non-blocking uploads where the whole solve is one launch (circulant grid small enough for the persistent kernel:
         # F^d <= 4096 with F = next_pow2(2 mtot - 1)) -- that is where the host running ahead pays (launch gaps of the
@@ -366,8 +384,7 @@ class _Grid:
         # (with torch's CPU pool capped, EFGP_ASYNC_UPLOAD_ALL=1 measures 7.11 vs 7.28 ms on the 3-D 64^3 fit and no
         # difference at 2-D 256^2; with an uncapped pool under a CPU quota the host running ahead made the throttling
         # stalls of efgp_hip/cpu_quota.py appear there too, so the conservative choice stays the default).
-        F = 1 << (2 * self.mtot - 2).bit_length()
-        async_ok = F ** d <= 4096 or bool(os.environ.get("EFGP_ASYNC_UPLOAD_ALL"))
+        async_ok = prod(1 << (2 * n - 2).bit_length() for n in self.shape) <= 4096 or bool(os.environ.get("EFGP_ASYNC_UPLOAD_ALL"))
         up = _upload if async_ok else (lambda t, dv: t.to(dv))
         self.dprime = None
         self.ws = None
@@ -404,14 +421,14 @@ class _Grid:
                 float((Sf - Sf.flip(0)).abs().max()) > 1e-12 * float(Sf.abs().max()):
             raise ValueError(f"{type(kernel).__name__}.spectral_density must be finite, non-negative and even (S(-xi) = S(xi)) on "
                              "the frequency grid: it is the spectral density of a real stationary kernel")
-        self.ws = up(torch.sqrt(S.to(torch.complex128) * self.h ** d), dev)       # (M,) complex, imag 0
+        self.ws = up(torch.sqrt(S.to(torch.complex128) * self.hprod), dev)       # (M,) complex, imag 0
         if want_grad:
-            self.dprime = up((self.h ** d * kernel.spectral_grad(where)).to(torch.complex128), dev)   # (M,H)
+            self.dprime = up((self.hprod * kernel.spectral_grad(where)).to(torch.complex128), dev)   # (M,H)
 
     @property
     def xis(self):
         if self._xis is None:
-            mesh = torch.meshgrid(*(self.xis_1d for _ in range(self.d)), indexing="ij")
+            mesh = torch.meshgrid(*self.xis_axes, indexing="ij")
             self._xis = torch.stack(mesh, dim=-1).view(-1, self.d)
         return self._xis
 
@@ -419,6 +436,15 @@ class _Grid:
         """(ws, dprime) as device tensors from ONE launch (efgp_spectral_weights) for the built-in kernels, else None."""
         if os.environ.get("EFGP_NO_NATIVE_GRID") or self.M > (1 << 24) or torch.device(dev).type != "cuda":
             return None
+        if self.ard:
+            # ws and the d + 1 derivative rows of an ARD kernel in one launch (efgp_spectral_weights_nd)
+            if not 1 <= self.d <= 3:
+                return None
+            dev = torch.device(dev)
+            if dev.index is None:
+                dev = torch.device("cuda", torch.cuda.current_device())
+            vals = kernel.get_hypers()
+            return spectral_weights_nd(dev, kernel.ard_kind, kernel.nu, vals[:-1], vals[-1], self.hs, self.shape, want_grad=want_grad)
         bk = _builtin_kernel_constants(kernel)
         if bk is None:
             return None
@@ -458,6 +484,8 @@ def _gradient_one_call(kernel, grid, xd, yd, points, sig, N, cg_tol, early_stopp
     """The whole adjoint-estimator step in one library call (efgp_hip.gradient_step) when it applies: built-in kernel, one GPU,
     generated probes, a circulant grid whose solves are single launches.  Returns what `_gradient_tail_native` returns, or None
     (nothing enqueued that matters) and the caller drives the entry points itself."""
+    if grid.ard:                       # the one-call step evaluates the isotropic weights itself
+        return None
     key = (dev.index, grid.d, grid.mtot)
     F = 1 << (2 * grid.mtot - 2).bit_length()
     if key in _NO_ONE_CALL_STEP or F ** grid.d > 4096 or os.environ.get("EFGP_NO_GRADIENT_STEP") or os.environ.get("EFGP_NO_NATIVE_GRID"):
@@ -490,10 +518,16 @@ def _domain_length(xd: torch.Tensor, shards: PointShards) -> float:
     return float((hi - lo).max())
 
 
+def _domain_sides(xd: torch.Tensor, shards: PointShards):
+    """Side of the bounding box per axis (the per-axis grids of the ARD kernels), from the same all-reduced min / max."""
+    lo, hi = torch.aminmax(xd, dim=0)
+    lo, hi = shards.minmax(lo, hi)
+    return [float(v) for v in (hi - lo).tolist()]
+
+
 def _normal_equations(plan: NufftPlan, yd, grid: _Grid, shards: PointShards):
     """(F*y (M,), Toeplitz vector v ((4m+1,)*d)) in one pass over the points, all-reduced over shards."""
-    m = (grid.mtot - 1) // 2
-    Fy, v = plan.type1_pair(yd, grid.shape, (4 * m + 1,) * grid.d)
+    Fy, v = plan.type1_pair(yd, grid.shape, tuple(2 * n - 1 for n in grid.shape))      # 2 n - 1 = 4 m + 1 lags per axis
     shards.sum_many_([Fy, v])
     return Fy.reshape(-1), v
 
@@ -518,7 +552,7 @@ def efgpnd_gradient_batched(
         do_profiling=False, compute_log_marginal=False,
         noise_floor: Optional[float] = None,
         stats_out: Optional[Dict[str, float]] = None,
-        mean_cg_init: Optional[torch.Tensor] = None,
+        mean_cg_init: Optional[torch.Tensor] = None, mean_cg_init_shape=None,
         use_mean_cg_preconditioner: bool = True,
         use_trace_cg_preconditioner: bool = True,
         log_marginal_probes=100, log_marginal_steps=25,
@@ -585,7 +619,9 @@ def efgpnd_gradient_batched(
                 "trace_cg_iters": trace_iters,
                 "trace_num_rhs": int(n_rhs),
                 "feature_count": int(M),
-                "mtot": int(grid.mtot),
+                **({} if grid.ard else {"mtot": grid.mtot}),
+                "shape": tuple(grid.shape),
+                "hs": tuple(grid.hs),
                 "trace_samples": int(trace_samples),
                 "mean_cg_warm_start_used": bool(warm),
                 "mean_cg_preconditioned": bool(use_mean_cg_preconditioner),
@@ -628,7 +664,11 @@ def efgpnd_gradient_batched(
     yd = y.detach().to(device=dev, dtype=torch.float64).contiguous()
     N_local, d = xd.shape
     N = int(shards.sum_scalars([N_local], dev)[0]) if shards.active else N_local
-    L = float(domain_length) if domain_length is not None else _domain_length(xd, shards)
+    if hasattr(kernel, "ard_kind"):
+        L = [float(v) for v in domain_length] if domain_length is not None else _domain_sides(xd, shards)
+        L = [v if v > 1e-9 else 1.0 for v in L]
+    else:
+        L = float(domain_length) if domain_length is not None else _domain_length(xd, shards)
     sig = float(sigmasq.detach()) if torch.is_tensor(sigmasq) else float(sigmasq)
     if noise_floor is not None:
         sig = max(sig, float(noise_floor))
@@ -641,6 +681,8 @@ def efgpnd_gradient_batched(
     # 1) frequency grid -----------------------------------------------------------------------
     grid = _Grid(kernel, eps, L, d, dev, want_grad=True, defer_weights=True)
     M = grid.M
+    if mean_cg_init_shape is not None and tuple(mean_cg_init_shape) != tuple(grid.shape):
+        mean_cg_init = None                   # a start vector of another block with the same mode count is no warm start
     lap("1_frequency_grid_setup")
 
     # 2) NUFFT plan ---------------------------------------------------------------------------
@@ -667,8 +709,8 @@ def efgpnd_gradient_batched(
         for name in ("4_solve_cg", "5_compute_term2", "6_monte_carlo_trace", "7_batch_cg_solve", "7.5_compute_alpha", "8_gradient_calculation"):
             lap(name)
         return finish()
-    plan = NufftPlan(xd, grid.h, tight, points=points)
-    plan_p = plan if (not nufft_eps or float(nufft_eps) <= tight) else NufftPlan(xd, grid.h, float(nufft_eps), points=points)
+    plan = NufftPlan(xd, grid.plan_h, tight, points=points)
+    plan_p = plan if (not nufft_eps or float(nufft_eps) <= tight) else NufftPlan(xd, grid.plan_h, float(nufft_eps), points=points)
     lap("2_nufft_setup")
 
     # 3) Toeplitz operator, Jacobi diagonal (F*y rides in the same pass over the points) --------
@@ -926,14 +968,18 @@ def _unwrap_operator(A_apply):
     raise TypeError("expected an operator made by create_A_mean / create_A_var")
 
 
-def diag_sums_nd(A_apply, J, xis_flat, max_cg_iter, cg_tol, ws, probes: Optional[torch.Tensor] = None, shards=None):
+def diag_sums_nd(A_apply, J, xis_flat, max_cg_iter, cg_tol, ws, probes: Optional[torch.Tensor] = None, shards=None, shape=None):
     """Hutchinson estimate of the lag sums c[r] = sum_{k-l=r} (A^-1)_{kl}-weighted products used by the
     stochastic variance (reference: efgpnd.py:1634-1664).  ``probes`` (J,M) of +-1 may be injected;
     otherwise they are drawn with torch.randint as in the reference (:1644).  ``shards`` (a PointShards of a multi-GPU
-    model; the probes must then be identical on all ranks): the J systems are split by rows over the ranks."""
-    Mtot, d_loc = xis_flat.shape
-    m_loc = round(Mtot ** (1 / d_loc))
-    assert m_loc ** d_loc == Mtot, "xis must lie on tensor grid"
+    model; the probes must then be identical on all ranks): the J systems are split by rows over the ranks.  ``shape``: the mode
+    count per axis of a per-axis grid (then ``xis_flat`` is not looked at); the lag box is (2 n_a - 1) per axis."""
+    if shape is not None:
+        m_loc, d_loc, Mtot = tuple(int(n) for n in shape), len(shape), prod(shape)
+    else:
+        Mtot, d_loc = xis_flat.shape
+        m_loc = round(Mtot ** (1 / d_loc))
+        assert m_loc ** d_loc == Mtot, "xis must lie on tensor grid"
     op = _unwrap_operator(A_apply)
     dev = op.toeplitz._dev
     if probes is None:
@@ -1020,9 +1066,10 @@ def logdet_slq(ws, sigma2, toeplitz, *, probes=1000, steps=100, dtype=torch.floa
 
 
 def compute_prediction_variance(x_new, xis, ws, A_var, cg_tol, max_cg_iter, variance_method, h, xcen,
-                                hutchinson_probes, nufft_eps, device, rdtype, cdtype, probes=None, shards=None):
+                                hutchinson_probes, nufft_eps, device, rdtype, cdtype, probes=None, shards=None, shape=None):
     """Latent posterior variance at x_new: 'regular' (one CG solve per point, microbatched) or
-    'stochastic' (Hutchinson lag sums + FFT-ordered type-2).  Reference: efgpnd.py:1761-1841."""
+    'stochastic' (Hutchinson lag sums + FFT-ordered type-2).  Reference: efgpnd.py:1761-1841.
+    ``shape`` with ``h`` a sequence: the per-axis grid of an ARD kernel (mode count and spacing per axis)."""
     method = variance_method.lower()
     if method == "regular":
         op = _unwrap_operator(A_var)
@@ -1030,9 +1077,13 @@ def compute_prediction_variance(x_new, xis, ws, A_var, cg_tol, max_cg_iter, vari
         wsd = ws.to(device=dev, dtype=torch.complex128)
         xn = x_new.to(device=dev, dtype=torch.float64)
         M_loc = wsd.numel()
-        mtot_loc = round(M_loc ** (1.0 / xn.shape[1]))
-        assert mtot_loc ** xn.shape[1] == M_loc, "ws must lie on the tensor grid"
-        hval = float(h)
+        if shape is not None:
+            mtot_loc, hval = tuple(int(n) for n in shape), tuple(float(v) for v in h)
+            assert prod(mtot_loc) == M_loc, "ws must lie on the per-axis grid"
+        else:
+            mtot_loc = round(M_loc ** (1.0 / xn.shape[1]))
+            assert mtot_loc ** xn.shape[1] == M_loc, "ws must lie on the tensor grid"
+            hval = float(h)
         out = []
         for xb in torch.split(xn, 8192, dim=0):
             rhs = variance_rhs(xb, hval, mtot_loc, wsd)                  # ws * conj(f(x*)): explicit feature rows (b, M)
@@ -1043,7 +1094,7 @@ def compute_prediction_variance(x_new, xis, ws, A_var, cg_tol, max_cg_iter, vari
         return torch.cat(out, dim=0).to(device=device, dtype=rdtype)
     if method == "stochastic":
         t1 = time.time()
-        est = diag_sums_nd(A_var, hutchinson_probes, xis, max_cg_iter, cg_tol, ws, probes=probes, shards=shards)
+        est = diag_sums_nd(A_var, hutchinson_probes, xis, max_cg_iter, cg_tol, ws, probes=probes, shards=shards, shape=shape)
         print(f"Time to compute diag sums: {time.time() - t1:.4f} seconds")
         return nufft_var_est_nd(est, h, xcen, x_new, nufft_eps).to(device=device, dtype=rdtype)
     raise ValueError(f"Variance method '{variance_method}' not implemented. Choose 'regular' or 'stochastic'.")
@@ -1229,6 +1280,8 @@ class EFGPND(nn.Module):
             L = _domain_length(xd, self._shards)
             if L <= 1e-9:
                 L = 1.0
+            if hasattr(self.kernel, "ard_kind"):        # a grid axis per box side (same all-reduced min / max)
+                L = [v if v > 1e-9 else 1.0 for v in _domain_sides(xd, self._shards)]
             n_glob = int(self._shards.sum_scalars([xd.shape[0]], dev)[0]) if self._shards.active else xd.shape[0]
             yy = self._shards.sum_scalars([vdot_real(yd, yd)], dev)[0]          # global sum of y^2 (gradient, once)
             self._devdata = dict(dev=dev, x=xd, y=yd, L=L, N=n_glob, yy=yy, points=None, passes=0)
@@ -1271,13 +1324,14 @@ class EFGPND(nn.Module):
             dd["x"], dd["y"], sigmasq=self._gp_params.host_pos()[-1], kernel=self.kernel, eps=self.eps,
             trace_samples=trace_samples, do_profiling=do_profiling, nufft_eps=nufft_eps, cg_tol=cg_tol,
             noise_floor=noise_floor, stats_out=stats,
-            mean_cg_init=self._last_gradient_beta if warm else None,
+            mean_cg_init=self._last_gradient_beta if warm else None, mean_cg_init_shape=getattr(self, "_last_gradient_shape", None),
             use_mean_cg_preconditioner=self.opts.get("mean_cg_preconditioner", True),
             use_trace_cg_preconditioner=self.opts.get("trace_cg_preconditioner", True),
             compute_log_marginal=compute_log_marginal, log_marginal_probes=log_marginal_probes,
             log_marginal_steps=log_marginal_steps, shards=self._shards, domain_length=dd["L"], y_norm_sq=dd["yy"],
             points=self._layout(), **kwargs)
         self._last_gradient_beta = stats.pop("mean_beta", None)
+        self._last_gradient_shape = tuple(stats["shape"]) if "shape" in stats else None
         grad_host = stats.pop("grad_host", None)       # the native tail reads grad | term1 | term2 back in one copy
         self._last_gradient_stats = stats
         grads, log_marginal = res if compute_log_marginal else (res, None)
@@ -1309,14 +1363,15 @@ class EFGPND(nn.Module):
         cdtype = _cmplx(rdtype)
 
         grid = _Grid(self.kernel, self.eps, dd["L"], d, dev, defer_weights=True)
-        warm = self.opts.get("mean_cg_warm_start", True) and self._beta is not None and tuple(self._beta.shape) == (grid.M,)
+        warm = self.opts.get("mean_cg_warm_start", True) and self._beta is not None and tuple(self._beta.shape) == (grid.M,) \
+            and (self._fit_state is None or tuple(self._fit_state["shape"]) == tuple(grid.shape))      # same block, not just the same M
         # Cold start of a built-in kernel on a 2-D grid: the weights may be made inside the mean solve (below); elsewhere they are
         # made now, ahead of the pass over the points
         bk = _builtin_kernel_constants(self.kernel) if (d == 2 and not warm and dev.type == "cuda" and
                                                         not os.environ.get("EFGP_NO_NATIVE_GRID")) else None
         if bk is None:
             grid.make_weights()
-        plan = NufftPlan(xd, grid.h, min(float(nufft_eps), _CONV_TOL), points=self._layout())
+        plan = NufftPlan(xd, grid.plan_h, min(float(nufft_eps), _CONV_TOL), points=self._layout())
         Fy, v = _normal_equations(plan, yd, grid, self._shards)
         # deferred: on the 48 x 48 Hermitian grids the operator launches nothing; the fused solve makes its spectrum
         toeplitz = ToeplitzND(v, force_pow2=True, defer_spectra=bk is not None)
@@ -1351,9 +1406,13 @@ class EFGPND(nn.Module):
         self._xis = (grid, rdtype)                 # the (M, d) node tensor is built when somebody asks for it (property below)
         self._ws = grid.ws.to(cdtype) if cdtype != torch.complex128 else grid.ws
         self._toeplitz = toeplitz
+        # h, mtot: the scalars of an isotropic grid (None for an ARD kernel); hs, shape, plan_h describe every grid
         self._fit_state = dict(h=grid.h, mtot=grid.mtot, d=d, sig=sig, ws=grid.ws, beta=beta,
-                               hypers=self._current_hypers(), Fy=Fy, v=v)
-        self._last_fit_stats = dict(mean_cg_iters=iters, mtot=grid.mtot, feature_count=grid.M, h=grid.h)
+                               hypers=self._current_hypers(), Fy=Fy, v=v, shape=grid.shape, hs=grid.hs, plan_h=grid.plan_h, ard=grid.ard)
+        if grid.ard:
+            self._last_fit_stats = dict(mean_cg_iters=iters, feature_count=grid.M, hs=grid.hs, shape=grid.shape)
+        else:
+            self._last_fit_stats = dict(mean_cg_iters=iters, mtot=grid.mtot, feature_count=grid.M, h=grid.h)
         self._fitted = True
         self._update_param_cache()
         # Nothing downstream reads the count before using beta: a solve that may hold a dead system is settled HERE -- last, behind
@@ -1370,7 +1429,8 @@ class EFGPND(nn.Module):
         if not torch.is_tensor(src):
             grid, rdtype = src
             xis = grid.xis.to(dtype=rdtype)
-            xis.h_float = grid.h
+            if not grid.ard:
+                xis.h_float = grid.h
             self.__dict__["_xis_src"] = src = xis
         return src
 
@@ -1403,14 +1463,14 @@ class EFGPND(nn.Module):
             raise ValueError(f"x_new has {d} columns, the model was built on {st['d']}")
         t0 = time.perf_counter()
         ranges = _StageRanges("EFGPND.predict", "predict_mean")
-        shape = (st["mtot"],) * d                       # carried explicitly (the reference re-derives it, :908)
+        shape = st["shape"]                             # carried explicitly (the reference re-derives it, :908)
         # the plan over x_new is kept while the same tensor (same storage, same version) comes back with the same grid:
         # predicting at the training points after every refit is the reference's own usage (efgpnd_ex.ipynb cell 23)
-        pkey = (xn.data_ptr(), tuple(xn.shape), xn._version, st["h"], float(nufft_eps))
+        pkey = (xn.data_ptr(), tuple(xn.shape), xn._version, st["plan_h"], float(nufft_eps))
         if self._predict_plan is not None and self._predict_plan[0] == pkey:
             plan = self._predict_plan[1]
         else:
-            plan = NufftPlan(xn, st["h"], float(nufft_eps))
+            plan = NufftPlan(xn, st["plan_h"], float(nufft_eps))
             self._predict_plan = (pkey, plan)
         mean = plan.type2(st["beta"], shape, real_only=True, mode_scale=st["ws"])     # F (ws * beta), efgpnd.py:919-922
         out_mean = mean.to(device=self.device, dtype=rdtype)
@@ -1425,9 +1485,10 @@ class EFGPND(nn.Module):
             var = compute_prediction_variance(
                 x_new=xn, xis=self._xis.to(torch.float64), ws=st["ws"], A_var=A_var,
                 cg_tol=self.opts.get("cg_tolerance", 1e-4), max_cg_iter=self.opts.get("max_cg_iterations", 1000),
-                variance_method=variance_method, h=st["h"], xcen=torch.zeros(d, dtype=torch.float64),
+                variance_method=variance_method, h=st["plan_h"], xcen=torch.zeros(d, dtype=torch.float64),
                 hutchinson_probes=hutchinson_probes, nufft_eps=nufft_eps, device=self.device, rdtype=rdtype,
-                cdtype=cdtype, probes=variance_probes, shards=self._shards if self._shards.active else None)
+                cdtype=cdtype, probes=variance_probes, shards=self._shards if self._shards.active else None,
+                shape=st["shape"] if st["ard"] else None)
         else:
             # the reference fills a (B,) tensor with NaN (efgpnd.py:947): same values as a stride-0 view of ONE NaN, without
             # writing 8 B bytes per call (16 us and 80 MB of traffic per predict at N = 1e7)
@@ -1501,12 +1562,12 @@ class EFGPND(nn.Module):
         dev = self._devdata["dev"]
         xn = _dev_points(x_new, dev)
         d, M = st["d"], st["ws"].numel()
-        shape = (st["mtot"],) * d
-        pkey = (xn.data_ptr(), tuple(xn.shape), xn._version, st["h"], float(self.nufft_eps))
+        shape = st["shape"]
+        pkey = (xn.data_ptr(), tuple(xn.shape), xn._version, st["plan_h"], float(self.nufft_eps))
         if self._predict_plan is not None and self._predict_plan[0] == pkey:
             plan_new = self._predict_plan[1]
         else:
-            plan_new = NufftPlan(xn, st["h"], float(self.nufft_eps))
+            plan_new = NufftPlan(xn, st["plan_h"], float(self.nufft_eps))
             self._predict_plan = (pkey, plan_new)
         seed_e1, seed_e2 = _derive_seed(seed, 1), _derive_seed(seed, 2)
         block = _SAMPLE_BLOCK[d]
@@ -1519,8 +1580,8 @@ class EFGPND(nn.Module):
             # replaces _fit_state; what the plan depends on is h)
             tol1 = min(float(self.nufft_eps), _CONV_TOL)
             sp = self._sample_plan
-            if sp is None or sp[0] != (st["h"], tol1) or sp[2] is not points:
-                self._sample_plan = sp = ((st["h"], tol1), NufftPlan(self._devdata["x"], st["h"], tol1, points=points), points)
+            if sp is None or sp[0] != (st["plan_h"], tol1) or sp[2] is not points:
+                self._sample_plan = sp = ((st["plan_h"], tol1), NufftPlan(self._devdata["x"], st["plan_h"], tol1, points=points), points)
             plan_x = sp[1]
             max_iter = int(self.opts.get("max_cg_iterations", 1000))
             diag = None
@@ -1586,11 +1647,15 @@ class EFGPND(nn.Module):
             raise ValueError(f"unknown sampling method {method!r}: 'dense' or 'efgp'")
         x = _as2d(self.x)
         xn = _as2d(x_new)
-        k = self.kernel.kernel
+        if hasattr(self.kernel, "ard_kind"):            # a function of the coordinate differences, not of the distance
+            km = self.kernel.kernel_matrix
+        else:
+            k = self.kernel.kernel
+            km = lambda a, b: k(torch.cdist(a, b, p=2))
         sig = self.sigmasq.detach()
-        K_no = k(torch.cdist(xn, x, p=2))
-        K_oo = k(torch.cdist(x, x, p=2)) + sig * torch.eye(x.shape[0], dtype=x.dtype, device=x.device)
-        K_nn = k(torch.cdist(xn, xn, p=2))
+        K_no = km(xn, x)
+        K_oo = km(x, x) + sig * torch.eye(x.shape[0], dtype=x.dtype, device=x.device)
+        K_nn = km(xn, xn)
         cov = K_nn - K_no @ torch.linalg.solve(K_oo, K_no.T)
         cov = cov + 1e-10 * torch.eye(xn.shape[0], dtype=xn.dtype, device=xn.device)
         chol = torch.linalg.cholesky(cov)
@@ -1648,10 +1713,11 @@ class EFGPND(nn.Module):
             opt.step()
             with torch.no_grad():
                 try:
-                    idx = self._gp_params.hypers_names.index("lengthscale")
+                    names = self._gp_params.hypers_names
                     floor = torch.tensor(min_lengthscale, device=self._gp_params.raw.device, dtype=self._gp_params.raw.dtype)
-                    if torch.exp(self._gp_params.raw[idx]) < floor:
-                        self._gp_params.raw[idx].copy_(torch.log(floor))
+                    for idx in [i for i, nm in enumerate(names) if nm.startswith("lengthscale_")] or [names.index("lengthscale")]:
+                        if torch.exp(self._gp_params.raw[idx]) < floor:
+                            self._gp_params.raw[idx].copy_(torch.log(floor))
                 except (ValueError, IndexError) as e:
                     if verbose:
                         print(f"Note: Could not apply lengthscale constraint: {e}")

@@ -147,3 +147,24 @@ def get_xis(kernel_obj, eps: float, L, use_integral: bool = False, l2scaled: boo
 
     xis = torch.arange(-hm, hm + 1, device="cpu", dtype=dtype) * h_spacing
     return xis, h_spacing, xis.numel()
+
+
+def get_xis_nd(kernel, eps: float, Ls, trunc_eps: Optional[float] = None):
+    """Per-axis grid of an ARD kernel (kernels/ard.py) on a box with sides ``Ls``: axis j runs the two bisections of
+    ``get_xis(use_integral=True)`` for the isotropic kernel of the same class with lengthscale l_j (through `efgp_grid_bounds`
+    where the library is loaded, as `get_xis` does) and the side L_j,
+
+        h_j = 1 / (L_j + Ltime(l_j)),   m_j = ceil(Lfreq(l_j) / h_j),   n_j = 2 m_j + 1.
+
+    Returns ``(hs, shape)``: d spacings and d mode counts.  With all l_j equal and all L_j equal this is the isotropic grid
+    bit for bit."""
+    d = kernel.dimension
+    Ls = [float(v) for v in (Ls.tolist() if torch.is_tensor(Ls) else Ls)]
+    if len(Ls) != d:
+        raise ValueError(f"get_xis_nd needs {d} box sides, got {len(Ls)}")
+    hs, shape = [], []
+    for j in range(d):
+        _, h, n = get_xis(kernel.isotropic(j), eps, Ls[j], use_integral=True, trunc_eps=trunc_eps)
+        hs.append(float(h))
+        shape.append(int(n))
+    return tuple(hs), tuple(shape)

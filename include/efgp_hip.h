@@ -109,6 +109,12 @@ int efgp_points_attach_values(efgp_points_t* pts, const double* y, void* stream)
  * width <= 8 (tol >= ~6e-8) and enough points per fine-grid cell run on the sorted copies. */
 int efgp_nufft_create_on(efgp_nufft_t** plan_out, efgp_points_t* pts, const double* xcen_host /* d doubles or NULL */,
                          double h, double tol);
+/* efgp_nufft_create / efgp_nufft_create_on with a grid spacing per axis, h: dim HOST doubles (replaces the scalar h of the two
+ * entries above for the per-axis grids of the ARD kernels): phi_a = 2 pi h_a (x_a - xcen_a).  Same plans, same transforms. */
+int efgp_nufft_create_nd(efgp_nufft_t** plan_out, int device, int dim, int64_t npts, const double* x,
+                         const double* xcen_host /* d doubles or NULL (=0) */, const double* h, double tol);
+int efgp_nufft_create_on_nd(efgp_nufft_t** plan_out, efgp_points_t* pts, const double* xcen_host /* d doubles or NULL */,
+                            const double* h, double tol);
 
 /* type 1 (points -> modes), replaces pff.finufft_type1(phi, vals, out_shape, eps, isign, modeord)
  * at efgpnd.py:1496-1499:
@@ -260,6 +266,17 @@ int efgp_spectral_weights_host(int kind, int dim, double nu, double lengthscale,
  * on `stream` instead of a host computation plus a staged upload. */
 int efgp_spectral_weights(int device, int kind, int dim, double nu, double lengthscale, double variance, double c0, double h, int mtot,
                           void* ws, void* dprime, void* stream);
+/* The weights of the ARD kernels (kernels/ard.py; one lengthscale per axis) on the per-axis grid omega_a = h_a k_a,
+ * k_a = -(n_a - 1)/2 .. (n_a - 1)/2, n_modes[a] odd, last axis fastest: replaces efgp_spectral_weights(_host) where the kernel has
+ * dim lengthscales and the grid dim spacings.  S(omega) = (prod l_a) S_1(rho), rho^2 = sum_a (l_a omega_a)^2, S_1 the isotropic
+ * density of the class (kind, nu as above) at lengthscale 1 and the same variance and dimension.
+ *     ws[k] = sqrt(S(omega_k) prod_a h_a);   dprime[k][j] = prod_a h_a * dS/dl_j (j < dim),  dprime[k][dim] = prod_a h_a * dS/dvariance
+ * (complex, imaginary parts 0; dprime (M, dim + 1) or NULL).  lengthscales, h, n_modes: dim HOST values each.  The device entry
+ * writes everything in one launch with the density evaluated once per node; the host twin runs the same per-node function. */
+int efgp_spectral_weights_host_nd(int kind, int dim, double nu, const double* lengthscales, double variance, const double* h,
+                                  const int64_t* n_modes, double* ws_out, double* dprime_out);
+int efgp_spectral_weights_nd(int device, int kind, int dim, double nu, const double* lengthscales, double variance, const double* h,
+                             const int64_t* n_modes, void* ws, void* dprime /* (M, dim+1) or NULL */, void* stream);
 
 /* ---- M-scale tail of the hyper-parameter gradient: replaces the torch glue of efgpnd_gradient_batched ----------------
  * (efgpnd.py:128-141, :155-176, :238-262; the adjoint form of this package: every N-length inner product of the reference
@@ -409,6 +426,16 @@ int efgp_variance_rhs(int device, int dim, int64_t mtot, double h, const double*
                       void* stream);
 int efgp_variance_contract(int device, int dim, int64_t mtot, double h, const double* x_new, int64_t npts, const void* ws,
                            const void* gamma, double* out, void* stream);
+/* The three entries above on a per-axis mode box (n_modes[0], .., n_modes[dim-1]) (HOST array; odd counts for the two variance
+ * entries) and, for the variance entries, a spacing per axis (h: dim HOST doubles): f_k(x*) = exp(2 pi i sum_a k_a h_a x*_a).
+ * They replace efgp_lag_sums / efgp_variance_rhs / efgp_variance_contract where the grid is not (mtot,)^d with one h; the lag box
+ * is (2 n_modes[a] - 1) per axis, FFT order. */
+int efgp_lag_sums_nd(int device, int dim, const int64_t* n_modes, const void* gamma, const double* eta, int nprobes, void* out,
+                     void* stream);
+int efgp_variance_rhs_nd(int device, int dim, const int64_t* n_modes, const double* h, const double* x_new, int64_t npts, const void* ws,
+                         void* rhs, void* stream);
+int efgp_variance_contract_nd(int device, int dim, const int64_t* n_modes, const double* h, const double* x_new, int64_t npts,
+                              const void* ws, const void* gamma, double* out, void* stream);
 /* Rows on the symmetric mode box of nmodes = mtot^d entries (odd; flat index j, the negated frequency at nmodes - 1 - j) for the
  * path sampler, one launch for all rows:
  *     out[s, j] = a * ws[j] * fz[s, j] + b * e[s, j],
