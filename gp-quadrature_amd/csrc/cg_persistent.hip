@@ -17,6 +17,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "cg_plan_host.hpp"
 #include "common.hpp"
 #include "spectral_weights.hpp"
 #include "toeplitz_cg.hpp"
@@ -25,9 +26,7 @@ namespace efgp {
 
 namespace pcg {
 
-constexpr int kThreads = 512;
-constexpr int kSlots = 4;            // vector elements per thread (M <= kSlots * kThreads)
-constexpr int kMaxGrid = 4608;       // complex elements per ping-pong buffer (2 x 72 KB = 144 KB LDS)
+// kThreads, kSlots, kMaxGrid and l1d::KS: cg_plan_host.hpp (the host's planners use them too)
 constexpr int kRedWaves = kThreads / 64;
 
 struct Pass {            // one 1-D FFT pass over dimension `dim`
@@ -1849,7 +1848,6 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
 // [n - 1, 2 n - 1)), recurrences and stopping rules as cg_persistent_kernel (cg.py:86-244).
 // ------------------------------------------------------------------------------------------------
 namespace l1d {
-constexpr int KS = 4;
 __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -2156,18 +2154,9 @@ __global__ __launch_bounds__(kThreads) void fft2d64_batch_kernel(const void* __r
 int fft2d64_batch_launch(const void* src, int src_is_real, int64_t src_stride, int L0, int L1, double2* dst, int64_t dst_stride,
                          int nbatch, hipStream_t stream) {
     using namespace pcg;
-    bool& attr = per_device_flag("fft2d64_batch");
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)fft2d64_batch_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)fft2d64_batch_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-        if (e != hipSuccess) {
-            set_error("64 x 64 batched transform: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return EFGP_EHIP;
-        }
-        attr = true;
-    }
     const size_t lds = (size_t)2 * s64::BUF * sizeof(double2);
+    const void* kernel = src_is_real ? (const void*)fft2d64_batch_kernel<true> : (const void*)fft2d64_batch_kernel<false>;
+    if (const int rc = raise_dynamic_lds(kernel, lds, "64 x 64 batched transform")) return rc;
     if (src_is_real) hipLaunchKernelGGL(fft2d64_batch_kernel<true>, dim3(nbatch), dim3(kThreads), lds, stream, src, src_stride, L0, L1, dst, dst_stride);
     else hipLaunchKernelGGL(fft2d64_batch_kernel<false>, dim3(nbatch), dim3(kThreads), lds, stream, src, src_stride, L0, L1, dst, dst_stride);
     hipError_t e = hipGetLastError();
@@ -2178,28 +2167,11 @@ int fft2d64_batch_launch(const void* src, int src_is_real, int64_t src_stride, i
     return EFGP_OK;
 }
 
-namespace pcg {
-
-}  // namespace pcg
-
-bool toeplitz_vhat_fused_eligible(const ToepGeom& g) {
-    return g.d == 2 && g.F[0] == 64 && g.F[1] == 64 && std::getenv("EFGP_NO_VHAT64") == nullptr;
-}
-
 int toeplitz_vhat_fused_launch(const double2* v, int L0, int L1, double factor, double2* vhat, hipStream_t stream) {
     using namespace pcg;
-    bool& attr = per_device_flag("vhat_2d64");
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)toeplitz_vhat_2d64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024 - 256);
-        if (e != hipSuccess) {
-            set_error("Toeplitz spectrum (64x64): hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return EFGP_EHIP;
-        }
-        attr = true;
-    }
-    hipLaunchKernelGGL(toeplitz_vhat_2d64_kernel, dim3(1), dim3(kThreads), (size_t)2 * s64::BUF * sizeof(double2), stream,
-                       v, L0, L1, factor, vhat);
+    const size_t lds = (size_t)2 * s64::BUF * sizeof(double2);
+    if (const int rc = raise_dynamic_lds((const void*)toeplitz_vhat_2d64_kernel, lds, "Toeplitz spectrum (64x64)")) return rc;
+    hipLaunchKernelGGL(toeplitz_vhat_2d64_kernel, dim3(1), dim3(kThreads), lds, stream, v, L0, L1, factor, vhat);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("Toeplitz spectrum (64x64) launch failed: %s", hipGetErrorString(e));
@@ -2211,17 +2183,8 @@ int toeplitz_vhat_fused_launch(const double2* v, int L0, int L1, double factor, 
 // vhat64 (may be null) and vhat48 in one launch; both are FFT(zero-padded v) / (their grid size), natural order
 int toeplitz_vhat_pair_launch(const double2* v, int L0, int L1, double2* vhat64, double2* vhat48, hipStream_t stream) {
     using namespace pcg;
-    bool& attr = per_device_flag("vhat_pair");
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)toeplitz_vhat_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024 - 256);
-        if (e != hipSuccess) {
-            set_error("Toeplitz spectra (64x64 + 48x48): hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return EFGP_EHIP;
-        }
-        attr = true;
-    }
     const size_t lds = vhat64 ? (size_t)2 * s64::BUF * sizeof(double2) : (size_t)(48 * 49 + 64 * 72) * sizeof(double2);
+    if (const int rc = raise_dynamic_lds((const void*)toeplitz_vhat_pair_kernel, lds, "Toeplitz spectra (64x64 + 48x48)")) return rc;
     hipLaunchKernelGGL(toeplitz_vhat_pair_kernel, dim3(vhat64 ? 2 : 1), dim3(kThreads), lds, stream, v, L0, L1, 1.0 / 4096.0, vhat64,
                        1.0 / 2304.0, vhat48);
     hipError_t e = hipGetLastError();
@@ -2363,24 +2326,11 @@ __global__ __launch_bounds__(kThreads) void toeplitz_apply_2d64_kernel(ApplyArgs
 
 }  // namespace pcg
 
-bool toeplitz_apply_fused_eligible(const ToepGeom& g) {
-    return g.d == 2 && g.F[0] == 64 && g.F[1] == 64 && g.n[0] == g.n[1] && g.n[0] <= 32 && g.M <= 2 * pcg::kThreads &&
-           std::getenv("EFGP_NO_APPLY64") == nullptr;
-}
-
 int toeplitz_apply_fused_launch(const ToepGeom& g, const double2* tw64, const double2* vhat, const double2* pre, const double2* post,
                                 const void* x, int x_is_real, double2* y, int rows, hipStream_t stream, int pre_stride) {
     using namespace pcg;
-    bool& attr = per_device_flag("apply_2d64");
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)toeplitz_apply_2d64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024 - 256);
-        if (e != hipSuccess) {
-            set_error("Toeplitz apply (64x64): hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return EFGP_EHIP;
-        }
-        attr = true;
-    }
+    const size_t lds = (size_t)2 * 64 * 72 * sizeof(double2);
+    if (const int rc = raise_dynamic_lds((const void*)toeplitz_apply_2d64_kernel, lds, "Toeplitz apply (64x64)")) return rc;
     ApplyArgs a;
     a.n = (int)g.n[0];
     a.M = (int)g.M;
@@ -2392,7 +2342,7 @@ int toeplitz_apply_fused_launch(const ToepGeom& g, const double2* tw64, const do
     a.x = x;
     a.x_is_real = x_is_real;
     a.y = y;
-    hipLaunchKernelGGL(toeplitz_apply_2d64_kernel, dim3(rows), dim3(kThreads), (size_t)2 * 64 * 72 * sizeof(double2), stream, a);
+    hipLaunchKernelGGL(toeplitz_apply_2d64_kernel, dim3(rows), dim3(kThreads), lds, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("Toeplitz apply (64x64) launch failed: %s", hipGetErrorString(e));
@@ -2434,159 +2384,87 @@ extern "C" int efgp_debug_cg_stamps(long long* out16) {
 }
 #endif
 
-bool persistent_cg_eligible(const ToepGeom& tg) {
-    int64_t padded = 1;
-    for (int a = 0; a < tg.d; ++a) {
-        if (tg.F[a] & (tg.F[a] - 1)) return false;
-        if (tg.F[a] > 4096) return false;
-    }
-    // padded leading dimension on the fastest axis when d > 1
-    for (int a = 0; a < tg.d; ++a) padded *= (a == tg.d - 1 && tg.d > 1) ? tg.F[a] + 1 : tg.F[a];
-    if (padded > pcg::kMaxGrid) return false;
-    if (tg.M > (int64_t)pcg::kSlots * pcg::kThreads) return false;
-    return true;
-}
+namespace pcg {
 
-int persistent_cg_launch(const ToepGeom& full, const double2* const* tw_full, const double2* vhat, const Herm48Operands* h48,
-                         const CgSolve& s, int* d_iters, hipStream_t stream, const LanczosOut* lz, const MeanFusedOperands* fuse) {
-    using namespace pcg;
-    // An axis with a single mode has F = 1: no stage to run (radices_for gives nstages = 0).  As axis 0 it would own the fused
-    // middle stage -- the spectral multiply would be skipped and the spectrum registers loaded through radix[-1].  Such an axis has
-    // one lag and one cell: block, padded grid and spectrum keep their row-major order without it, so the kernels get the geometry
-    // of the remaining axes (exact).  A grid of one cell in all never comes here (efgp_toeplitz_create_ex).
-    ToepGeom tg = full;
-    const double2* twiddles[3] = {nullptr, nullptr, nullptr};
-    tg.d = 0;
+// An axis with a single mode has F = 1: no stage to run (radices_for gives nstages = 0).  As axis 0 it would own the fused
+// middle stage -- the spectral multiply would be skipped and the spectrum registers loaded through radix[-1].  Such an axis has
+// one lag and one cell: block, padded grid and spectrum keep their row-major order without it, so the kernels get the geometry
+// of the remaining axes (exact).  Returns how many axes are left: a grid of one cell in all never comes here
+// (efgp_toeplitz_create_ex).
+static int squeeze_unit_axes(const ToepGeom& full, const double2* const* tw_full, ToepGeom* tg, const double2** twiddles) {
+    *tg = full;
+    tg->d = 0;
     for (int i = 0; i < full.d; ++i) {
         if (full.F[i] == 1) continue;
-        tg.n[tg.d] = full.n[i];
-        tg.F[tg.d] = full.F[i];
-        twiddles[tg.d] = tw_full[i];
-        ++tg.d;
+        tg->n[tg->d] = full.n[i];
+        tg->F[tg->d] = full.F[i];
+        twiddles[tg->d] = tw_full[i];
+        ++tg->d;
     }
-    for (int i = tg.d; i < 3; ++i) tg.n[i] = tg.F[i] = 1;
-    if (tg.d == 0) {
-        set_error("persistent CG: a grid of a single cell has no transform to run");
-        return EFGP_EUNSUPPORTED;
-    }
-    Args a;
-    a.ws_out = nullptr;
-    a.vsrc = nullptr;
-    a.vhat_out = nullptr;
-    Geom& g = a.g;
-    g.d = tg.d;
-    for (int i = 0; i < 3; ++i) {
-        g.n[i] = i < tg.d ? (int)tg.n[i] : 1;
-        g.F[i] = i < tg.d ? (int)tg.F[i] : 1;
-        g.tw[i] = i < tg.d ? twiddles[i] : nullptr;
-    }
-    // shift geometry so that the LAST real dimension sits in slot 2 for the vhat flat index (F[1], F[2] used)
-    // -> we keep dims in slots 0..d-1 and set missing trailing F to 1, flat = (i0*F1 + i1)*F2 + i2 holds.
-    // strides of the padded grid
-    int stride = 1;
-    for (int i = 2; i >= 0; --i) {
-        if (i >= tg.d) {
-            g.ld[i] = 0;
-            continue;
+    for (int i = tg->d; i < 3; ++i) tg->n[i] = tg->F[i] = 1;
+    return tg->d;
+}
+
+// Pass `p` over dimension `dim`, with the line ranges of the two other dimensions.  Forward (the last dimension goes first): lines
+// restricted to the leading n-box of the dims not transformed yet.  Inverse (the first dimension goes first): outputs cropped to
+// [n-1, 2n-1), later passes only visit cropped lines.
+static void set_pass(const Geom& g, int dim, bool inverse, Pass& p) {
+    p.dim = dim;
+    p.n = g.F[dim];
+    radices_for(p.n, &p);
+    int oi = 0;
+    for (int o = 0; o < 3; ++o) {
+        if (o == dim) continue;
+        p.other[oi] = o;
+        p.lo[oi] = 0;
+        if (o >= g.d) {
+            p.hi[oi] = 1;
+        } else if (o > dim) {           // forward: already transformed; inverse: still to come -- full range
+            p.hi[oi] = g.F[o];
+        } else if (!inverse) {          // not transformed yet: only the n-box is non-zero
+            p.hi[oi] = g.n[o];
+        } else {                        // already inverse-transformed and cropped
+            p.lo[oi] = g.n[o] - 1;
+            p.hi[oi] = 2 * g.n[o] - 1;
         }
-        g.ld[i] = stride;
-        stride *= (i == tg.d - 1 && tg.d > 1) ? g.F[i] + 1 : g.F[i];
+        ++oi;
     }
-    g.padded = stride;
-    g.M = (int)tg.M;
-    g.npass = tg.d;
-    // forward: last dimension first; lines restricted to the leading n-box of not-yet-transformed dims
-    for (int q = 0; q < tg.d; ++q) {
-        const int dim = tg.d - 1 - q;
-        Pass& p = g.fwd[q];
-        p.dim = dim;
-        p.n = g.F[dim];
-        radices_for(p.n, &p);
-        int oi = 0;
-        for (int o = 0; o < 3; ++o) {
-            if (o == dim) continue;
-            p.other[oi] = o;
-            if (o >= tg.d) {
-                p.lo[oi] = 0;
-                p.hi[oi] = 1;
-            } else if (o < dim) {       // not transformed yet: only the n-box is non-zero
-                p.lo[oi] = 0;
-                p.hi[oi] = g.n[o];
-            } else {                    // already transformed: full range
-                p.lo[oi] = 0;
-                p.hi[oi] = g.F[o];
-            }
-            ++oi;
-        }
-        p.in_limit = g.n[dim];
-        p.out_lo = 0;
-        p.out_hi = p.n;
-    }
-    // inverse: first dimension first; outputs cropped to [n-1, 2n-1); later passes only visit cropped lines
-    for (int q = 0; q < tg.d; ++q) {
-        const int dim = q;
-        Pass& p = g.inv[q];
-        p.dim = dim;
-        p.n = g.F[dim];
-        radices_for(p.n, &p);
-        int oi = 0;
-        for (int o = 0; o < 3; ++o) {
-            if (o == dim) continue;
-            p.other[oi] = o;
-            if (o >= tg.d) {
-                p.lo[oi] = 0;
-                p.hi[oi] = 1;
-            } else if (o < dim) {       // already inverse-transformed and cropped
-                p.lo[oi] = g.n[o] - 1;
-                p.hi[oi] = 2 * g.n[o] - 1;
-            } else {
-                p.lo[oi] = 0;
-                p.hi[oi] = g.F[o];
-            }
-            ++oi;
-        }
-        p.in_limit = p.n;
-        p.out_lo = g.n[dim] - 1;
-        p.out_hi = 2 * g.n[dim] - 1;
-    }
-    // inverse passes use the forward radices in reverse order (so that the fused middle stage lines up)
-    for (int q = 0; q < tg.d; ++q) {
-        Pass& p = g.inv[q];
-        for (int i = 0; i < p.nstages / 2; ++i) std::swap(p.radix[i], p.radix[p.nstages - 1 - i]);
-    }
-    // `other[1]` must be the faster-varying (smaller stride) of the two so that lanes walk it first
-    for (int q = 0; q < tg.d; ++q) {
-        for (Pass* p : {&g.fwd[q], &g.inv[q]}) {
-            const int s0 = p->other[0] < tg.d ? g.ld[p->other[0]] : 0;
-            const int s1 = p->other[1] < tg.d ? g.ld[p->other[1]] : 0;
-            const bool swap = (p->other[1] >= tg.d) ? (p->other[0] < tg.d) : (p->other[0] < tg.d && s0 < s1 && s0 > 0);
-            if (swap) {
-                std::swap(p->other[0], p->other[1]);
-                std::swap(p->lo[0], p->lo[1]);
-                std::swap(p->hi[0], p->hi[1]);
-            }
-        }
-    }
+    p.in_limit = inverse ? p.n : g.n[dim];
+    p.out_lo = inverse ? g.n[dim] - 1 : 0;
+    p.out_hi = inverse ? 2 * g.n[dim] - 1 : p.n;
+}
+
+// how the lanes walk the lines of each pass
+static void order_lines(Geom& g) {
     auto ilog2 = [](int v) {
         int l = 0;
         while ((1 << l) < v) ++l;
         return l;
     };
-    for (int q = 0; q < tg.d; ++q) {
+    for (int q = 0; q < g.d; ++q) {
         for (Pass* p : {&g.fwd[q], &g.inv[q]}) {
+            // `other[1]` must be the faster-varying (smaller stride) of the two so that lanes walk it first
+            const int s0 = p->other[0] < g.d ? g.ld[p->other[0]] : 0;
+            const int s1 = p->other[1] < g.d ? g.ld[p->other[1]] : 0;
+            const bool swap = (p->other[1] >= g.d) ? (p->other[0] < g.d) : (p->other[0] < g.d && s0 < s1 && s0 > 0);
+            if (swap) {
+                std::swap(p->other[0], p->other[1]);
+                std::swap(p->lo[0], p->lo[1]);
+                std::swap(p->hi[0], p->hi[1]);
+            }
             p->w1_log2 = ilog2(p->hi[1] - p->lo[1]);
             p->lines_log2 = p->w1_log2 + ilog2(p->hi[0] - p->lo[0]);
         }
     }
-    // fused middle stage: forward last pass (dim 0) and inverse first pass (dim 0) share dimension and the
-    // last forward radix equals the first inverse radix by construction; both visit the same lines (all of
-    // the other dimensions' FFT range), so the fusion is always structurally valid when d >= 1
-    g.fuse_mid = 1;
-    // LDS twiddle copies behind the two ping-pong buffers while they fit in the 160 KB budget
+}
+
+// LDS twiddle copies behind the two ping-pong buffers while they fit in the 160 KB budget, and every pass's strides in the padded
+// grid and in the unpadded spectrum
+static void place_twiddles_and_strides(Geom& g) {
     g.tw_lds_total = 0;
     const int lds_budget = 160 * 1024 - 256;
     for (int i = 0; i < 3; ++i) g.tw_lds_off[i] = -1;
-    for (int i = 0; i < tg.d; ++i) {
+    for (int i = 0; i < g.d; ++i) {
         int shared = -1;
         for (int b_ = 0; b_ < i; ++b_)
             if (g.F[b_] == g.F[i] && g.tw_lds_off[b_] >= 0) shared = g.tw_lds_off[b_];
@@ -2601,25 +2479,67 @@ int persistent_cg_launch(const ToepGeom& full, const double2* const* tw_full, co
         }
     }
     int vstride[3] = {0, 0, 0};
-    {
-        int acc = 1;
-        for (int i = tg.d - 1; i >= 0; --i) {
-            vstride[i] = acc;
-            acc *= g.F[i];
-        }
+    int acc = 1;
+    for (int i = g.d - 1; i >= 0; --i) {
+        vstride[i] = acc;
+        acc *= g.F[i];
     }
-    for (int q = 0; q < tg.d; ++q) {
+    for (int q = 0; q < g.d; ++q) {
         for (Pass* p : {&g.fwd[q], &g.inv[q]}) {
             p->vs_pos = vstride[p->dim];
-            p->vs_c0 = p->other[0] < tg.d ? vstride[p->other[0]] : 0;
-            p->vs_c1 = p->other[1] < tg.d ? vstride[p->other[1]] : 0;
+            p->vs_c0 = p->other[0] < g.d ? vstride[p->other[0]] : 0;
+            p->vs_c1 = p->other[1] < g.d ? vstride[p->other[1]] : 0;
             p->pstride = g.ld[p->dim];
-            p->s0 = p->other[0] < tg.d ? g.ld[p->other[0]] : 0;
-            p->s1 = p->other[1] < tg.d ? g.ld[p->other[1]] : 0;
+            p->s0 = p->other[0] < g.d ? g.ld[p->other[0]] : 0;
+            p->s1 = p->other[1] < g.d ? g.ld[p->other[1]] : 0;
             p->tw_lds = g.tw_lds_off[p->dim];
             p->tw_glob = g.tw[p->dim];
         }
     }
+}
+
+// The pass geometry of the generic kernel for a block without unit axes: dims sit in slots 0..d-1 and missing trailing F are 1, so
+// the spectrum's flat index (i0*F1 + i1)*F2 + i2 holds
+static void pass_geometry(const ToepGeom& tg, const double2* const* twiddles, Geom& g) {
+    g.d = tg.d;
+    for (int i = 0; i < 3; ++i) {
+        g.n[i] = i < tg.d ? (int)tg.n[i] : 1;
+        g.F[i] = i < tg.d ? (int)tg.F[i] : 1;
+        g.tw[i] = i < tg.d ? twiddles[i] : nullptr;
+    }
+    // strides of the padded grid
+    int stride = 1;
+    for (int i = 2; i >= 0; --i) {
+        if (i >= tg.d) {
+            g.ld[i] = 0;
+            continue;
+        }
+        g.ld[i] = stride;
+        stride *= (i == tg.d - 1 && tg.d > 1) ? g.F[i] + 1 : g.F[i];
+    }
+    g.padded = stride;
+    g.M = (int)tg.M;
+    g.npass = tg.d;
+    for (int q = 0; q < tg.d; ++q) {
+        set_pass(g, tg.d - 1 - q, false, g.fwd[q]);
+        Pass& p = g.inv[q];
+        set_pass(g, q, true, p);
+        // inverse passes use the forward radices in reverse order (so that the fused middle stage lines up)
+        for (int i = 0; i < p.nstages / 2; ++i) std::swap(p.radix[i], p.radix[p.nstages - 1 - i]);
+    }
+    order_lines(g);
+    // fused middle stage: forward last pass (dim 0) and inverse first pass (dim 0) share dimension and the
+    // last forward radix equals the first inverse radix by construction; both visit the same lines (all of
+    // the other dimensions' FFT range), so the fusion is always structurally valid when d >= 1
+    g.fuse_mid = 1;
+    place_twiddles_and_strides(g);
+}
+
+// the solve as the kernels take it (the geometry apart)
+static void solve_args(const CgSolve& s, const double2* vhat, int* d_iters, const LanczosOut* lz, Args& a) {
+    a.ws_out = nullptr;
+    a.vsrc = nullptr;
+    a.vhat_out = nullptr;
     a.ws = s.ws;
     a.diag = s.diag;
     a.diag_scale = s.diag_scale;
@@ -2636,13 +2556,83 @@ int persistent_cg_launch(const ToepGeom& full, const double2* const* tw_full, co
     a.b = s.b;
     a.x = s.x;
     a.iters = d_iters;
-    const int rows = s.nbatch, variant = s.variant;
     a.hist = cg_history().buf;
     a.hist_cap = cg_history().capacity;
     a.lz_steps = lz ? lz->steps : 0;
     a.lz_alpha = lz ? lz->alpha : nullptr;
     a.lz_beta = lz ? lz->beta : nullptr;
     a.lz_norm2 = lz ? lz->norm2 : nullptr;
+}
+
+// the 48 x 48 kernels: the operator's second spectrum and twiddles; the fused mean solve makes ws and that spectrum itself
+static void operands48(const Herm48Operands& h48, const MeanFusedOperands* fuse, Args& a) {
+    a.vhat = fuse ? nullptr : h48.vhat;
+    a.g.F[0] = a.g.F[1] = 48;
+    a.g.tw[0] = a.g.tw[1] = h48.tw;
+    if (!fuse) return;
+    a.ws = nullptr;
+    a.wk_kind = fuse->kind;
+    a.wk_mtot = fuse->mtot;
+    a.wk_nu = fuse->nu;
+    a.wk_ell = fuse->ell;
+    a.wk_c0 = fuse->c0;
+    a.wk_h = fuse->h;
+    a.ws_out = fuse->ws_out;
+    a.vsrc = fuse->v;
+    a.vL0 = fuse->L0;
+    a.vL1 = fuse->L1;
+    a.vhat_out = fuse->vhat48_out;
+}
+
+// kernel, workgroup size and dynamic LDS of a pick (one workgroup per system)
+struct PickLaunch {
+    void (*kernel)(Args);
+    int threads;
+    size_t lds;
+    const char* what;
+};
+static PickLaunch launch_of(const PersistentChoice& c, int variant, const Geom& g) {
+    // 48 x 48: the coefficient prologue works on the 48 x 48 grid, 73 KB (two workgroups per CU still fit); the fused prologue's
+    // grid + 32 line slots of scratch outgrow the iteration's 53 KB too -- one workgroup, so the extra LDS costs nothing
+    constexpr size_t lds48d = (size_t)h48::kLdsElemsDense * sizeof(double2);
+    static_assert(h48::kLdsElemsDense >= h48::kLdsElems, "the fused prologue's LDS covers the iteration's");
+    switch (c.pick) {
+        case PersistentPick::fused48:
+            return {c.dense48 ? cg_herm48_kernel<0, true, true> : cg_herm48_kernel<0, true, false>, h48::kThreadsH, lds48d,
+                    "fused mean solve (48x48)"};
+        case PersistentPick::herm48: {
+            void (*const dense[2])(Args) = {cg_herm48_kernel<0, false, true>, cg_herm48_kernel<1, false, true>};
+            void (*const fft2d[2])(Args) = {cg_herm48_kernel<0, false, false>, cg_herm48_kernel<1, false, false>};
+            return {(c.dense48 ? dense : fft2d)[variant != 0], h48::kThreadsH, c.dense48 ? lds48d : (size_t)h48::kLdsElems * sizeof(double2),
+                    "persistent CG (48x48, Hermitian)"};
+        }
+        case PersistentPick::herm64:
+            return {variant == 0 ? cg_herm64_kernel<0> : cg_herm64_kernel<1>, h64::kThreadsH, (size_t)h64::kLdsElems * sizeof(double2),
+                    "persistent CG (64x64, Hermitian)"};
+        case PersistentPick::line1d:          // 1-D: one wave per system
+            return {cg_line1d_kernel, 64, (size_t)4 * g.F[0] * sizeof(double2), "persistent CG (1-D)"};
+        case PersistentPick::fast64:
+            return {cg_persistent_2d64_kernel, kThreads, (size_t)2 * 64 * 72 * sizeof(double2), "persistent CG (64x64)"};
+        case PersistentPick::generic:
+            break;
+    }
+    return {cg_persistent_kernel, kThreads, ((size_t)2 * g.padded + g.tw_lds_total) * sizeof(double2), "persistent CG"};
+}
+
+}  // namespace pcg
+
+int persistent_cg_launch(const ToepGeom& full, const double2* const* tw_full, const double2* vhat, const Herm48Operands* h48,
+                         const CgSolve& s, int* d_iters, hipStream_t stream, const LanczosOut* lz, const MeanFusedOperands* fuse) {
+    using namespace pcg;
+    ToepGeom tg;
+    const double2* twiddles[3] = {nullptr, nullptr, nullptr};
+    if (squeeze_unit_axes(full, tw_full, &tg, twiddles) == 0) {
+        set_error("persistent CG: a grid of a single cell has no transform to run");
+        return EFGP_EUNSUPPORTED;
+    }
+    Args a;
+    pass_geometry(tg, twiddles, a.g);
+    solve_args(s, vhat, d_iters, lz, a);
 #ifdef EFGP_CG_STAMPS
     {
         static long long* d_stamps = nullptr;
@@ -2652,124 +2642,16 @@ int persistent_cg_launch(const ToepGeom& full, const double2* const* tw_full, co
         g_last_stamps = d_stamps;
     }
 #endif
-    const size_t lds = ((size_t)2 * g.padded + g.tw_lds_total) * sizeof(double2);
-    bool& attr_set = per_device_flag("cg_persistent");
-    if (!attr_set && lds > 65536) {
-        hipError_t e = hipFuncSetAttribute((const void*)cg_persistent_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024 - 256);
-        if (e != hipSuccess) {
-            set_error("persistent CG: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return EFGP_EHIP;
-        }
-        attr_set = true;
+    PersistentChoice c;
+    if (const int rc = pick_persistent(full, s, h48 != nullptr && h48->vhat != nullptr, lz != nullptr, fuse != nullptr, &c)) return rc;
+    if (c.pick == PersistentPick::fused48 || c.pick == PersistentPick::herm48) operands48(*h48, fuse, a);
+    const PickLaunch l = launch_of(c, s.variant, a.g);
+    if (const int rc = raise_dynamic_lds((const void*)l.kernel, l.lds, l.what)) return rc;
+    {
+        KernelTimer timer("cg_solve", stream);
+        hipLaunchKernelGGL(l.kernel, dim3(s.nbatch), dim3(l.threads), l.lds, stream, a);
     }
-    // the specialised kernels are picked by the caller's shape: a block with a unit axis runs the generic kernel on its other axes
-    const bool fast64 = full.d == 2 && g.F[0] == 64 && g.F[1] == 64 && g.n[0] == g.n[1] && g.n[0] <= 32 &&
-                        std::getenv("EFGP_NO_CG64") == nullptr;
-    const bool herm64 = fast64 && s.hermitian && !lz && (g.n[0] & 1) && g.n[0] <= 31 && std::getenv("EFGP_NO_CG_HERM") == nullptr;
-    // blocks of up to 23 x 23 modes: the smallest circulant grid, 48 x 48 (the operator holds a second spectrum for it)
-    const bool herm48 = herm64 && h48 != nullptr && h48->vhat != nullptr && g.n[0] <= 23 && std::getenv("EFGP_NO_CG48") == nullptr;
-    if (fuse != nullptr && !(herm48 && variant == 0 && rows == 1 && s.zero_x0 && s.b_times_ws && !s.diag)) {
-        set_error("fused mean solve: the system is not a cold-start 48 x 48 Hermitian mean solve");
-        return EFGP_EUNSUPPORTED;
-    }
-    // EFGP_CG48_FFT2D=1: the round 4 operator application (packed column transforms) instead of the per-frequency Toeplitz products.
-    // Batches keep it too: the resident coefficients take the kernel to 256 + 16 registers, one workgroup per CU instead of two.
-    const bool dense48 = rows == 1 && std::getenv("EFGP_CG48_FFT2D") == nullptr;
-    if (herm48 && fuse != nullptr) {
-        // the prologue's grid + 32 line slots of scratch outgrow the iteration's 53 KB; one workgroup, so the extra LDS costs nothing
-        constexpr size_t lds_f = (size_t)h48::kLdsElemsDense * sizeof(double2);
-        static_assert(h48::kLdsElemsDense >= h48::kLdsElems, "the fused prologue's LDS covers the iteration's");
-        bool& attr_f = per_device_flag("cg_herm48_fused");
-        if (!attr_f) {
-            hipError_t e2 = hipFuncSetAttribute((const void*)cg_herm48_kernel<0, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f);
-            if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)cg_herm48_kernel<0, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f);
-            if (e2 != hipSuccess) {
-                set_error("fused mean solve (48x48): hipFuncSetAttribute failed: %s", hipGetErrorString(e2));
-                return EFGP_EHIP;
-            }
-            attr_f = true;
-        }
-        a.vhat = nullptr;
-        a.ws = nullptr;
-        a.wk_kind = fuse->kind;
-        a.wk_mtot = fuse->mtot;
-        a.wk_nu = fuse->nu;
-        a.wk_ell = fuse->ell;
-        a.wk_c0 = fuse->c0;
-        a.wk_h = fuse->h;
-        a.ws_out = fuse->ws_out;
-        a.vsrc = fuse->v;
-        a.vL0 = fuse->L0;
-        a.vL1 = fuse->L1;
-        a.vhat_out = fuse->vhat48_out;
-        g.F[0] = g.F[1] = 48;
-        g.tw[0] = g.tw[1] = h48->tw;
-        KernelTimer timer("cg_solve", stream);
-        if (dense48) hipLaunchKernelGGL((cg_herm48_kernel<0, true, true>), dim3(1), dim3(h48::kThreadsH), lds_f, stream, a);
-        else hipLaunchKernelGGL((cg_herm48_kernel<0, true, false>), dim3(1), dim3(h48::kThreadsH), lds_f, stream, a);
-    } else if (herm48) {
-        bool& attr_h = per_device_flag("cg_herm48");
-        // the coefficient prologue works on the 48 x 48 grid: 73 KB, two workgroups per CU still fit
-        const size_t lds_d = (size_t)h48::kLdsElemsDense * sizeof(double2);
-        const size_t lds_h = dense48 ? lds_d : (size_t)h48::kLdsElems * sizeof(double2);
-        if (!attr_h) {
-            hipError_t e2 = hipFuncSetAttribute((const void*)cg_herm48_kernel<0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
-            if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)cg_herm48_kernel<1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
-            if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)cg_herm48_kernel<0, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
-            if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)cg_herm48_kernel<1, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
-            if (e2 != hipSuccess) {
-                set_error("persistent CG (48x48, Hermitian): hipFuncSetAttribute failed: %s", hipGetErrorString(e2));
-                return EFGP_EHIP;
-            }
-            attr_h = true;
-        }
-        a.vhat = h48->vhat;
-        g.F[0] = g.F[1] = 48;
-        g.tw[0] = g.tw[1] = h48->tw;
-        KernelTimer timer("cg_solve", stream);
-        if (dense48 && variant == 0) hipLaunchKernelGGL((cg_herm48_kernel<0, false, true>), dim3(rows), dim3(h48::kThreadsH), lds_h, stream, a);
-        else if (dense48) hipLaunchKernelGGL((cg_herm48_kernel<1, false, true>), dim3(rows), dim3(h48::kThreadsH), lds_h, stream, a);
-        else if (variant == 0) hipLaunchKernelGGL((cg_herm48_kernel<0, false, false>), dim3(rows), dim3(h48::kThreadsH), lds_h, stream, a);
-        else hipLaunchKernelGGL((cg_herm48_kernel<1, false, false>), dim3(rows), dim3(h48::kThreadsH), lds_h, stream, a);
-    } else if (herm64) {
-        bool& attr_h = per_device_flag("cg_herm64");
-        const size_t lds_h = (size_t)h64::kLdsElems * sizeof(double2);
-        if (!attr_h) {
-            hipError_t e2 = hipFuncSetAttribute((const void*)cg_herm64_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h);
-            if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)cg_herm64_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h);
-            if (e2 != hipSuccess) {
-                set_error("persistent CG (64x64, Hermitian): hipFuncSetAttribute failed: %s", hipGetErrorString(e2));
-                return EFGP_EHIP;
-            }
-            attr_h = true;
-        }
-        KernelTimer timer("cg_solve", stream);
-        if (variant == 0) hipLaunchKernelGGL(cg_herm64_kernel<0>, dim3(rows), dim3(h64::kThreadsH), lds_h, stream, a);
-        else hipLaunchKernelGGL(cg_herm64_kernel<1>, dim3(rows), dim3(h64::kThreadsH), lds_h, stream, a);
-    } else if (full.d == 1 && !lz && g.n[0] <= 64 * l1d::KS - 1 && g.F[0] >= 8 && g.F[0] <= 512 && (g.F[0] & (g.F[0] - 1)) == 0 &&
-               std::getenv("EFGP_NO_CG_LINE1D") == nullptr) {
-        KernelTimer timer("cg_solve", stream);             // 1-D: one wave per system
-        hipLaunchKernelGGL(cg_line1d_kernel, dim3(rows), dim3(64), (size_t)4 * g.F[0] * sizeof(double2), stream, a);
-    } else if (fast64) {
-        bool& attr64 = per_device_flag("cg_2d64");
-        if (!attr64) {
-            hipError_t e2 = hipFuncSetAttribute((const void*)cg_persistent_2d64_kernel,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-            if (e2 != hipSuccess) {
-                set_error("persistent CG (64x64): hipFuncSetAttribute failed: %s", hipGetErrorString(e2));
-                return EFGP_EHIP;
-            }
-            attr64 = true;
-        }
-        KernelTimer timer("cg_solve", stream);
-        hipLaunchKernelGGL(cg_persistent_2d64_kernel, dim3(rows), dim3(kThreads), (size_t)2 * 64 * 72 * sizeof(double2),
-                           stream, a);
-    } else {
-        KernelTimer timer("cg_solve", stream);
-        hipLaunchKernelGGL(cg_persistent_kernel, dim3(rows), dim3(kThreads), lds, stream, a);
-    }
-    hipError_t e = hipGetLastError();
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("persistent CG launch failed: %s", hipGetErrorString(e));
         return EFGP_EHIP;

@@ -28,11 +28,21 @@ void set_error(const char* fmt, ...) {
 static std::mutex g_mu;
 static std::map<int, std::unique_ptr<DeviceCtx>> g_ctx;
 
-bool& per_device_flag(const char* key) {
-    static std::map<std::pair<int, std::string>, bool> flags;
+int raise_dynamic_lds(const void* kernel, size_t bytes, const char* what) {
+    static std::mutex mu;
+    static std::map<std::pair<int, const void*>, size_t> raised;
     int dev = 0;
     (void)hipGetDevice(&dev);
-    return flags[std::make_pair(dev, std::string(key))];
+    std::lock_guard<std::mutex> lk(mu);
+    size_t& have = raised[std::make_pair(dev, kernel)];
+    if (have >= bytes) return EFGP_OK;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) {
+        set_error("%s: hipFuncSetAttribute failed: %s", what, hipGetErrorString(e));
+        return EFGP_EHIP;
+    }
+    have = bytes;
+    return EFGP_OK;
 }
 
 DeviceCtx* device_ctx(int device) {
@@ -288,6 +298,7 @@ static std::vector<TimingRec> g_recs;
 // recycled events, per device (an event belongs to the device that was current when it was created; recording it on another
 // device's stream fails): hipEventCreate per launch cost the host ~10 us per timed kernel
 static std::map<int, std::vector<hipEvent_t>> g_free_events;
+static std::mutex g_timing_mu;               // g_recs and g_free_events: timers run on any host thread, on any device
 constexpr size_t kMaxTimingRecs = 1 << 16;
 
 static int current_device() {
@@ -322,7 +333,9 @@ hipError_t stream_wait(hipStream_t stream) {
 }
 
 KernelTimer::KernelTimer(const char* name, hipStream_t s) : stream(s) {
-    if (!g_timing || g_recs.size() >= kMaxTimingRecs) return;
+    if (!g_timing) return;
+    std::lock_guard<std::mutex> lk(g_timing_mu);
+    if (g_recs.size() >= kMaxTimingRecs) return;
     if (!g_timing_only.empty() && g_timing_only != name) return;
     TimingRec r;
     r.name = name;
@@ -340,6 +353,7 @@ KernelTimer::KernelTimer(const char* name, hipStream_t s) : stream(s) {
 
 KernelTimer::~KernelTimer() {
     if (slot < 0) return;
+    std::lock_guard<std::mutex> lk(g_timing_mu);
     TimingRec& r = g_recs[(size_t)slot];
     if (r.valid && hipEventRecord(r.stop, stream) != hipSuccess) {
         (void)hipGetLastError();
@@ -348,6 +362,7 @@ KernelTimer::~KernelTimer() {
 }
 
 static void clear_timing() {
+    std::lock_guard<std::mutex> lk(g_timing_mu);
     for (auto& r : g_recs) {
         g_free_events[r.device].push_back(r.start);
         g_free_events[r.device].push_back(r.stop);
@@ -387,6 +402,7 @@ int efgp_kernel_timing_read(const char* name, double* total_ms_out, int64_t* lau
     EFGP_HIP_CHECK(hipDeviceSynchronize());
     double tot = 0.0;
     int64_t cnt = 0;
+    std::lock_guard<std::mutex> lk(g_timing_mu);
     for (auto& r : g_recs) {
         if (r.name != name || !r.valid) continue;
         float ms = 0.f;

@@ -109,9 +109,11 @@ struct DeviceCtx {
     int up_turn = 0;
 };
 
-// a once-per-DEVICE flag (function attributes such as hipFuncAttributeMaxDynamicSharedMemorySize are per device: a
-// process-wide static would leave the second GPU of a process without them); keyed by a site name, for the current device
-bool& per_device_flag(const char* key);
+// Raises hipFuncAttributeMaxDynamicSharedMemorySize of `kernel` on the current device to at least `bytes`.  The attribute is a
+// per-kernel, per-DEVICE maximum (a process-wide flag would leave the second GPU of a process without it), so it is only ever
+// raised: a cache keyed by (device, kernel) under a mutex -- host threads on different devices hold different DeviceGuard locks --
+// makes the runtime call only when the cached value is lower.  EFGP_EHIP with the error set ("<what>: ...") on failure.
+int raise_dynamic_lds(const void* kernel, size_t bytes, const char* what);
 
 // returns the context of `device` (creates it, queries properties); nullptr + error on failure
 DeviceCtx* device_ctx(int device);
@@ -156,7 +158,7 @@ struct KernelTimer {     // RAII: records start at construction, stop at destruc
 // A device context is single-stream at any moment (shared scratch, pooled blocks reused in stream order, caches): a caller that
 // comes in on ANOTHER stream than the context's last one is ordered behind everything queued on that one (an event recorded
 // there, awaited here; a device-wide wait when that fails) instead of racing with it.  Nothing happens while the stream stays
-// the same.  Host threads are not serialised: one thread per device at a time, as before.
+// the same.  Host threads are serialised per device only (DeviceGuard); what devices share is locked on its own.
 void stream_handover(int device, hipStream_t stream);
 // the per-device lock behind DeviceGuard: returns the context it locked (nullptr when the device has none and none can be made)
 DeviceCtx* device_ctx_lock(int device);

@@ -276,15 +276,11 @@ static int launch_pass(DeviceCtx* ctx, const double2* src, double2* dst, int64_t
     // the most the L rule below can ask for: one line of the longest length (131104 B) or 150 KB of strided lines
     constexpr int kPassLdsMax = 150 << 10;
     static_assert(2 * (kFftMaxLine + 1) * (int)sizeof(double2) <= kPassLdsMax, "a single line must fit the LDS budget");
-    bool& attr_set = per_device_flag("own_fft_pass");
-    if (!attr_set) {
-        if (kPassLdsMax + 256 > ctx->max_lds) {
-            set_error("own_fft: the device offers %d bytes of LDS per workgroup, the line transform needs %d", ctx->max_lds, kPassLdsMax + 256);
-            return EFGP_EUNSUPPORTED;
-        }
-        EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)own_fft_pass_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kPassLdsMax));
-        attr_set = true;
+    if (kPassLdsMax + 256 > ctx->max_lds) {
+        set_error("own_fft: the device offers %d bytes of LDS per workgroup, the line transform needs %d", ctx->max_lds, kPassLdsMax + 256);
+        return EFGP_EUNSUPPORTED;
     }
+    if (const int rc = raise_dynamic_lds((const void*)own_fft_pass_kernel, kPassLdsMax, "own_fft")) return rc;
     OwnFftPass p;
     p.src = src;
     p.dst = dst;

@@ -23,8 +23,8 @@
 
 #include <cstdlib>
 
+#include "cg_plan_host.hpp"
 #include "common.hpp"
-#include "es_kernel.hpp"
 #include "line_fft.hpp"
 #include "toeplitz_cg.hpp"
 
@@ -478,7 +478,7 @@ __global__ __launch_bounds__(kVecThreads) void cg_axpy_kernel(CgArgs a) {
 //   followed by cg_axpy_kernel.  Lines are transformed with a Stockham autosort FFT (radix 4, one radix-2 stage
 //   for odd log2 F) in two LDS ping-pong buffers; twiddles come from the per-length table exp(-2 pi i q / F).
 // ==========================================================================================================
-constexpr int kLineThreads = 256;
+// kLineThreads, kCoopMaxG, kCoopLoads: cg_plan_host.hpp (the host's planners use them too)
 
 __device__ __forceinline__ int ilog2(int v) { return 31 - __clz(v); }
 
@@ -1074,8 +1074,6 @@ __global__ __launch_bounds__(kLineThreads) void cg_rows_inv_kernel(LineArgs a) {
 // ==========================================================================================================
 constexpr int kCoopSlots = 4;                 // vector elements per thread (own rows x n1 <= 4 x 256)
 constexpr unsigned kCoopPollLimit = 1u << 22; // ~ seconds of polling before a barrier is declared dead
-constexpr int kCoopMaxG = 64;
-constexpr int kCoopLoads = 16;                // grid elements a thread brings in per phase (lpbc F0 / 256 and lines F1 / 256 at most)
 
 struct CoopArgs {
     ToepGeom g;
@@ -2464,7 +2462,7 @@ static double2* twiddle_table_for(DeviceCtx* ctx, int64_t n, hipStream_t stream)
 static int ensure_deferred_spectra(efgp_toeplitz_s* op, hipStream_t stream) {
     if (!op->pair_pending) return EFGP_OK;
     const int L0 = (int)op->Ls[0], L1 = (int)op->Ls[1];
-    const int rc = op->vhat48_ready ? toeplitz_vhat_fused_launch(op->v_ref, L0, L1, 1.0 / 4096.0, op->pair_target, stream)
+    const int rc = op->vhat48_ready ? toeplitz_vhat_fused_launch(op->v_ref, L0, L1, 1.0 / (double)kCells64, op->pair_target, stream)
                                     : toeplitz_vhat_pair_launch(op->v_ref, L0, L1, op->pair_target, op->vhat48, stream);
     if (rc != EFGP_OK) return rc;
     op->pair_pending = false;
@@ -2530,22 +2528,27 @@ static dim3 grid_for(int64_t work, int rows, int threads, int cap = 1024) {
     return dim3(blocks, rows);
 }
 
-// vhat = FFT(zero-padded v) / Ftot on the reference's grid, made on first use when the operator was created with a smaller
-// cooperative grid (efgp_toeplitz_create)
+// out = FFT(zero-padded v) / Ftot on grid g: the pad kernel with the lag box as its block (n := L; the inverse transform's 1 / Ftot
+// folded in before the FFT), then the transform
+static int make_spectrum(efgp_toeplitz_s* op, const ToepGeom& g, const double2* v, double2* out, hipStream_t stream) {
+    const ToepGeom gv = lag_geometry(g, op->Ls);
+    hipLaunchKernelGGL(pad_scale_kernel, grid_for(g.Ftot, 1, kVecThreads), dim3(kVecThreads), 0, stream, gv, v, gv.M, (const double2*)nullptr,
+                       (const int*)nullptr, (const int*)nullptr, out, 1.0 / (double)g.Ftot);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_error("Toeplitz spectrum: pad launch failed: %s", hipGetErrorString(e));
+        return EFGP_EHIP;
+    }
+    return fft_c2c(op->ctx, g.d, g.F, 1, out, true, stream);
+}
+
+// the spectrum on the reference's grid, made on first use when the operator was created with a smaller cooperative grid
+// (efgp_toeplitz_create_ex)
 static int ensure_reference_spectrum(efgp_toeplitz_s* op, hipStream_t stream) {
     const int rcd = ensure_deferred_spectra(op, stream);
     if (rcd != EFGP_OK) return rcd;
     if (op->vhat_ready) return EFGP_OK;
-    ToepGeom gv = op->g;
-    gv.M = 1;
-    for (int a = 0; a < 3; ++a) {
-        gv.n[a] = op->Ls[a];
-        gv.M *= gv.n[a];
-    }
-    hipLaunchKernelGGL(pad_scale_kernel, grid_for(op->g.Ftot, 1, kVecThreads), dim3(kVecThreads), 0, stream, gv, (const double2*)op->v_keep,
-                       gv.M, (const double2*)nullptr, (const int*)nullptr, (const int*)nullptr, op->vhat, 1.0 / (double)op->g.Ftot);
-    EFGP_HIP_CHECK(hipGetLastError());
-    int rc = fft_c2c(op->ctx, op->g.d, op->g.F, 1, op->vhat, true, stream);
+    const int rc = make_spectrum(op, op->g, op->v_keep, op->vhat, stream);
     if (rc != EFGP_OK) return rc;
     op->vhat_ready = true;
     pool_free(op->ctx, op->v_keep, op->v_keep_bytes);        // stream-ordered reuse: the pad launch above read it on this stream
@@ -2578,12 +2581,12 @@ static int circulant(efgp_toeplitz_s* op, double2* pad, int slots, hipStream_t s
 static bool ensure_centred_spectrum(efgp_toeplitz_s* op, hipStream_t stream) {
     if (op->vhat_c) return true;
     if (ensure_reference_spectrum(op, stream) != EFGP_OK) return false;
-    op->vhat_c = (double2*)pool_alloc(op->ctx, (size_t)op->g.Ftot * sizeof(double2));
+    op->vhat_c = (double2*)pool_alloc(op->ctx, spectrum_bytes(op->g));
     if (!op->vhat_c) return false;
     hipLaunchKernelGGL(center_spectrum_kernel, dim3((unsigned)((op->g.Ftot + 255) / 256)), dim3(256), 0, stream, op->vhat, op->tw[0],
                        op->tw[1], (int)op->g.n[0], (int)op->g.n[1], (int)op->g.F[0], (int)op->g.F[1], op->vhat_c);
     if (hipGetLastError() != hipSuccess) {
-        pool_free(op->ctx, op->vhat_c, (size_t)op->g.Ftot * sizeof(double2));
+        pool_free(op->ctx, op->vhat_c, spectrum_bytes(op->g));
         op->vhat_c = nullptr;
         return false;
     }
@@ -2633,7 +2636,7 @@ static int setup_apply_herm3(efgp_toeplitz_s* op, CgArgs& a, int rows, int* host
     DeviceCtx* ctx = op->ctx;
     const ToepGeom& g = op->g;
     if (!op->vc3) {
-        op->vc3 = (double*)pool_alloc(ctx, (size_t)g.Ftot * sizeof(double));
+        op->vc3 = (double*)pool_alloc(ctx, real_spectrum_bytes(g));
         if (!op->vc3) return EFGP_ENOMEM;
         hipLaunchKernelGGL(center_spectrum3_real_kernel, dim3((unsigned)((g.Ftot + 255) / 256)), dim3(256), 0, stream, op->vhat, op->tw[0],
                            op->tw[1], op->tw[2], (int)g.n[0], (int)g.n[1], (int)g.n[2], (int)g.F[0], (int)g.F[1], (int)g.F[2], op->vc3);
@@ -2683,11 +2686,11 @@ static int setup_apply_herm3(efgp_toeplitz_s* op, CgArgs& a, int rows, int* host
     ap->lds[2] = line_lds_bytes(lpb, g.F[2]);
     ap->lds[1] = line_lds_bytes(l3h.lpb_s, g.F[1]);
     ap->lds[0] = line_lds_bytes(l3h.lpb_m, g.F[0]);
-    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3h_fwd2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[2]));
-    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3h_inv2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[2]));
-    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3h_dim1_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[1]));
-    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3h_dim1_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[1]));
-    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3h_mid0_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[0]));
+    if (const int rc = raise_dynamic_lds((const void*)cg3h_fwd2_kernel, ap->lds[2], "CG line kernels")) return rc;
+    if (const int rc = raise_dynamic_lds((const void*)cg3h_inv2_kernel, ap->lds[2], "CG line kernels")) return rc;
+    if (const int rc = raise_dynamic_lds((const void*)cg3h_dim1_kernel<0>, ap->lds[1], "CG line kernels")) return rc;
+    if (const int rc = raise_dynamic_lds((const void*)cg3h_dim1_kernel<1>, ap->lds[1], "CG line kernels")) return rc;
+    if (const int rc = raise_dynamic_lds((const void*)cg3h_mid0_kernel, ap->lds[0], "CG line kernels")) return rc;
     a.nblk = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(std::min(kCgBlocksMax, knob("EFGP_CG_NBLK", 128)), (a.v_len + kVecThreads - 1) / kVecThreads),
                                                         std::max<int64_t>(1, 1024 / rows)));
     ap->kind = OperatorApply::kLines3H;
@@ -2713,9 +2716,9 @@ static int setup_apply(efgp_toeplitz_s* op, const CgSolve& s, CgArgs& a, int row
         la.nblk_rows = (int)((g.n[0] + la.lpb - 1) / la.lpb);
         ap->lds[1] = line_lds_bytes(la.lpb, g.F[1]);
         ap->lds[0] = line_lds_bytes(la.lpb, g.F[0]);
-        EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg_rows_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[1]));
-        EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg_rows_inv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[1]));
-        EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg_cols_mid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[0]));
+        if (const int rc = raise_dynamic_lds((const void*)cg_rows_fwd_kernel, ap->lds[1], "CG line kernels")) return rc;
+        if (const int rc = raise_dynamic_lds((const void*)cg_rows_inv_kernel, ap->lds[1], "CG line kernels")) return rc;
+        if (const int rc = raise_dynamic_lds((const void*)cg_cols_mid_kernel, ap->lds[0], "CG line kernels")) return rc;
         ap->kind = OperatorApply::kLines2;
         return EFGP_OK;
     }
@@ -2735,11 +2738,11 @@ static int setup_apply(efgp_toeplitz_s* op, const CgSolve& s, CgArgs& a, int row
     l3.nblk_lines = (int)((nlines + l3.lpb_c - 1) / l3.lpb_c);
     ap->lds[2] = line_lds_bytes(l3.lpb_c, g.F[2]);
     for (int q = 0; q < 2; ++q) ap->lds[q] = line_lds_bytes(l3.lpb_s, g.F[q]);
-    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3_fwd2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[2]));
-    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3_inv2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[2]));
-    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3_dim1_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[1]));
-    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3_dim1_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[1]));
-    EFGP_HIP_CHECK(hipFuncSetAttribute((const void*)cg3_mid0_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ap->lds[0]));
+    if (const int rc = raise_dynamic_lds((const void*)cg3_fwd2_kernel, ap->lds[2], "CG line kernels")) return rc;
+    if (const int rc = raise_dynamic_lds((const void*)cg3_inv2_kernel, ap->lds[2], "CG line kernels")) return rc;
+    if (const int rc = raise_dynamic_lds((const void*)cg3_dim1_kernel<0>, ap->lds[1], "CG line kernels")) return rc;
+    if (const int rc = raise_dynamic_lds((const void*)cg3_dim1_kernel<1>, ap->lds[1], "CG line kernels")) return rc;
+    if (const int rc = raise_dynamic_lds((const void*)cg3_mid0_kernel, ap->lds[0], "CG line kernels")) return rc;
     ap->kind = OperatorApply::kLines3;
     if (s.hermitian && (g.n[0] & 1) && (g.n[1] & 1) && (g.n[2] & 1) && g.n[0] >= 3 && std::getenv("EFGP_NO_CG_HERM3") == nullptr)
         return setup_apply_herm3(op, a, rows, host, stream, ap);
@@ -3052,6 +3055,118 @@ static int solve_multi_launch(efgp_toeplitz_s* op, const CgSolve& s, int* iters_
     return EFGP_OK;
 }
 
+// ---- operator creation: the steps of efgp_toeplitz_create_ex, in its order -------------------------------------------------------
+// A step that cannot be taken (no twiddle table, no pooled block, a failed launch) takes back what the plan decided on it.
+
+// block and twiddles of the 48 x 48 spectrum
+static void take_spectrum48(efgp_toeplitz_s* op, hipStream_t stream) {
+    const double2* tw48 = twiddle_table_for(op->ctx, 48, stream);
+    op->vhat48 = tw48 ? (double2*)pool_alloc(op->ctx, kSpectrum48Bytes) : nullptr;
+    if (op->vhat48) op->h48.tw = tw48;
+}
+
+// a copy of the lags, for the reference grid's spectrum on first use; false (nothing kept) when it cannot be made
+static bool keep_lags(efgp_toeplitz_s* op, size_t bytes, const void* v, hipStream_t stream) {
+    op->v_keep_bytes = bytes;
+    op->v_keep = (double2*)pool_alloc(op->ctx, bytes);
+    const bool ok = op->v_keep != nullptr && hipMemcpyAsync(op->v_keep, v, bytes, hipMemcpyDeviceToDevice, stream) == hipSuccess;
+    if (!ok && op->v_keep) {
+        pool_free(op->ctx, op->v_keep, bytes);
+        op->v_keep = nullptr;
+    }
+    op->vhat_ready = !ok;
+    return ok;
+}
+
+// The spectrum of a 64 x 64 grid (`target`: the own grid's, or the embedding's) in one launch.  While the 48 x 48 spectrum has a
+// block and is still to be made, the same launch carries it -- or, deferred, both are left pending (ensure_deferred_spectra).
+static int make_spectrum64(efgp_toeplitz_s* op, double2* target, const double2* v, bool defer_pair, bool* made48, hipStream_t stream) {
+    const int L0 = (int)op->Ls[0], L1 = (int)op->Ls[1];
+    if (!op->vhat48 || *made48) return toeplitz_vhat_fused_launch(v, L0, L1, 1.0 / (double)kCells64, target, stream);
+    if (defer_pair) {
+        op->pair_pending = true;
+        op->pair_target = target;
+        *made48 = true;
+        return EFGP_OK;
+    }
+    const int rc = toeplitz_vhat_pair_launch(v, L0, L1, target, op->vhat48, stream);
+    *made48 = rc == EFGP_OK;
+    return rc;
+}
+
+// twiddle tables of the own grid; without one, none of the kernels that transform in LDS runs
+static void take_twiddles(efgp_toeplitz_s* op, const OperatorPlan& pl, hipStream_t stream) {
+    op->persistent_ok = pl.eligible;
+    op->lines_ok = pl.lines_ok;
+    op->lines3_ok = pl.lines3_ok;
+    if (!op->persistent_ok && !op->lines_ok && !op->lines3_ok) return;
+    for (int a = 0; a < op->g.d; ++a) {
+        op->tw[a] = twiddle_table_for(op->ctx, op->g.F[a], stream);
+        if (op->tw[a]) continue;
+        op->persistent_ok = op->lines_ok = op->lines3_ok = false;
+        return;
+    }
+}
+
+// the cooperative solve's smaller grid: twiddles, block, and the spectrum there with the centring rotation in place
+static void make_small_coop_grid(efgp_toeplitz_s* op, const OperatorPlan& pl, const double2* v, hipStream_t stream) {
+    DeviceCtx* ctx = op->ctx;
+    op->g_co = pl.g_co;
+    op->tw_co[0] = twiddle_table_for(ctx, op->g_co.F[0], stream);
+    op->tw_co[1] = twiddle_table_for(ctx, op->g_co.F[1], stream);
+    op->vhat_co = (op->tw_co[0] && op->tw_co[1]) ? (double2*)pool_alloc(ctx, pl.vhat_co_bytes) : nullptr;
+    if (!op->vhat_co) return;
+    bool ok = make_spectrum(op, op->g_co, v, op->vhat_co, stream) == EFGP_OK;
+    if (ok) {
+        hipLaunchKernelGGL(center_spectrum_kernel, dim3((unsigned)((op->g_co.Ftot + 255) / 256)), dim3(256), 0, stream, op->vhat_co,
+                           op->tw_co[0], op->tw_co[1], (int)op->g.n[0], (int)op->g.n[1], (int)op->g_co.F[0], (int)op->g_co.F[1],
+                           op->vhat_co);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    if (ok) {
+        op->coop_small = true;
+        return;
+    }
+    (void)hipGetLastError();
+    pool_free(ctx, op->vhat_co, pl.vhat_co_bytes);
+    op->vhat_co = nullptr;
+}
+
+// the 64 x 64 embedding of the single-launch solves: block, twiddles, spectrum (any of them missing: they stay on the own grid)
+static void make_embedding64(efgp_toeplitz_s* op, const OperatorPlan& pl, const double2* v, bool defer_pair, bool* made48, hipStream_t stream) {
+    DeviceCtx* ctx = op->ctx;
+    op->g_cg = pl.g_cg;
+    op->vhat_cg = (double2*)pool_alloc(ctx, kSpectrum64Bytes);
+    bool ok = op->vhat_cg != nullptr;
+    if (ok) {
+        op->tw_cg[0] = op->tw_cg[1] = twiddle_table_for(ctx, 64, stream);
+        ok = op->tw_cg[0] != nullptr;
+    }
+    if (ok) ok = make_spectrum64(op, op->vhat_cg, v, defer_pair, made48, stream) == EFGP_OK;
+    if (ok) {
+        op->cg64 = true;
+        return;
+    }
+    (void)hipGetLastError();
+    if (op->vhat_cg) pool_free(ctx, op->vhat_cg, kSpectrum64Bytes);
+    op->vhat_cg = nullptr;
+}
+
+// pending spectra read the caller's lags on first use; a 48 x 48 block that no 64 x 64 launch carries (grid not on the fused path)
+// goes back: the Hermitian solves keep 64 x 64
+static void settle_spectrum48(efgp_toeplitz_s* op, const double2* v, bool made48) {
+    if (op->pair_pending) {
+        op->v_ref = v;
+        op->vhat48_ready = false;
+    }
+    if (op->vhat48 && made48) {
+        op->h48.vhat = op->vhat48;
+    } else if (op->vhat48) {
+        pool_free(op->ctx, op->vhat48, kSpectrum48Bytes);
+        op->vhat48 = nullptr;
+    }
+}
+
 }  // namespace efgp
 
 extern "C" {
@@ -3061,223 +3176,51 @@ int efgp_toeplitz_create(efgp_toeplitz_t** op_out, int device, int dim, const in
     return efgp_toeplitz_create_ex(op_out, device, dim, Ls, v, force_pow2, 0, stream_);
 }
 
-int efgp_toeplitz_create_ex(efgp_toeplitz_t** op_out, int device, int dim, const int64_t* Ls, const void* v, int force_pow2, int flags,
+int efgp_toeplitz_create_ex(efgp_toeplitz_t** op_out, int device, int dim, const int64_t* Ls, const void* v_, int force_pow2, int flags,
                             void* stream_) {
-    EFGP_REQUIRE(op_out && Ls && v, "efgp_toeplitz_create: null argument");
+    EFGP_REQUIRE(op_out && Ls && v_, "efgp_toeplitz_create: null argument");
     EFGP_REQUIRE((flags & ~EFGP_TOEPLITZ_DEFER_SPECTRA) == 0, "efgp_toeplitz_create_ex: unknown flags %d", flags);
     EFGP_REQUIRE(dim >= 1 && dim <= 3, "efgp_toeplitz_create: dim must be 1, 2 or 3 (got %d)", dim);
     for (int a = 0; a < dim; ++a) EFGP_REQUIRE(Ls[a] >= 1, "efgp_toeplitz_create: Ls[%d] < 1", a);
     DeviceCtx* ctx = device_ctx(device);
     if (!ctx) return EFGP_EHIP;
     hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard guard(device, (hipStream_t)stream_);
+    const double2* v = (const double2*)v_;
+    DeviceGuard guard(device, stream);
+    const OperatorPlan pl = plan_operator(dim, Ls, force_pow2, flags);
     auto* op = new efgp_toeplitz_s();
     op->device = device;
     op->ctx = ctx;
-    op->g.d = dim;
-    op->g.M = 1;
-    op->g.Ftot = 1;
-    for (int a = 0; a < 3; ++a) {
-        op->Ls[a] = a < dim ? Ls[a] : 1;
-        op->g.n[a] = a < dim ? (Ls[a] + 1) / 2 : 1;                       // efgpnd.py:1259
-        op->g.F[a] = a < dim ? (force_pow2 ? next_pow2(Ls[a]) : next_smooth_even(Ls[a])) : 1;   // :1269
-        op->g.M *= op->g.n[a];
-        op->g.Ftot *= op->g.F[a];
-    }
-    op->vhat = (double2*)pool_alloc(ctx, (size_t)op->g.Ftot * sizeof(double2));
-    if (!op->vhat) {
-        efgp_toeplitz_destroy(op);
-        return EFGP_ENOMEM;
-    }
-    // vhat = FFT(zero-padded v) / Ftot.  Reuse the pad kernel with n := L, i.e. a geometry whose block is L.
-    ToepGeom gv = op->g;
-    gv.M = 1;
-    for (int a = 0; a < 3; ++a) {
-        gv.n[a] = op->Ls[a];
-        gv.M *= gv.n[a];
-    }
-    int rc = EFGP_OK;
-    // Hermitian solves of blocks up to 23 x 23 run on the 48 x 48 circulant grid: its spectrum rides in the launch that makes the
-    // 64 x 64 one (this grid's, or the embedding's below)
-    const bool want48 = dim == 2 && op->g.n[0] == op->g.n[1] && (op->g.n[0] & 1) && op->g.n[0] <= 23 && op->g.F[0] <= 64 &&
-                        op->g.F[0] == op->g.F[1] && persistent_cg_eligible(op->g) && std::getenv("EFGP_NO_CG48") == nullptr &&
-                        std::getenv("EFGP_NO_CG64") == nullptr && std::getenv("EFGP_NO_CG_HERM") == nullptr;
-    if (want48) {
-        const double2* tw48 = twiddle_table_for(ctx, 48, stream);
-        op->vhat48 = tw48 ? (double2*)pool_alloc(ctx, (size_t)2304 * sizeof(double2)) : nullptr;
-        if (op->vhat48) op->h48.tw = tw48;
-    }
-    bool made48 = false;
-    // deferred: the launch that would make the 64 x 64 and 48 x 48 spectra together is left to the fused mean solve and to first use
-    const bool defer_pair = (flags & EFGP_TOEPLITZ_DEFER_SPECTRA) && op->vhat48 != nullptr && std::getenv("EFGP_NO_DEFER_SPECTRA") == nullptr;
-    // 2-D grids of the cooperative solve (128..512 per axis): when a smaller cooperative grid exists (made below) nothing on the
-    // fit path reads the reference grid's spectrum -- keep a copy of v and make it on first use
-    bool defer_ref = dim == 2 && std::getenv("EFGP_NO_COOP_SMALL") == nullptr && std::getenv("EFGP_EAGER_REF_SPECTRUM") == nullptr;
-    for (int a = 0; a < dim && defer_ref; ++a) {
-        const int64_t F = op->g.F[a];
-        defer_ref = F >= 128 && F <= 512 && (F & (F - 1)) == 0;
-    }
-    if (defer_ref) {
-        op->v_keep_bytes = (size_t)gv.M * sizeof(double2);
-        op->v_keep = (double2*)pool_alloc(ctx, op->v_keep_bytes);
-        defer_ref = op->v_keep != nullptr &&
-                    hipMemcpyAsync(op->v_keep, v, op->v_keep_bytes, hipMemcpyDeviceToDevice, stream) == hipSuccess;
-        if (!defer_ref && op->v_keep) {
-            pool_free(ctx, op->v_keep, op->v_keep_bytes);
-            op->v_keep = nullptr;
-        }
-        op->vhat_ready = !defer_ref;
-    }
-    if (defer_ref) {
-        // nothing now
-    } else if (toeplitz_vhat_fused_eligible(op->g)) {
-        if (op->vhat48 && defer_pair) {
-            op->pair_pending = true;
-            op->pair_target = op->vhat;
-            made48 = true;
-        } else if (op->vhat48) {
-            rc = toeplitz_vhat_pair_launch((const double2*)v, (int)op->Ls[0], (int)op->Ls[1], op->vhat, op->vhat48, stream);
-            made48 = rc == EFGP_OK;
-        } else {
-            rc = toeplitz_vhat_fused_launch((const double2*)v, (int)op->Ls[0], (int)op->Ls[1], 1.0 / (double)op->g.Ftot, op->vhat,
-                                            stream);
-        }
-    } else {
-        hipLaunchKernelGGL(pad_scale_kernel, grid_for(op->g.Ftot, 1, kVecThreads), dim3(kVecThreads), 0, stream, gv,
-                           (const double2*)v, gv.M, (const double2*)nullptr, (const int*)nullptr, (const int*)nullptr,
-                           op->vhat, 1.0 / (double)op->g.Ftot);   // the inverse transform's 1/Ftot, folded in before the FFT
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            efgp_toeplitz_destroy(op);          // vhat, and vhat48 / v_keep where they were taken
-            set_error("efgp_toeplitz_create: pad launch failed: %s", hipGetErrorString(e));
-            return EFGP_EHIP;
-        }
-        rc = fft_c2c(ctx, dim, op->g.F, 1, op->vhat, true, stream);
-    }
-    if (rc != EFGP_OK) {
+    op->g = pl.g;
+    for (int a = 0; a < 3; ++a) op->Ls[a] = pl.Ls[a];
+    auto fail = [op](int rc) {          // every failure frees what was taken so far
         efgp_toeplitz_destroy(op);
         return rc;
+    };
+    op->vhat = (double2*)pool_alloc(ctx, pl.vhat_bytes);
+    if (!op->vhat) return fail(EFGP_ENOMEM);
+    if (pl.want48) take_spectrum48(op, stream);
+    const bool defer_pair = pl.defer_pair && op->vhat48 != nullptr;
+    bool made48 = false;
+    int rc = EFGP_OK;
+    if (pl.defer_ref && keep_lags(op, pl.v_keep_bytes, v, stream)) {
+        // nothing now: ensure_reference_spectrum
+    } else if (pl.vhat_fused) {
+        rc = make_spectrum64(op, op->vhat, v, defer_pair, &made48, stream);
+    } else {
+        rc = make_spectrum(op, op->g, v, op->vhat, stream);
     }
-    op->persistent_ok = persistent_cg_eligible(op->g);
-    op->lines_ok = dim == 2;
-    for (int a = 0; a < dim && op->lines_ok; ++a) {
-        const int64_t F = op->g.F[a];
-        op->lines_ok = F >= 128 && F <= 512 && (F & (F - 1)) == 0;
-    }
-    op->lines3_ok = dim == 3;
-    for (int a = 0; a < dim && op->lines3_ok; ++a) {
-        const int64_t F = op->g.F[a];
-        op->lines3_ok = F >= 64 && F <= 256 && (F & (F - 1)) == 0;
-    }
-    if (op->persistent_ok || op->lines_ok || op->lines3_ok) {
-        for (int a = 0; a < dim; ++a) {
-            op->tw[a] = twiddle_table_for(ctx, op->g.F[a], stream);
-            if (op->tw[a]) continue;
-            op->persistent_ok = false;
-            op->lines_ok = false;
-            op->lines3_ok = false;
-            break;
-        }
-    }
-    if (op->lines_ok && std::getenv("EFGP_NO_COOP_SMALL") == nullptr) {
-        static const int64_t ladder[] = {96, 128, 192, 256, 384, 512};
-        op->g_co = op->g;
-        op->g_co.Ftot = 1;
-        bool smaller = false;
-        for (int a = 0; a < 2; ++a) {
-            for (int64_t c : ladder)
-                if (c >= op->Ls[a]) {
-                    op->g_co.F[a] = c;
-                    break;
-                }
-            smaller = smaller || op->g_co.F[a] < op->g.F[a];
-            op->g_co.Ftot *= op->g_co.F[a];
-        }
-        if (smaller) {
-            op->tw_co[0] = twiddle_table_for(ctx, op->g_co.F[0], stream);
-            op->tw_co[1] = twiddle_table_for(ctx, op->g_co.F[1], stream);
-            op->vhat_co = (op->tw_co[0] && op->tw_co[1]) ? (double2*)pool_alloc(ctx, (size_t)op->g_co.Ftot * sizeof(double2)) : nullptr;
-            if (op->vhat_co) {
-                // spectrum on the small grid: FFT(zero-padded v) / Ftot, then the centring rotation in place
-                ToepGeom gp = op->g_co;
-                gp.M = 1;
-                for (int a = 0; a < 3; ++a) {
-                    gp.n[a] = op->Ls[a];
-                    gp.M *= gp.n[a];
-                }
-                hipLaunchKernelGGL(pad_scale_kernel, grid_for(gp.Ftot, 1, kVecThreads), dim3(kVecThreads), 0, stream, gp, (const double2*)v, gp.M,
-                                   (const double2*)nullptr, (const int*)nullptr, (const int*)nullptr, op->vhat_co, 1.0 / (double)gp.Ftot);
-                bool ok = hipGetLastError() == hipSuccess && fft_c2c(ctx, 2, op->g_co.F, 1, op->vhat_co, true, stream) == EFGP_OK;
-                if (ok) {
-                    hipLaunchKernelGGL(center_spectrum_kernel, dim3((unsigned)((op->g_co.Ftot + 255) / 256)), dim3(256), 0, stream, op->vhat_co,
-                                       op->tw_co[0], op->tw_co[1], (int)op->g.n[0], (int)op->g.n[1], (int)op->g_co.F[0], (int)op->g_co.F[1],
-                                       op->vhat_co);
-                    ok = hipGetLastError() == hipSuccess;
-                }
-                if (ok) {
-                    op->coop_small = true;
-                } else {
-                    (void)hipGetLastError();
-                    pool_free(ctx, op->vhat_co, (size_t)op->g_co.Ftot * sizeof(double2));
-                    op->vhat_co = nullptr;
-                }
-            }
-        }
-    }
+    if (rc != EFGP_OK) return fail(rc);
+    take_twiddles(op, pl, stream);
+    if (op->lines_ok && pl.coop_small) make_small_coop_grid(op, pl, v, stream);
     // the centred spectrum on the reference's grid: needed by the cooperative solve only when it runs there (no smaller grid, or
     // EFGP_NO_COOP_SMALL later on: built on first use then)
-    if (!op->vhat_ready && !op->coop_small) {
-        rc = ensure_reference_spectrum(op, stream);
-        if (rc != EFGP_OK) {
-            efgp_toeplitz_destroy(op);
-            return rc;
-        }
-    }
+    if (!op->vhat_ready && !op->coop_small && (rc = ensure_reference_spectrum(op, stream)) != EFGP_OK) return fail(rc);
     if (op->lines_ok && !op->coop_small) (void)ensure_centred_spectrum(op, stream);
-    if (dim == 2 && op->persistent_ok && op->g.n[0] == op->g.n[1] && op->g.F[0] == op->g.F[1] && op->g.F[0] < 64 &&
-        op->Ls[0] <= 63 && std::getenv("EFGP_NO_CG64_EMBED") == nullptr && std::getenv("EFGP_NO_CG64") == nullptr) {
-        op->g_cg = op->g;
-        op->g_cg.F[0] = op->g_cg.F[1] = 64;
-        op->g_cg.Ftot = 64 * 64;
-        op->vhat_cg = (double2*)pool_alloc(ctx, (size_t)4096 * sizeof(double2));
-        bool ok = op->vhat_cg != nullptr;
-        if (ok) {
-            op->tw_cg[0] = op->tw_cg[1] = twiddle_table_for(ctx, 64, stream);
-            ok = op->tw_cg[0] != nullptr;
-        }
-        if (ok) {
-            if (op->vhat48 && !made48 && defer_pair) {
-                op->pair_pending = true;
-                op->pair_target = op->vhat_cg;
-                made48 = true;
-            } else if (op->vhat48 && !made48) {
-                ok = toeplitz_vhat_pair_launch((const double2*)v, (int)op->Ls[0], (int)op->Ls[1], op->vhat_cg, op->vhat48, stream) == EFGP_OK;
-                made48 = ok;
-            } else {
-                ok = toeplitz_vhat_fused_launch((const double2*)v, (int)op->Ls[0], (int)op->Ls[1], 1.0 / 4096.0, op->vhat_cg, stream) == EFGP_OK;
-            }
-        }
-        if (ok) {
-            op->cg64 = true;
-        } else {
-            (void)hipGetLastError();
-            if (op->vhat_cg) pool_free(ctx, op->vhat_cg, (size_t)4096 * sizeof(double2));
-            op->vhat_cg = nullptr;
-        }
-    }
-    // a single mode on a grid of one cell (and no 64 x 64 embedding): the single-launch kernels have no transform stage to run
-    // there (persistent_cg_launch); the multi-launch solver skips axes of extent 1 in its transforms and solves the scalar system
+    if (pl.embed64 && op->persistent_ok) make_embedding64(op, pl, v, defer_pair, &made48, stream);
+    // a grid of one cell without the embedding: no transform stage for the single-launch kernels (plan_operator)
     if (op->g.Ftot == 1 && !op->cg64) op->persistent_ok = false;
-    if (op->pair_pending) {
-        op->v_ref = (const double2*)v;
-        op->vhat48_ready = false;
-    }
-    if (op->vhat48 && made48) {
-        op->h48.vhat = op->vhat48;
-    } else if (op->vhat48) {          // no 64 x 64 launch carried it (grid not on the fused path): the Hermitian solves keep 64 x 64
-        pool_free(ctx, op->vhat48, (size_t)2304 * sizeof(double2));
-        op->vhat48 = nullptr;
-    }
+    settle_spectrum48(op, v, made48);
     *op_out = op;
     return EFGP_OK;
 }
@@ -3287,13 +3230,13 @@ int efgp_toeplitz_destroy(efgp_toeplitz_t* op) {
     DeviceGuard guard(op->device);
     // the spectrum block goes back to the pool; work already enqueued on the caller's stream that reads it
     // finishes before any later enqueue on that stream can overwrite a recycled block (single stream)
-    if (op->vhat) pool_free(op->ctx, op->vhat, (size_t)op->g.Ftot * sizeof(double2));
-    if (op->vhat_cg) pool_free(op->ctx, op->vhat_cg, (size_t)4096 * sizeof(double2));
-    if (op->vhat48) pool_free(op->ctx, op->vhat48, (size_t)2304 * sizeof(double2));
-    if (op->vhat_c) pool_free(op->ctx, op->vhat_c, (size_t)op->g.Ftot * sizeof(double2));
-    if (op->vhat_co) pool_free(op->ctx, op->vhat_co, (size_t)op->g_co.Ftot * sizeof(double2));
+    if (op->vhat) pool_free(op->ctx, op->vhat, spectrum_bytes(op->g));
+    if (op->vhat_cg) pool_free(op->ctx, op->vhat_cg, kSpectrum64Bytes);
+    if (op->vhat48) pool_free(op->ctx, op->vhat48, kSpectrum48Bytes);
+    if (op->vhat_c) pool_free(op->ctx, op->vhat_c, spectrum_bytes(op->g));
+    if (op->vhat_co) pool_free(op->ctx, op->vhat_co, spectrum_bytes(op->g_co));
     if (op->v_keep) pool_free(op->ctx, op->v_keep, op->v_keep_bytes);
-    if (op->vc3) pool_free(op->ctx, op->vc3, (size_t)op->g.Ftot * sizeof(double));
+    if (op->vc3) pool_free(op->ctx, op->vc3, real_spectrum_bytes(op->g));
     delete op;
     return EFGP_OK;
 }
@@ -3311,13 +3254,7 @@ int efgp_toeplitz_single_launch_solves(efgp_toeplitz_t* op) {
 
 int efgp_toeplitz_cg_shape(efgp_toeplitz_t* op, int hermitian, int64_t* shape_out) {
     EFGP_REQUIRE(op && shape_out, "efgp_toeplitz_cg_shape: null argument");
-    for (int a = 0; a < op->g.d; ++a) shape_out[a] = op->g.F[a];
-    if (op->g.d == 2 && op->persistent_ok) {
-        if (hermitian && op->h48.vhat && std::getenv("EFGP_NO_CG48") == nullptr) shape_out[0] = shape_out[1] = 48;
-        else if (op->cg64) shape_out[0] = shape_out[1] = 64;
-    } else if (op->coop_small && std::getenv("EFGP_NO_COOP_SMALL") == nullptr && std::getenv("EFGP_NO_CG_COOP") == nullptr) {
-        for (int a = 0; a < 2; ++a) shape_out[a] = op->g_co.F[a];
-    }
+    cg_solve_shape(op->g, op->persistent_ok, op->h48.vhat != nullptr, op->cg64, op->coop_small ? &op->g_co : nullptr, hermitian, shape_out);
     return EFGP_OK;
 }
 
@@ -3407,84 +3344,102 @@ int efgp_internal_cg_single_launch(efgp_toeplitz_s* op, const void* ws, double s
     return enqueue_persistent(op, s, row_iters_dev, stream);
 }
 
-// Enqueues the cooperative solve of `nbatch` systems on a 2-D 128^2..512^2 grid (cg_coop2d_kernel).  Few systems: G = 32-64
-// workgroups per system (latency); many systems (variance / trace probes): as few workgroups per system as the registers
-// allow, G = 1 when the mode block has <= 2048 entries -- no grid barrier, one system per CU (throughput).  Iteration counts
-// go to d_iters (device, nbatch ints; -3 where a grid barrier died), *d_status (device int) is non-zero when one did.
-// EFGP_EUNSUPPORTED when no launch shape fits.
+// ---- the cooperative solve -------------------------------------------------------------------------------------------------------
+// what a synchronous caller needs after the enqueue: the status word, the shape that ran, the diagnostic stamps
 struct CoopInfo {
     int* d_status = nullptr;
-    int G = 0, rows_wg = 0, lines = 0, cols_wg = 0, per = 0;
+    CoopShape shape;
     double* stamps = nullptr;
     int dbg = 0;
-    bool herm = false;
 };
-static int coop_enqueue(efgp_toeplitz_s* op, const CgSolve& s, int* d_iters, hipStream_t stream, CoopInfo* info, int nan_on_dead) {
-    const int nbatch = s.nbatch;
-    DeviceCtx* ctx = op->ctx;
-    const bool small = op->coop_small && std::getenv("EFGP_NO_COOP_SMALL") == nullptr;
-    const ToepGeom g = small ? op->g_co : op->g;
-    const int F0 = (int)g.F[0], F1 = (int)g.F[1], n0 = (int)g.n[0], n1 = (int)g.n[1];
-    // Hermitian systems (the caller's promise, checked by the kernel): rows k0 >= 0 only, column pairs (cg_coop2d_herm_kernel)
-    const bool herm = s.hermitian && (n0 & 1) && (n1 & 1) && n0 >= 3 && std::getenv("EFGP_NO_CG_COOP_HERM") == nullptr;
-    const int nrow = herm ? (n0 + 1) / 2 : n0;            // rows of the mode block the workgroups share out
-    const int ncol = herm ? F1 / 2 : F1;                  // column lines (pairs) they share out
-    // workgroups per system: as many as the latency shape uses (16 / 32 / 64) while the whole batch stays resident (one
-    // workgroup per CU), never fewer than the registers need (8 vector entries per thread)
-    int G_lat = F1 / 8;      // 16 / 32 / 64 (measured at 128^2: 19.9 us per iteration with 16 workgroups, 22.7 with 32, 20.6 with 8)
-    if (herm && F1 <= 256) G_lat = F1 / 16;   // half the work per system: 8 / 16 workgroups measured best at 128^2 / 256^2, 64 at 512^2
-    if (const char* ed = std::getenv("EFGP_COOP_GDIV")) G_lat = std::max(1, F1 / std::max(1, std::atoi(ed)));  // experiments: G = F1 / div
-    if (const char* eg = std::getenv("EFGP_COOP_G")) G_lat = std::max(1, std::min(G_lat, std::atoi(eg)));   // experiments
-    // the workgroup counts a grid offers: G_lat halved while it stays whole (16 8 4 2 1; 12 6 3 1 on the 48 R grids)
-    auto halve = [](int Gv) { return Gv > 1 ? ((Gv & 1) ? 1 : Gv / 2) : 1; };
-    int G_min = G_lat;       // the smallest count whose rows still fit a workgroup's registers (8 vector entries per thread)
-    while (G_min > 1 && ((nrow + halve(G_min) - 1) / halve(G_min)) * n1 <= 8 * kLineThreads) G_min = halve(G_min);
-    if (const char* eg = std::getenv("EFGP_COOP_GMIN")) {                                                       // experiments
-        int Gv = G_lat;
-        while (Gv > G_min && halve(Gv) >= std::atoi(eg)) Gv = halve(Gv);
-        G_min = std::max(G_min, Gv);
+
+// diagnostic runs of the cooperative solve (EFGP_COOP_DBG=2): the phase shares of workgroup 0, system 0
+static int coop_print_stamps(const CoopInfo& ci, int iters0) {
+    const CoopShape& sh = ci.shape;
+    double hs[14];
+    EFGP_HIP_CHECK(hipMemcpy(hs, ci.stamps, sizeof(hs), hipMemcpyDeviceToHost));
+    const char* nm[14] = {"R store to b1", "barrier 1", "C store", "barrier 2", "Ri load+fft", "pAp sum (incl. barrier)", "update", "rr/rz sum (incl. barrier)",
+                          "C load", "C transform 1 (+ multiply)", "-", "C transform 2", "R zero fill, ws u", "R transform"};
+    double tot = 0;
+    for (int q = 0; q < 14; ++q) tot += hs[q];
+    std::fprintf(stderr, "[coop] G = %d, rows/wg %d, lines/pass %d, columns/wg %d, systems/launch %d\n", sh.G, sh.rows_wg, sh.lines, sh.cols_wg, sh.per);
+    for (int q = 0; q < 14; ++q) std::fprintf(stderr, "[coop] %-28s %9.0f cycles/iter %5.1f%%\n", nm[q], hs[q] / std::max(1, iters0), 100.0 * hs[q] / tot);
+    return EFGP_OK;
+}
+// ... of the Hermitian kernel: waits for the solve and prints at once
+static int coop_print_herm_stamps(const CoopShape& sh, const double* stamps, const int* d_iters, hipStream_t stream) {
+    double hs[12];
+    int it0 = 0;
+    EFGP_HIP_CHECK(stream_wait(stream));
+    EFGP_HIP_CHECK(hipMemcpy(hs, stamps, sizeof(hs), hipMemcpyDeviceToHost));
+    EFGP_HIP_CHECK(hipMemcpy(&it0, d_iters, sizeof(int), hipMemcpyDeviceToHost));
+    const char* nm[10] = {"partial <r,r>, <r,z>", "R: rows of ws z -> b1", "barrier 1 + all-reduce", "beta, p update", "C: loads b1/b3, assemble",
+                          "C: transform, spectrum, transform", "C: unpack, stores to b2", "barrier 2 + all-reduce", "Ri: loads of b2", "Ri: transform, A p, x r z"};
+    double tot = 0;
+    for (int q = 0; q < 10; ++q) tot += hs[q];
+    std::fprintf(stderr, "[coop-herm] G = %d, rows/wg %d, lines/pass %d, column pairs/wg %d, systems/launch %d, %d iterations\n", sh.G, sh.rows_wg, sh.lines, sh.cols_wg, sh.per, it0);
+    for (int q = 0; q < 10; ++q) std::fprintf(stderr, "[coop-herm] %-36s %9.0f ticks/iter %5.1f%%\n", nm[q], hs[q] / std::max(1, it0), 100.0 * hs[q] / tot);
+    return EFGP_OK;
+}
+
+// The kernel of a launch shape, by (Hermitian, 8 vector entries per thread, G == 1).  One combination has no kernel: the general
+// solve with G = 1 and at most 1024 vector entries.  A cooperative grid has F >= 128 on the reference's grid, so n >= 33 per axis,
+// and a workgroup that owns a whole system then holds n0 n1 >= 1089 > 1024 entries: ks is 8 (tools/cg_plan_check.cpp --sweep walks
+// every block and batch size and asserts it).  coop_enqueue answers EFGP_EUNSUPPORTED for it like for a shape that does not fit.
+using CoopKernel = void (*)(CoopArgs);
+static CoopKernel coop_kernel(const CoopShape& sh) {
+    static const CoopKernel table[2][2][2] = {
+        {{cg_coop2d_kernel<4, false>, nullptr}, {cg_coop2d_kernel<8, false>, cg_coop2d_kernel<8, true>}},
+        {{cg_coop2d_herm_kernel<4, false>, cg_coop2d_herm_kernel<4, true>}, {cg_coop2d_herm_kernel<8, false>, cg_coop2d_herm_kernel<8, true>}}};
+    return table[sh.herm ? 1 : 0][sh.ks == 8 ? 1 : 0][sh.G == 1 ? 1 : 0];
+}
+
+// One cooperative launch of nsys systems.  The hand-rolled grid barrier needs every workgroup of a launch resident: at most one
+// workgroup per CU is asked for (G * nsys <= num_cu: coop_shape), so it is enough that ONE fits a CU with these registers and this
+// much LDS -- asked once per (device, kernel, LDS size), the query is a host round trip into the runtime.
+static int launch_coop(CoopKernel kern, int device, const CoopShape& sh, int nsys, const CoopArgs& ca, hipStream_t stream) {
+    if (const int rc = raise_dynamic_lds((const void*)kern, sh.lds, "cooperative CG")) return rc;
+    static std::mutex mu;
+    static std::map<std::tuple<int, const void*, size_t>, bool> fits;
+    const auto key = std::make_tuple(device, (const void*)kern, sh.lds);
+    bool known;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        known = fits.count(key) != 0;
     }
-    int G = G_lat;
-    while (G > G_min && (int64_t)G * nbatch > ctx->num_cu) G = halve(G);
-    const int ks = ((nrow + G - 1) / G) * n1 <= 4 * kLineThreads ? 4 : 8;
-    // columns per LDS pass: as many as the workgroup owns, the per-thread load registers (16) and the LDS allow -- a pass of
-    // 8 columns leaves one work item per thread and stage (latency bound: 134 us per iteration of a 128^2 system on one CU
-    // with 8, 4 items with 32).  Hermitian: a line is a column PAIR and a thread loads two values per (k0, line) slot.
-    const int load_cap = herm ? (kCoopLoads / 2) * kLineThreads / nrow : kCoopLoads * kLineThreads / F0;
-    int lpbc = 1;
-    while (lpbc * 2 <= std::min(ncol / G, load_cap)) lpbc <<= 1;
-    // LDS of a column pass: two images of lpbc lines (+ the Hermitian kernel's slice of the spectrum).  (Until late in round 4 the
-    // bound was four images: half the columns per pass -- 96^2, one system per workgroup: 50 -> 42 us per iteration; 384^2
-    // general: 30.7 -> 26.9.)
-    const size_t lds_factor = std::getenv("EFGP_COOP_LDSF") ? (size_t)std::atoi(std::getenv("EFGP_COOP_LDSF")) : (herm ? 3 : 2);
-    while (lpbc > 4 && (lds_factor * lpbc * (F0 + 1) + (size_t)F0 + (size_t)F1) * sizeof(double2) + 2048 > (size_t)ctx->max_lds) lpbc >>= 1;
-    while (lpbc > 1 && (ncol / G) % lpbc) lpbc >>= 1;           // a pass count per workgroup must be whole (48 R grids: 3 * 2^k lines)
-    bool shape_ok = G <= kCoopMaxG && ((nrow + G - 1) / G) * n1 <= ks * kLineThreads && ncol % (G * lpbc) == 0;
-    const int rows_wg = (nrow + G - 1) / G, cols_wg = ncol / G;
-    int lines = std::min(rows_wg, kCoopLoads * kLineThreads / F1);
-    auto lds_for = [&](int ln) {
-        const size_t bufsz = (size_t)std::max(ln * (F1 + 1), lpbc * (F0 + 1));
-        return (2 * bufsz + (size_t)F1 + (F0 == F1 ? 0 : (size_t)F0)) * sizeof(double2);
-    };
-    while (lines > 1 && lds_for(lines) + 2048 > (size_t)ctx->max_lds) --lines;
-    size_t lds = lds_for(lines);
-    // Hermitian, one column pass per workgroup: its slice of the spectrum stays in LDS (16-32 KB)
-    const size_t spec_bytes = (size_t)F0 * lpbc * sizeof(double2);
-    const bool spec_lds = herm && cols_wg == lpbc && lds + spec_bytes + 2048 <= (size_t)ctx->max_lds &&
-                          std::getenv("EFGP_NO_COOP_SPEC_LDS") == nullptr;
-    if (spec_lds) lds += spec_bytes;
-    shape_ok = shape_ok && lds + 2048 <= (size_t)ctx->max_lds && G <= ctx->num_cu &&
-               (herm ? lpbc * nrow <= (kCoopLoads / 2) * kLineThreads : lpbc * F0 <= kCoopLoads * kLineThreads);
-    if (!shape_ok) return EFGP_EUNSUPPORTED;
-    const int cap = std::max(1, ctx->num_cu / G);                      // systems resident at once (one workgroup per CU)
-    const int per = std::min(cap, nbatch);
-    const size_t grid_elems = (size_t)per * (size_t)n0 * (size_t)F1;
-    double2* pad = (double2*)scratch(ctx, SLOT_TOEP_PAD, 3 * grid_elems * sizeof(double2));
-    // partial sums | arrival counters (64 B apart) | status
-    const size_t off_bar = (size_t)per * 3 * kCoopMaxG * sizeof(double);
-    const size_t off_status = off_bar + (size_t)per * 64;
-    char* scb = (char*)scratch(ctx, SLOT_MISC, off_status + 64 + 128);
-    if (!pad || !scb) return EFGP_ENOMEM;
+    if (!known) {
+        int fit = 0;
+        EFGP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, kern, kLineThreads, sh.lds));
+        if (fit < 1) {
+            set_error("cooperative CG: no workgroup with %zu bytes of LDS fits a CU", sh.lds);
+            return EFGP_EHIP;
+        }
+        std::lock_guard<std::mutex> lk(mu);
+        fits[key] = true;
+    }
+    hipLaunchKernelGGL(kern, dim3(sh.G, nsys), dim3(kLineThreads), sh.lds, stream, ca);
+    EFGP_HIP_CHECK(hipGetLastError());
+    return EFGP_OK;
+}
+
+// scratch of one launch of sh.per systems: three intermediate grids | partial sums | arrival counters (64 B apart) | status | stamps
+struct CoopScratch {
+    double2* pad = nullptr;
+    char* scb = nullptr;
+    size_t grid_elems = 0, off_bar = 0, off_status = 0;
+};
+static bool coop_scratch(DeviceCtx* ctx, const ToepGeom& g, const CoopShape& sh, CoopScratch* sc) {
+    sc->grid_elems = (size_t)sh.per * (size_t)g.n[0] * (size_t)g.F[1];
+    sc->pad = (double2*)scratch(ctx, SLOT_TOEP_PAD, 3 * sc->grid_elems * sizeof(double2));
+    sc->off_bar = (size_t)sh.per * 3 * kCoopMaxG * sizeof(double);
+    sc->off_status = sc->off_bar + (size_t)sh.per * 64;
+    sc->scb = (char*)scratch(ctx, SLOT_MISC, sc->off_status + 64 + 128);
+    return sc->pad && sc->scb;
+}
+
+// the kernel's arguments but for the slab of systems (b, x, iters, hist: set per launch)
+static CoopArgs coop_args(const efgp_toeplitz_s* op, const CgSolve& s, const ToepGeom& g, bool small, const CoopShape& sh, const CoopScratch& sc,
+                          int nan_on_dead, bool test_dead) {
     CoopArgs ca;
     ca.g = g;
     ca.ws = s.ws;
@@ -3498,67 +3453,51 @@ static int coop_enqueue(efgp_toeplitz_s* op, const CgSolve& s, int* d_iters, hip
     ca.early_stop = s.early_stop;
     ca.batched = s.batched;
     ca.max_iter = s.max_iter;
-    if (!small && !ensure_centred_spectrum(op, stream)) return EFGP_EUNSUPPORTED;
     ca.vhat = small ? op->vhat_co : op->vhat_c;
     ca.tw0 = small ? op->tw_co[0] : op->tw[0];
     ca.tw1 = small ? op->tw_co[1] : op->tw[1];
-    ca.b1 = pad;
-    ca.b2 = pad + grid_elems;
-    ca.b3 = pad + 2 * grid_elems;
-    ca.spec_lds = spec_lds ? 1 : 0;
-    ca.partial = (double*)scb;
-    ca.bar = (unsigned*)(scb + off_bar);
-    ca.status = (int*)(scb + off_status);
+    ca.b1 = sc.pad;
+    ca.b2 = sc.pad + sc.grid_elems;
+    ca.b3 = sc.pad + 2 * sc.grid_elems;
+    ca.spec_lds = sh.spec_lds ? 1 : 0;
+    ca.partial = (double*)sc.scb;
+    ca.bar = (unsigned*)(sc.scb + sc.off_bar);
+    ca.status = (int*)(sc.scb + sc.off_status);
     ca.hist_cap = cg_history().capacity;
     ca.nan_on_dead = nan_on_dead;
-    ca.G = G;
+    ca.G = sh.G;
+    ca.bar_need = test_dead ? sh.G + 1 : sh.G;
+    ca.rows_wg = sh.rows_wg;
+    ca.cols_wg = sh.cols_wg;
+    ca.lines = sh.lines;
+    ca.lpbc = sh.lpbc;
+    ca.dbg = std::getenv("EFGP_COOP_DBG") ? std::atoi(std::getenv("EFGP_COOP_DBG")) : 0;
+    ca.stamps = (double*)(sc.scb + sc.off_status + 64);
+    return ca;
+}
+
+// Enqueues the cooperative solve of `nbatch` systems on a 2-D 128^2..512^2 grid in the launch shape coop_shape gives.  Iteration
+// counts go to d_iters (device, nbatch ints; -3 where a grid barrier died), *d_status (device int) is non-zero when one did.
+// EFGP_EUNSUPPORTED when no launch shape fits.
+static int coop_enqueue(efgp_toeplitz_s* op, const CgSolve& s, int* d_iters, hipStream_t stream, CoopInfo* info, int nan_on_dead) {
+    const int nbatch = s.nbatch;
+    const bool small = op->coop_small && std::getenv("EFGP_NO_COOP_SMALL") == nullptr;
+    const ToepGeom g = small ? op->g_co : op->g;
+    const CoopShape sh = coop_shape(g, nbatch, s.hermitian != 0, op->ctx->num_cu, op->ctx->max_lds);
+    const CoopKernel kern = coop_kernel(sh);
+    if (!sh.ok || !kern) return EFGP_EUNSUPPORTED;
+    CoopScratch sc;
+    if (!coop_scratch(op->ctx, g, sh, &sc)) return EFGP_ENOMEM;
+    if (!small && !ensure_centred_spectrum(op, stream)) return EFGP_EUNSUPPORTED;
     // test hook (tests/test_gpu_variance_ops.py): every grid barrier of this launch dies at once -- one arrival more than there
     // are workgroups is awaited and the status word is preset, so the first status check (256 polls) ends the wait
-    const bool test_dead = G > 1 && std::getenv("EFGP_COOP_TEST_DEAD") != nullptr;
-    ca.bar_need = test_dead ? G + 1 : G;
-    ca.rows_wg = rows_wg;
-    ca.cols_wg = cols_wg;
-    ca.lines = lines;
-    ca.lpbc = lpbc;
-    ca.dbg = std::getenv("EFGP_COOP_DBG") ? std::atoi(std::getenv("EFGP_COOP_DBG")) : 0;
-    ca.stamps = (double*)(scb + off_status + 64);
+    const bool test_dead = sh.G > 1 && std::getenv("EFGP_COOP_TEST_DEAD") != nullptr;
+    CoopArgs ca = coop_args(op, s, g, small, sh, sc, nan_on_dead, test_dead);
     if (ca.dbg == 2) EFGP_HIP_CHECK(hipMemsetAsync(ca.stamps, 0, 128, stream));
-    auto launch = [&](auto kern, int nsys) -> hipError_t {
-        // attribute and occupancy query once per (device, kernel, LDS size): both are host round trips into the runtime.  The
-        // attribute is a per-kernel maximum: it is only ever raised.
-        static std::mutex mu;
-        static std::map<std::pair<int, const void*>, size_t> attr_set;
-        static std::map<std::tuple<int, const void*, size_t>, bool> fits;
-        bool raise_attr, known;
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            auto it = attr_set.find(std::make_pair(op->device, (const void*)kern));
-            raise_attr = it == attr_set.end() || it->second < lds;
-            known = fits.count(std::make_tuple(op->device, (const void*)kern, lds)) != 0;
-        }
-        if (raise_attr) {
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-            std::lock_guard<std::mutex> lk(mu);
-            attr_set[std::make_pair(op->device, (const void*)kern)] = lds;
-        }
-        if (!known) {
-            // the hand-rolled grid barrier needs every workgroup of a launch resident: at most one workgroup per CU is asked for
-            // (G * nsys <= num_cu above), so it is enough that ONE fits a CU with these registers and this much LDS
-            int fit = 0;
-            hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, kern, kLineThreads, lds);
-            if (e != hipSuccess) return e;
-            if (fit < 1) return hipErrorLaunchOutOfResources;
-            std::lock_guard<std::mutex> lk(mu);
-            fits[std::make_tuple(op->device, (const void*)kern, lds)] = true;
-        }
-        hipLaunchKernelGGL(kern, dim3(G, nsys), dim3(kLineThreads), lds, stream, ca);
-        return hipGetLastError();
-    };
     {
         KernelTimer timer("cg_coop", stream);
-        for (int s0 = 0; s0 < nbatch; s0 += per) {
-            const int nsys = std::min(per, nbatch - s0);
+        for (int s0 = 0; s0 < nbatch; s0 += sh.per) {
+            const int nsys = std::min(sh.per, nbatch - s0);
             ca.b = s.b + (int64_t)s0 * g.M;
             ca.x = s.x + (int64_t)s0 * g.M;
             ca.iters = d_iters + s0;
@@ -3567,48 +3506,16 @@ static int coop_enqueue(efgp_toeplitz_s* op, const CgSolve& s, int* d_iters, hip
             // slabs give up at their first poll (the per-system iteration counts carry the -3 of the slab that died).  It sits
             // right behind the arrival counters: one fill for both
             if (!test_dead) {
-                EFGP_HIP_CHECK(hipMemsetAsync(scb + off_bar, 0, (size_t)per * 64 + 64, stream));
+                EFGP_HIP_CHECK(hipMemsetAsync(sc.scb + sc.off_bar, 0, (size_t)sh.per * 64 + 64, stream));
             } else {
-                EFGP_HIP_CHECK(hipMemsetAsync(scb + off_bar, 0, (size_t)per * 64, stream));
-                EFGP_HIP_CHECK(hipMemsetAsync(scb + off_status, 1, 64, stream));
+                EFGP_HIP_CHECK(hipMemsetAsync(sc.scb + sc.off_bar, 0, (size_t)sh.per * 64, stream));
+                EFGP_HIP_CHECK(hipMemsetAsync(sc.scb + sc.off_status, 1, 64, stream));
             }
-            hipError_t e;
-            if (herm) {
-                if (G == 1 && ks == 8) e = launch(cg_coop2d_herm_kernel<8, true>, nsys);
-                else if (G == 1) e = launch(cg_coop2d_herm_kernel<4, true>, nsys);
-                else if (ks == 8) e = launch(cg_coop2d_herm_kernel<8, false>, nsys);
-                else e = launch(cg_coop2d_herm_kernel<4, false>, nsys);
-            } else if (G == 1 && ks == 8) e = launch(cg_coop2d_kernel<8, true>, nsys);
-            else if (G == 1) e = launch(cg_coop2d_kernel<4, true>, nsys);
-            else if (ks == 8) e = launch(cg_coop2d_kernel<8, false>, nsys);
-            else e = launch(cg_coop2d_kernel<4, false>, nsys);
-            EFGP_HIP_CHECK(e);
+            if (const int rc = launch_coop(kern, op->device, sh, nsys, ca, stream)) return rc;
         }
     }
-    if (info) {
-        info->d_status = ca.status;
-        info->G = G;
-        info->rows_wg = rows_wg;
-        info->lines = lines;
-        info->cols_wg = cols_wg;
-        info->per = per;
-        info->stamps = ca.stamps;
-        info->herm = herm;
-        info->dbg = ca.dbg;
-    }
-    if (herm && ca.dbg == 2) {          // diagnostic run (EFGP_COOP_DBG=2): wait and print the phase shares of workgroup 0, system 0
-        double hs[12];
-        int it0 = 0;
-        EFGP_HIP_CHECK(stream_wait(stream));
-        EFGP_HIP_CHECK(hipMemcpy(hs, ca.stamps, sizeof(hs), hipMemcpyDeviceToHost));
-        EFGP_HIP_CHECK(hipMemcpy(&it0, d_iters, sizeof(int), hipMemcpyDeviceToHost));
-        const char* nm[10] = {"partial <r,r>, <r,z>", "R: rows of ws z -> b1", "barrier 1 + all-reduce", "beta, p update", "C: loads b1/b3, assemble",
-                              "C: transform, spectrum, transform", "C: unpack, stores to b2", "barrier 2 + all-reduce", "Ri: loads of b2", "Ri: transform, A p, x r z"};
-        double tot = 0;
-        for (int q = 0; q < 10; ++q) tot += hs[q];
-        std::fprintf(stderr, "[coop-herm] G = %d, rows/wg %d, lines/pass %d, column pairs/wg %d, systems/launch %d, %d iterations\n", G, rows_wg, lines, cols_wg, per, it0);
-        for (int q = 0; q < 10; ++q) std::fprintf(stderr, "[coop-herm] %-36s %9.0f ticks/iter %5.1f%%\n", nm[q], hs[q] / std::max(1, it0), 100.0 * hs[q] / tot);
-    }
+    if (info) *info = CoopInfo{ca.status, sh, ca.stamps, ca.dbg};
+    if (sh.herm && ca.dbg == 2) return coop_print_herm_stamps(sh, ca.stamps, d_iters, stream);
     return EFGP_OK;
 }
 
@@ -3642,19 +3549,6 @@ static int read_back_counts(DeviceCtx* ctx, const CgSolve& s, const int* d_iters
         its->assign(hit, hit + s.nbatch);
     }
     report_counts(hit, s, iters_out, row_iters_out);
-    return EFGP_OK;
-}
-
-// diagnostic run of the cooperative solve (EFGP_COOP_DBG=2): the phase shares of workgroup 0, system 0
-static int coop_print_stamps(const CoopInfo& ci, int iters0) {
-    double hs[14];
-    EFGP_HIP_CHECK(hipMemcpy(hs, ci.stamps, sizeof(hs), hipMemcpyDeviceToHost));
-    const char* nm[14] = {"R store to b1", "barrier 1", "C store", "barrier 2", "Ri load+fft", "pAp sum (incl. barrier)", "update", "rr/rz sum (incl. barrier)",
-                          "C load", "C transform 1 (+ multiply)", "-", "C transform 2", "R zero fill, ws u", "R transform"};
-    double tot = 0;
-    for (int q = 0; q < 14; ++q) tot += hs[q];
-    std::fprintf(stderr, "[coop] G = %d, rows/wg %d, lines/pass %d, columns/wg %d, systems/launch %d\n", ci.G, ci.rows_wg, ci.lines, ci.cols_wg, ci.per);
-    for (int q = 0; q < 14; ++q) std::fprintf(stderr, "[coop] %-28s %9.0f cycles/iter %5.1f%%\n", nm[q], hs[q] / std::max(1, iters0), 100.0 * hs[q] / tot);
     return EFGP_OK;
 }
 

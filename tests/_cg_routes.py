@@ -1,5 +1,5 @@
 """The host dispatch of the CG solves (csrc/toeplitz_cg.hip: efgp_toeplitz_create_ex, cg_solve_sync, setup_apply, coop_enqueue;
-csrc/cg_persistent.hip: persistent_cg_eligible, persistent_cg_launch) restated in Python, and the named cases of
+csrc/cg_persistent.hip: persistent_cg_launch; csrc/cg_plan_host.cpp: the planners both call) restated in Python, and the named cases of
 tests/test_gpu_cg_routes.py.
 
 `route(ns, hermitian, env)` says which kernel a solve of the block `ns` runs on, from the block shape, the Hermitian promise and
@@ -8,7 +8,7 @@ GPU that every case lands where it is listed, and the GPU tests assert that the 
 """
 import math
 
-K_THREADS, K_SLOTS, K_MAX_GRID = 512, 4, 4608          # cg_persistent.hip: kThreads, kSlots, kMaxGrid
+K_THREADS, K_SLOTS, K_MAX_GRID = 512, 4, 4608          # cg_plan_host.hpp: pcg::kThreads, kSlots, kMaxGrid
 LINE1D_MAX_N = 64 * 4 - 1                              # 64 * l1d::KS - 1
 COOP_LADDER = (96, 128, 192, 256, 384, 512)
 

@@ -386,6 +386,38 @@ def test_cooperative_solves_on_the_smallest_grid_equal_the_power_of_two_grid(n0,
     assert runs[True][0][1] < 2 * n0 * n1            # the preconditioned mean system converged before its iteration cap
 
 
+@pytest.mark.parametrize("n0,n1,nb,hermitian,grid", [(33, 33, 1, False, (96, 96)), (85, 129, 11, False, (192, 384)), (33, 33, 86, False, (96, 96)),
+                                                     (33, 33, 1, True, (96, 96)), (43, 129, 43, True, (96, 384)), (33, 33, 86, True, (96, 96)),
+                                                     (47, 47, 86, True, (96, 96))])
+def test_every_cooperative_kernel_equals_the_multi_launch_iteration(n0, n1, nb, hermitian, grid, monkeypatch):
+    """The seven instantiations of the cooperative kernels that a launch shape can ask for (general and Hermitian, 4 or 8 vector
+    entries per thread, G > 1 or G == 1), each at the smallest block x batch that reaches it on a 256-CU device
+    (tests/test_cg_plan_host.py asserts which kernel each case lands on); cg_coop2d_kernel<4, true> cannot be reached and does not
+    exist.  Three forced iterations, A_mean with the Jacobi diagonal and A_var without, against the multi-launch iteration
+    (EFGP_NO_CG_COOP): relative l2 distance per row below 1e-12, the bound
+    test_line_and_cooperative_iterations_on_non_cubic_blocks holds the general kernel to against the same partner.
+    Worst rows measured with the library before the host planners were split out and with this one (they are equal):
+    profiles/cg_plan_refactor_gpu_tests.txt."""
+    from efgp_hip import ToeplitzOp, cg_solve
+    v, ws, b = _psd_system(n0, n1, 3 + n0, nb)
+    sig = 25.0
+    diag = (2500.0 * ws.abs().pow(2).real + sig).cuda()
+    op = ToeplitzOp(v.cuda())
+    assert tuple(op.cg_shape(hermitian=hermitian)) == grid
+    runs = {}
+    for coop in (True, False):
+        if not coop:
+            monkeypatch.setenv("EFGP_NO_CG_COOP", "1")
+        runs[coop] = [cg_solve(op, ws.cuda(), sig, variant, b.cuda(), None, 1e-300, max_iter=3, early_stop=False, diag=dg, batched=True,
+                               hermitian=hermitian) for variant, dg in ((0, diag), (1, None))]
+    monkeypatch.delenv("EFGP_NO_CG_COOP")
+    for variant, (out, ref) in enumerate(zip(runs[True], runs[False])):
+        assert out[2] == ref[2] == [3] * nb, (variant, out[2], ref[2])
+        worst = max(_rel(out[0][r], ref[0][r]) for r in range(nb))
+        print(f"\ncoop {n0}x{n1} nb={nb} herm={hermitian} variant {variant}: worst row {worst:.3e}")
+        assert worst < 1e-12, (variant, worst)
+
+
 def _replay_system(d, mtot, hermitian):
     """Five right-hand sides on a (mtot,)*d block; Hermitian: conjugate-even rows and a real even ws (tests/test_gpu_cg_hermitian.py)."""
     x, v, T = _setup(d, mtot, N=300, seed=9)
