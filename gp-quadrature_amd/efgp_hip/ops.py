@@ -746,6 +746,35 @@ def variance_contract(x_new, h, mtot, ws, gamma):
     return out
 
 
+def cheb_interp(nodes_per_axis, weights_per_axis, node_values, x_new, clamp=True):
+    """Tensor-product barycentric interpolation (efgp_cheb_interp): `nodes_per_axis` / `weights_per_axis` are d sequences (arrays,
+    tensors) of the ascending nodes and their barycentric weights, `node_values` holds prod n_a doubles with the last axis fastest
+    and `x_new` is (npts, d) on the GPU -> (npts,) float64 there, clamped at 0 when `clamp`.  Sizes are checked by the entry
+    point (d 1..3, 2..64 nodes per axis, at most 4096 node values): a breach is a ValueError naming the argument."""
+    dev = x_new.device
+    xn = _dc(x_new, dev, _RD)
+    if xn.ndim != 2:
+        raise ValueError(f"cheb_interp: x_new must be (npts, d), got {tuple(xn.shape)}")
+    npts, d = xn.shape
+    if len(nodes_per_axis) != d or len(weights_per_axis) != d:
+        raise ValueError(f"cheb_interp: {len(nodes_per_axis)} node axes and {len(weights_per_axis)} weight axes for {d}-D points")
+    nd = [torch.as_tensor(a, dtype=_RD).reshape(-1) for a in nodes_per_axis]
+    wt = [torch.as_tensor(a, dtype=_RD).reshape(-1) for a in weights_per_axis]
+    counts = [int(a.numel()) for a in nd]
+    if [int(a.numel()) for a in wt] != counts:
+        raise ValueError("cheb_interp: every axis needs as many weights as nodes")
+    vals = _dc(torch.as_tensor(node_values).reshape(-1), dev, _RD)
+    if vals.numel() != math.prod(counts):
+        raise ValueError(f"cheb_interp: {vals.numel()} node values for a node box of {tuple(counts)}")
+    nodes = torch.cat(nd).to(dev)
+    weights = torch.cat(wt).to(dev)
+    out = torch.empty(npts, dtype=_RD, device=dev)
+    with _on(dev):
+        check(lib().efgp_cheb_interp(dev.index, d, _i64(counts), _ptr(nodes), _ptr(weights), _ptr(vals), _ptr(xn), npts, int(bool(clamp)),
+                                     _ptr(out), _stream(dev)), "efgp_cheb_interp")
+    return out
+
+
 def spectral_weights_nd(dev, kind, nu, lengthscales, variance, hs, shape, want_grad=False):
     """(ws (M,), dprime (M, d + 1) or None) of an ARD kernel on the per-axis grid, complex128 on `dev`, in one launch
     (efgp_spectral_weights_nd)."""

@@ -11,8 +11,12 @@ estimator are kernels of their own (efgp_pg_estep_update, efgp_pg_weight_rows, e
 negative-binomial E-step pass and the gradient of r are efgp_pg_nb_estep_update and efgp_pg_nb_total_count_grad.
 torch carries allocations, the O(M) diagonal products around the solves and the O(#hypers) optimiser state.
 
-Scope: SE kernel, float64, predictive_variance_method="exact", a GPU device.  Anything else is refused with an error that
-names the option.  The product path does not import scikit-learn.
+Scope: SE kernel, float64, the constructor option predictive_variance_method="exact", a GPU device.  Anything else is refused with
+an error that names the option.  The approximate variances are chosen per call on a fitted estimator: `predictive_variance(X,
+method=...)` and the `variance_method=` keyword of `predict_response_mean` / `predict_proba` / `predict_mean_count` take "exact",
+"stochastic" (alias "stochastic_diag_sums": Hutchinson probes on the mode grid, one cached batched solve, efgp_lag_sums, one
+FFT-ordered type 2 per call) and "chebyshev" (the exact variance at n^d Chebyshev-Lobatto nodes of the test box, interpolated by
+efgp_cheb_interp; csrc/cheb_interp.hip).  The product path does not import scikit-learn.
 """
 from __future__ import annotations
 
@@ -36,6 +40,8 @@ __all__ = ["PolyagammaGPClassifier", "PolyagammaGPNegativeBinomialRegressor", "a
 _SE_NAMES = ("squared_exponential", "se", "rbf")
 _EXACT_VARIANCE = "exact"
 _UNSUPPORTED_VARIANCE = ("stochastic", "stochastic_diag_sums", "chebyshev")
+_VARIANCE_METHODS = ("exact", "stochastic", "stochastic_diag_sums", "chebyshev")      # the per-call keyword of the predictions
+_CHEB_MAX_AXIS, _CHEB_MAX_BOX = 64, 4096                                              # efgp_cheb_interp
 
 
 def approximate_logistic_gaussian_prob(mean: torch.Tensor, variance: torch.Tensor | None = None) -> torch.Tensor:
@@ -321,6 +327,7 @@ class _BasePolyagammaGPEstimator:
         N, d = X_arr.shape
         self._N = N
         self.last_fit_stats = {"solves": []}
+        self._variance_sums_cache = self._last_variance_stats = None     # the stochastic variance's lag sums belong to one fit
 
         xd = torch.as_tensor(X_arr).to(dev).contiguous()
         targets = torch.as_tensor(values).to(dev).contiguous()
@@ -443,22 +450,145 @@ class _BasePolyagammaGPEstimator:
             return self.posterior_mean_.copy()
         return self._latent_mean(self._device_points(X_arr)).cpu().numpy()
 
-    def predictive_variance(self, X):
+    # -- approximate variances, chosen per call (pg_classifier.py:767-1009, 1128-1216) ---------------------------------------------
+    @staticmethod
+    def _variance_method(method):
+        """The per-call keyword -> "exact" | "stochastic" | "chebyshev" (None is "exact", "stochastic_diag_sums" is "stochastic")."""
+        if method is None:
+            return _EXACT_VARIANCE
+        name = str(method).lower()
+        if name not in _VARIANCE_METHODS:
+            raise ValueError(f"variance method {method!r}: must be one of {', '.join(repr(m) for m in _VARIANCE_METHODS)}")
+        return "stochastic" if name == "stochastic_diag_sums" else name
+
+    @property
+    def last_variance_stats(self):
+        """What the last off-training variance computed: `method`; for "stochastic" `n_probes`, `seed` (the host stream's seed, or
+        the drawn device seed with random_state=None), `cached` (the lag sums came from the cache: no solve), `cg_iters` and the
+        per-row counts `rows` of the probe solve that made the sums; for "chebyshev" `n_nodes_total`, the per-axis `nodes` and
+        the `node_values` they were interpolated from (host arrays, at most 4096 doubles)."""
+        return dict(getattr(self, "_last_variance_stats", None) or {})
+
+    def _stochastic_variance_sums(self):
+        """Lag sums c[r] = mean_j sum_{k - l = r} gamma_j[k] eta_j[l] of J Rademacher probes eta on the mode grid,
+        gamma_j = (ws^2 / D_s) A^-1 D_s eta_j: one batched solve on the fit's operator and efgp_lag_sums, (2 mtot - 1)^d complex
+        in FFT order.  With random_state set the probes are the reference's host stream (seed random_state + 2_000_000),
+        otherwise device-hash probes of a drawn seed.  Kept under the key (J, seed or None) until the next fit: a later
+        prediction does no solve, and with random_state=None the drawn probes stay fixed."""
+        from efgp_hip.ops import cg_solve, lag_sums, rademacher_fill
+        J = int(self.predictive_variance_probes)
+        if J <= 0:
+            raise ValueError(f"predictive_variance_probes={self.predictive_variance_probes!r}: must be positive for the stochastic "
+                             "predictive variance")
+        rs = self.random_state
+        key = (J, None if rs is None else int(rs) + 2_000_000)
+        cache = getattr(self, "_variance_sums_cache", None)
+        if cache is not None and cache["key"] == key:
+            return cache, True
+        spec, dev = self._spec, self._dev
+        if rs is not None:
+            seed = key[1]
+            eta = _sample_rademacher((J, spec.M), seed).to(dev)
+        else:
+            seed = self._draw_seed()
+            eta = rademacher_fill(dev, seed, J, spec.M)
+        # the probes are real, not conjugate-even: the general solver route
+        y, iters, rows = cg_solve(self._op_pred, spec.ds, 1.0, 1, spec.ds * eta, None, self.cg_tol, max_iter=2000, early_stop=True,
+                                  batched=True)
+        gamma = spec.ws2_over_ds * y.reshape(J, spec.M)
+        sums = lag_sums(gamma, eta, spec.mtot, spec.d)
+        cache = {"key": key, "sums": sums, "seed": int(seed), "n_probes": J, "cg_iters": int(iters), "rows": [int(v) for v in rows]}
+        self._variance_sums_cache = cache
+        return cache, False
+
+    def _stochastic_variance(self, xn):
+        """Re sum_r c[r] exp(2 pi i h r . x*) of the cached lag sums: one FFT-ordered type-2 transform, clamped at 0."""
+        from efgp_hip.ops import NufftPlan
+        cache, cached = self._stochastic_variance_sums()
+        spec = self._spec
+        var = NufftPlan(xn, spec.h, self.nufft_eps).type2(cache["sums"], spec.conv_shape, modeord=1, real_only=True)
+        self._last_variance_stats = dict(method="stochastic", n_probes=cache["n_probes"], seed=cache["seed"], cached=cached,
+                                         cg_iters=cache["cg_iters"], rows=list(cache["rows"]))
+        return var.reshape(-1).clamp_min(0.0)
+
+    @staticmethod
+    def _chebyshev_axis(lo, hi, n):
+        """Ascending Chebyshev-Lobatto nodes mid + half cos(pi k / (n - 1)) of [lo, hi] and their barycentric weights (-1)^k, halved
+        at both ends (the reference's common factor 2 / (hi - lo) cancels in the interpolation formula)."""
+        k = np.arange(n, dtype=np.float64)
+        nodes = 0.5 * (lo + hi) + 0.5 * (hi - lo) * np.cos(np.pi * k / (n - 1))
+        weights = (-1.0) ** k
+        weights[0] *= 0.5
+        weights[-1] *= 0.5
+        order = np.argsort(nodes)
+        return nodes[order], weights[order]
+
+    def _chebyshev_variance(self, xn):
+        """The exact variance at the n^d Chebyshev-Lobatto nodes of the test points' bounding box (`_latent_variance`, in
+        prediction_batch_size blocks), interpolated at every test point by efgp_cheb_interp and clamped at 0."""
+        from efgp_hip.ops import cheb_interp
+        n = int(self.predictive_variance_chebyshev_nodes)
+        d = xn.shape[1]
+        if n < 2:
+            raise ValueError(f"predictive_variance_chebyshev_nodes={self.predictive_variance_chebyshev_nodes!r}: must be at least 2")
+        if n > _CHEB_MAX_AXIS or n ** d > _CHEB_MAX_BOX:
+            raise ValueError(f"predictive_variance_chebyshev_nodes={n} in {d} dimensions is {n ** d} node solves: at most "
+                             f"{_CHEB_MAX_AXIS} nodes per axis and {_CHEB_MAX_BOX} nodes in all are supported")
+        lo_t, hi_t = torch.aminmax(xn, dim=0)
+        bounds = torch.stack([lo_t, hi_t]).cpu().numpy()
+        nodes, weights = [], []
+        for a in range(d):
+            lo, hi = float(bounds[0, a]), float(bounds[1, a])
+            if np.isclose(lo, hi):
+                pad = max(abs(lo), 1.0) * 1e-6
+                lo, hi = lo - pad, hi + pad
+            nd, wt = self._chebyshev_axis(lo, hi, n)
+            nodes.append(nd)
+            weights.append(wt)
+        mesh = np.meshgrid(*nodes, indexing="ij")
+        node_points = np.stack([g.reshape(-1) for g in mesh], axis=1)
+        node_values = self._latent_variance(self._device_points(node_points))
+        out = cheb_interp(nodes, weights, node_values, xn, clamp=True)
+        self._last_variance_stats = dict(method="chebyshev", n_nodes_total=int(node_points.shape[0]), nodes=[a.copy() for a in nodes],
+                                         node_values=node_values.cpu().numpy().reshape((n,) * d))
+        return out
+
+    def _predictive_variance_at(self, xn, method):
+        """Device variance at the rows of xn by the normalised method."""
+        if xn.shape[0] == 0:
+            return torch.empty(0, dtype=torch.float64, device=xn.device)
+        if method == "stochastic":
+            return self._stochastic_variance(xn)
+        if method == "chebyshev":
+            return self._chebyshev_variance(xn)
+        self._last_variance_stats = dict(method=_EXACT_VARIANCE)
+        return self._latent_variance(xn)
+
+    def predictive_variance(self, X, *, method=None):
+        """Latent predictive variance at the rows of X.  method None / "exact": one feature-space solve per point;
+        "stochastic" (alias "stochastic_diag_sums"): `predictive_variance_probes` Hutchinson probes, solved once per fit and
+        cached, then one type-2 transform per call; "chebyshev": the exact variance at `predictive_variance_chebyshev_nodes`^d
+        nodes of X's bounding box, interpolated.  Both options are read at call time.  The training inputs return
+        `posterior_var_diag_` whatever the method."""
+        method = self._variance_method(method)
         self._check_fitted()
         X_arr = _check_array(X, self.n_features_in_)
         if self._is_training_input(X_arr):
             return self.posterior_var_diag_.copy()
-        return self._latent_variance(self._device_points(X_arr)).cpu().numpy()
+        return self._predictive_variance_at(self._device_points(X_arr), method).cpu().numpy()
 
-    def predict_response_mean(self, X):
+    def predict_response_mean(self, X, *, variance_method=None):
+        method = self._variance_method(variance_method)
         self._check_fitted()
         X_arr = _check_array(X, self.n_features_in_)
+        if X_arr.shape[0] == 0:
+            return np.empty(0, dtype=np.float64)
         if self._is_training_input(X_arr):
             mean = torch.as_tensor(self.posterior_mean_, dtype=torch.float64)
             variance = torch.as_tensor(self.posterior_var_diag_, dtype=torch.float64)
         else:
             xn = self._device_points(X_arr)
-            mean, variance = self._latent_mean(xn), self._latent_variance(xn)
+            mean, variance = self._latent_mean(xn), self._predictive_variance_at(xn, method)
         return self._response_mean(mean, variance).cpu().numpy()
 
     # -- function draws ----------------------------------------------------------------------------------------------------
@@ -620,8 +750,8 @@ class PolyagammaGPClassifier(_BasePolyagammaGPEstimator):
     def _response_mean(self, mean, variance):
         return approximate_logistic_gaussian_prob(mean, variance)
 
-    def predict_proba(self, X):
-        p1 = np.clip(self.predict_response_mean(X), 1e-8, 1.0 - 1e-8)
+    def predict_proba(self, X, *, variance_method=None):
+        p1 = np.clip(self.predict_response_mean(X, variance_method=variance_method), 1e-8, 1.0 - 1e-8)
         return np.column_stack([1.0 - p1, p1])
 
     def sample_proba(self, X, n_samples, *, seed=None):
@@ -780,8 +910,8 @@ class PolyagammaGPNegativeBinomialRegressor(_BasePolyagammaGPEstimator):
     def _response_mean(self, mean, variance):
         return negative_binomial_gaussian_mean(mean, variance, total_count=self.total_count_)
 
-    def predict_mean_count(self, X):
-        return self.predict_response_mean(X)
+    def predict_mean_count(self, X, *, variance_method=None):
+        return self.predict_response_mean(X, variance_method=variance_method)
 
     def sample_mean_count(self, X, n_samples, *, seed=None):
         """r exp(f) of every draw of `sample_latent(X, n_samples, seed=seed)` with the fitted total count r -> (n_samples, n): joint

@@ -450,6 +450,19 @@ int efgp_variance_contract_nd(int device, int dim, const int64_t* n_modes, const
 int efgp_hermitian_normal_rows(int device, uint64_t seed, int64_t index_offset, int nrows, int64_t nmodes, double a, const void* ws,
                                const void* fz, double b, void* out, void* stream);
 
+/* Tensor-product barycentric interpolation from a node box to npts points (the Chebyshev predictive variance of the PG
+ * estimators, pg_classifier.py:894-942, 1000-1003).  Per point x and axis a, with nodes x_k and weights c_k of that axis:
+ *     |x_a - x_k| <= 1e-14 for some k: w_a is one-hot at the first such k (ascending node order);
+ *     otherwise                        w_a[k] = (c_k / (x_a - x_k)) / sum_l (c_l / (x_a - x_l));
+ *     out = sum over the node box of prod_a w_a[i_a] * node_values[i_0, .., i_{dim-1}],   max(0, .) when clamp_nonneg.
+ * n_nodes: dim HOST counts; nodes, bary_weights: sum_a n_nodes[a] DEVICE doubles each, ascending per axis, the axes concatenated;
+ * node_values: prod_a n_nodes[a] DEVICE doubles, last axis fastest; x_new: (npts, dim) row-major; out: npts doubles.
+ * dim 1..3, 2 <= n_nodes[a] <= 64, prod n_nodes <= 4096, npts >= 0 (0: nothing is launched); anything else, or a null pointer
+ * with npts > 0, is EFGP_EINVAL.  Every output is written by one thread in a fixed order of operations: two calls agree bit for
+ * bit. */
+int efgp_cheb_interp(int device, int dim, const int64_t* n_nodes, const double* nodes, const double* bary_weights,
+                     const double* node_values, const double* x_new, int64_t npts, int clamp_nonneg, double* out, void* stream);
+
 /* ---- Polya-Gamma estimators: the pointwise and M-scale passes around the weighted solves (pg_classifier.py) -----------------
  * efgp_pg_estep_update: one pass over the N points after the E-step's batched solve (:552-569, :252-257, :129-138):
  *     mean[n] = S[0, n];  sigma_diag[n] = (1/J) sum_j z[j, n] S[1 + j, n];
