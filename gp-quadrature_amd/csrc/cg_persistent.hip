@@ -1282,6 +1282,7 @@ constexpr int kLdsElems = G_ELEMS + T_ELEMS + Q_ELEMS;     // 53 KB
 // per-frequency Toeplitz products (round 6, dense48_coeffs below): lane = (f1, three rows k0 = a0 .. a0 + 2), a0 = 0, 3, 6, 9
 constexpr int ND = 4 * F;                // dense lanes (waves 0..2)
 constexpr int NC = 25;                   // lags a0 - 11 .. a0 + 13 of a dense lane
+constexpr int kReread = 8;               // row of the multiply-adds in front of which a dense lane re-reads G of its own three rows
 constexpr int LDV = 49;                  // pitch of the prologue's 48 x 48 grid (vhat48_lines)
 constexpr int kLdsElemsDense = F * LDV + (kThreadsH / 8) * LX;      // the prologue's grid + 32 line slots: 73 KB
 static_assert(2 * G_ELEMS + NR * LX <= kLdsElemsDense, "the iteration's G, Yh and row scratch alias the prologue's grid");
@@ -1327,6 +1328,26 @@ __device__ __forceinline__ void exchange_8to6(const double2 (&v)[8], double2 (&u
     for (int t = 1; t < 6; ++t) u[t] = cmulp(u[t], tw[t - 1]);
     dft6(u);
 }
+// exchange_8to6 for an iteration that forms <p, A p> ahead of D (cg_herm48_kernel, FREQ_DOT): the lane's share of <x, x>,
+// scale * sum |x[s]|^2, is issued behind the six reads, while they are under way.
+__device__ __forceinline__ double exchange_8to6_norm(const double2 (&v)[8], double2 (&u)[6], bool writer, double2* __restrict__ wr,
+                                                     const double2* __restrict__ rd, const double2 (&tw)[5], const double2 (&x)[4],
+                                                     double scale) {
+    wave_sync();
+    if (writer) s64::store8_all<1>(wr, v);
+    wave_sync();
+#pragma unroll
+    for (int t = 0; t < 6; ++t) u[t] = rd[9 * t];
+    __builtin_amdgcn_sched_barrier(0);
+    const double x01 = fma(x[0].x, x[0].x, x[0].y * x[0].y) + fma(x[1].x, x[1].x, x[1].y * x[1].y);
+    const double x23 = fma(x[2].x, x[2].x, x[2].y * x[2].y) + fma(x[3].x, x[3].x, x[3].y * x[3].y);
+    const double xx = scale * (x01 + x23);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 1; t < 6; ++t) u[t] = cmulp(u[t], tw[t - 1]);
+    dft6(u);
+    return xx;
+}
 // "8x6", second half: every lane j < 8 has run the radix-6 stage on u and twiddles its outputs with tw[k - 1] = w48^(j k); the
 // lanes k < 6 take value k of the eight writers and run the radix-8 stage of which the outputs 0, 1, 6, 7 are wanted:
 // v[k2] = X[k + 6 k2].
@@ -1340,6 +1361,37 @@ __device__ __forceinline__ void exchange_6to8(double2 (&u)[6], double2 (&v)[8], 
     wave_sync();
     s64::load8_all<9>(rd, v);
     h64::dft8_out4(v);
+}
+
+// sum over the lanes 0..31 of a wave, returned to every lane; also right where the lanes 32..63 sit out (they are not read)
+__device__ __forceinline__ double half_wave_sum(double v) {
+    EFGP_DPP_ADD(v, 0x111, 0xF);   // row_shr:1
+    EFGP_DPP_ADD(v, 0x112, 0xF);   // row_shr:2
+    EFGP_DPP_ADD(v, 0x114, 0xF);   // row_shr:4
+    EFGP_DPP_ADD(v, 0x118, 0xF);   // row_shr:8   -> lane 15 of every 16-lane row holds the row sum
+    EFGP_DPP_ADD(v, 0x142, 0xA);   // row_bcast:15 into row 1 -> lane 31 holds the sum of the lanes 0..31
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), 31);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 31);
+    return __hiloint2double(hi, lo);
+}
+
+// exchange_6to8 for an iteration that forms <p, A p> ahead of D (cg_herm48_kernel, FREQ_DOT): the sum of `part` over the lanes 0..31
+// and the quotient num / (sum + 1e-16) are issued behind the eight reads, while the LDS trip (the six writes, then the reads) is
+// under way.  A wave runs one instruction at a time, so the wait for LDS is where they cost least.
+__device__ __forceinline__ double exchange_6to8_quot(double2 (&u)[6], double2 (&v)[8], double2* __restrict__ wr,
+                                                     const double2* __restrict__ rd, const double2 (&tw)[5], double part, double num) {
+#pragma unroll
+    for (int t = 1; t < 6; ++t) u[t] = cmulp(u[t], tw[t - 1]);
+    wave_sync();
+#pragma unroll
+    for (int t = 0; t < 6; ++t) wr[t] = u[t];
+    wave_sync();
+    s64::load8_all<9>(rd, v);
+    __builtin_amdgcn_sched_barrier(0);
+    const double quot = num / (half_wave_sum(part) + 1e-16);
+    __builtin_amdgcn_sched_barrier(0);
+    h64::dft8_out4(v);
+    return quot;
 }
 
 // vhat[f0][f1] = factor * sum_l v[l] w48^(f0 l0 + f1 l1), natural order: the spectrum of the Toeplitz vector on this grid.  Lines in
@@ -1495,7 +1547,14 @@ __device__ __forceinline__ void dense48_coeffs(double2* lds2, const double2 (&tw
 // DENSE (round 6): the operator application keeps the row transforms A and D and replaces the packed column transforms B / C by
 // per-frequency Hermitian Toeplitz products over k0 with coefficients resident in registers (h48::dense48_coeffs); !DENSE is the
 // round 4 application (EFGP_CG48_FFT2D=1).
-template <int VARIANT, bool FUSED = false, bool DENSE = true>
+// FREQ_DOT (round 7, DENSE only): <p, A p> is formed in the row-frequency domain, one phase early, and the iteration runs on three
+// workgroup barriers instead of four.  ws is real and A transforms ws * p, so <p, A p> = sigma^2 <p, p> + <ws p, T (ws p)>, and by
+// Parseval along k1 (a 48-point transform of a row supported on the 23 modes; the 1 / 48 of the inverse sits in cf)
+//     <ws p, T ws p> = sum_f1 [ Re G[0][f1] Yh[0][f1] + 2 sum_{k0 = 1..11} Re(conj G[k0][f1] Yh[k0][f1]) ]
+// with exactly the G the dense lanes read and the Yh they produce (row 0: both after the projection, so the identity also holds
+// for an iterate with a conjugate-odd part).  The same recurrence with one inner product evaluated in another basis; no vector is
+// formed by recurrence.  !FREQ_DOT (EFGP_CG48_MODE_DOT=1) is the round 6 iteration: <p, A p> summed over the modes behind D.
+template <int VARIANT, bool FUSED = false, bool DENSE = true, bool FREQ_DOT = false>
 __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
     using namespace h48;
     using h64::block_sum_h;
@@ -1504,10 +1563,16 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
     using h64::div_rcp;
     constexpr int KS = 4;
     static_assert(h64::kWavesH == kWavesH, "the block reductions are shared with the 64 x 64 kernel");
+    static_assert(DENSE || !FREQ_DOT, "the row-frequency <p,Ap> reads what the per-frequency Toeplitz products hold");
     extern __shared__ double2 lds2[];
     __shared__ double red[4 * kWavesH];
     __shared__ double s_rcp;             // 1 / (<r,z> + 1e-16) for the next beta, computed by an idle wave during A
     __shared__ int s_stop;               // convergence decision of the last completed iteration, taken by an idle wave during A
+    // FREQ_DOT: the lanes' summands of <u, A u>.  [0, ND): the Toeplitz terms of the dense lanes, written between barriers 1 and 2;
+    // [ND, ND + 96): wgt * sigma^2 sum |u|^2 over the four slots of every row lane (0 where a lane holds no mode), written in A, in
+    // front of barrier 1.  Both are read behind barrier 2, by the row lanes in D; the next writes (the next A, the next dense
+    // phase) have barrier 3 behind that read.  A warm start's first application leaves nothing to clear: every slot is rewritten.
+    __shared__ double s_part[FREQ_DOT ? ND + 8 * NR : 1];
     double2* const Gb = lds2;                    // G[k0][f1], k0 = 0..11 (rows beyond h are zero), f1 = 0..47
     double2* const Tb = lds2 + G_ELEMS;          // conj T[row(p)][q]: rows p = 0..11 and 36..47 (stored at p - 24); DENSE: conj Yh[k0][f1], pitch LDR
     double2* const Qb = Tb + (DENSE ? G_ELEMS : T_ELEMS);       // exchange scratch: column lines (B/C), aliased by the row lines (A, D)
@@ -1616,17 +1681,24 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
 #endif
     int stop = 0;
     double rcp_rz = 0.0;
+    double rz = 0.0;
+    double alpha_fd = 0.0;               // FREQ_DOT: rz / (<u, A u> + 1e-16) of the last operator application, formed inside D
     auto apply_A = [&](const double2 (&u)[KS], double2 (&Au)[KS]) __attribute__((always_inline)) {
         double2 v[8], u6[6];
         EFGP_STAMP(7);
         // A ("6x8"): rows k0 >= 0, modes k1 wrapped to positions k1 mod 48 -> G[k0][f1]
         if (row_role) {
+            double uu = 0.0;
             dft8_in4(make_double2(wsr[0] * u[0].x, wsr[0] * u[0].y), make_double2(wsr[1] * u[1].x, wsr[1] * u[1].y),
                      make_double2(wsr[2] * u[2].x, wsr[2] * u[2].y), make_double2(wsr[3] * u[3].x, wsr[3] * u[3].y), v);
-            exchange_8to6(v, u6, j < 6, xw, xr, twr);     // u6[k2] = G[k0][j + 8 k2]
+            // u6[k2] = G[k0][j + 8 k2].  FREQ_DOT: and the lane's share of the sigma^2 <u,u> of <u, A u> (the slots without a mode
+            // hold zeros)
+            if constexpr (FREQ_DOT) uu = exchange_8to6_norm(v, u6, j < 6, xw, xr, twr, u, VARIANT == 0 ? wgt * a.sigmasq : wgt);
+            else exchange_8to6(v, u6, j < 6, xw, xr, twr);
             double2* g0 = Gb + k0 * LDR + j;
 #pragma unroll
             for (int t = 0; t < 6; ++t) g0[8 * t] = u6[t];
+            if constexpr (FREQ_DOT) s_part[ND + tid] = uu;
         }
         __syncthreads();
         stop = s_stop;
@@ -1646,8 +1718,19 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
                 double2 acc[3];
 #pragma unroll
                 for (int o = 0; o < 3; ++o) acc[o] = make_double2(cf[11 + o].x * gm[0].x, cf[11 + o].y * gm[0].x);
+                double2 gk[3];
 #pragma unroll
                 for (int m = 1; m < NR; ++m) {
+                    if constexpr (FREQ_DOT) {
+                        // G of the lane's own rows once more (kd differs between the lanes of a wave: gm[kd + o] is no register).
+                        // Issued late in the multiply-adds, into registers that rows of gm have left: next to the twelve reads the
+                        // three would push coefficients out to AGPRs, behind the loop their latency would stand exposed.
+                        if (m == kReread) {
+#pragma unroll
+                            for (int o = 0; o < 3; ++o) gk[o] = g0[(kd + o) * LDR];
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    }
 #pragma unroll
                     for (int o = 0; o < 3; ++o) {
                         const double2 cm = cf[11 + o - m], cp = cf[11 + o + m];
@@ -1665,6 +1748,15 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
                 t0[0] = make_double2(acc[0].x, kd == 0 ? 0.0 : -acc[0].y);       // conj Yh: D transforms conjugated inputs
                 t0[LDR] = make_double2(acc[1].x, -acc[1].y);
                 t0[2 * LDR] = make_double2(acc[2].x, -acc[2].y);
+                if constexpr (FREQ_DOT) {
+                    EFGP_STAMP(1);
+                    // Re(conj G Yh) of the three rows: row 0 once and from the real parts only, the others twice (rows beyond h
+                    // have G = 0)
+                    const double t0r = kd == 0 ? gk[0].x * acc[0].x : 2.0 * fma(gk[0].y, acc[0].y, gk[0].x * acc[0].x);
+                    const double t12 = fma(gk[1].y, acc[1].y, gk[1].x * acc[1].x) + fma(gk[2].y, acc[2].y, gk[2].x * acc[2].x);
+                    // no wave sum here, where it would stand on the chain of the phase: the row lanes add the lanes' terms up in D
+                    s_part[tid] = fma(2.0, t12, t0r);
+                }
             }
         } else if (col_role) {
             // B ("6x8"): packed columns z[k0] = G[k0][q] + i G[k0][q + 24] (k0 >= 0), conj G[-k0][q] + i conj G[-k0][q + 24] (k0 < 0),
@@ -1697,14 +1789,30 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
             }
         }
         __syncthreads();
-        EFGP_STAMP(1);
+        EFGP_STAMP(FREQ_DOT ? 6 : 1);
         // D ("8x6"): row k0 >= 0 of the result, from Yh[k0] (DENSE) or from the packed columns at +k0 and -k0; conjugated inputs,
         // forward transform
         if (row_role) {
+            double uAu = 0.0;
             if constexpr (DENSE) {
+                // FREQ_DOT: <u, A u> and the step length in the block of D.  The 288 summands: nine per lane here, then over the 32
+                // lanes (both row waves have their lanes 0..31 in this block) and the division inside the exchange.  All fifteen
+                // reads go out together, the summands first.
+                double pt[9];
+                if constexpr (FREQ_DOT) {
+                    const double* sp = s_part + (lane & 31);
+#pragma unroll
+                    for (int t = 0; t < 9; ++t) pt[t] = sp[32 * t];
+                }
                 const double2* tp = Tb + k0 * LDR + j;
 #pragma unroll
                 for (int t = 0; t < 6; ++t) u6[t] = tp[8 * t];
+                if constexpr (FREQ_DOT) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    double tsum = ((pt[0] + pt[1]) + (pt[2] + pt[3])) + (pt[4] + pt[5]);
+                    if (VARIANT == 1) tsum /= a.sigmasq;
+                    uAu = tsum + ((pt[6] + pt[7]) + pt[8]);
+                }
             } else {
                 const double2* tp = Tb + k0 * LT + j;
                 const double2* tm = Tb + (k0 == 0 ? 0 : 2 * NR - k0) * LT + j;
@@ -1716,7 +1824,10 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
                 }
             }
             dft6(u6);
-            exchange_6to8(u6, v, xw, xr, twr);            // lanes j < 6: v[k2] = conj Y[k0][j + 6 k2], k2 in {0, 1, 6, 7}
+            // lanes j < 6: v[k2] = conj Y[k0][j + 6 k2], k2 in {0, 1, 6, 7}.  FREQ_DOT: and rz / (<u, A u> + 1e-16); a warm start's
+            // first application has rz = 0 and drops the value
+            if constexpr (FREQ_DOT) alpha_fd = exchange_6to8_quot(u6, v, xw, xr, twr, uAu, rz);
+            else exchange_6to8(u6, v, xw, xr, twr);
             const double2 y[KS] = {s64::conjd(v[0]), s64::conjd(v[1]), s64::conjd(v[6]), s64::conjd(v[7])};
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
@@ -1728,6 +1839,7 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
                 Au[s] = ok[s] ? val : make_double2(0.0, 0.0);
             }
         } else {
+            if constexpr (FREQ_DOT) alpha_fd = 0.0;      // these lanes hold no modes: their vectors are zero and stay zero
 #pragma unroll
             for (int s = 0; s < KS; ++s) Au[s] = make_double2(0.0, 0.0);
         }
@@ -1745,7 +1857,7 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
     } else {
         apply_A(xv, Ap);
     }
-    double rz = 0.0, bb = 0.0, asym = 0.0;
+    double bb = 0.0, asym = 0.0;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
         if (ok[s]) {
@@ -1789,12 +1901,17 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
     for (; it < a.max_iter;) {
         apply_A(pv, Ap);
         if (stop) break;
-        double pAp = 0.0;
+        double alpha;
+        if constexpr (FREQ_DOT) {
+            alpha = alpha_fd;                             // from D straight into the updates
+        } else {
+            double pAp = 0.0;
 #pragma unroll
-        for (int s = 0; s < KS; ++s) pAp += pv[s].x * Ap[s].x + pv[s].y * Ap[s].y;
-        pAp = block_sum_h(pAp * wgt, red) + 1e-16;
-        EFGP_STAMP(3);
-        const double alpha = rz / pAp;
+            for (int s = 0; s < KS; ++s) pAp += pv[s].x * Ap[s].x + pv[s].y * Ap[s].y;
+            pAp = block_sum_h(pAp * wgt, red) + 1e-16;
+            EFGP_STAMP(3);
+            alpha = rz / pAp;
+        }
         double rr = 0.0, rzn = 0.0;
         double2 zv[KS];
 #pragma unroll
@@ -2596,15 +2713,20 @@ static PickLaunch launch_of(const PersistentChoice& c, int variant, const Geom& 
     // grid + 32 line slots of scratch outgrow the iteration's 53 KB too -- one workgroup, so the extra LDS costs nothing
     constexpr size_t lds48d = (size_t)h48::kLdsElemsDense * sizeof(double2);
     static_assert(h48::kLdsElemsDense >= h48::kLdsElems, "the fused prologue's LDS covers the iteration's");
+    // EFGP_CG48_MODE_DOT=1 (read per call): the dense 48 x 48 kernels sum <p,Ap> over the modes behind D (the round 6 iteration, four
+    // barriers) instead of forming it in the row-frequency domain (round 7, three)
+    const bool freq_dot = std::getenv("EFGP_CG48_MODE_DOT") == nullptr;
     switch (c.pick) {
-        case PersistentPick::fused48:
-            return {c.dense48 ? cg_herm48_kernel<0, true, true> : cg_herm48_kernel<0, true, false>, h48::kThreadsH, lds48d,
-                    "fused mean solve (48x48)"};
+        case PersistentPick::fused48: {
+            void (*const dense[2])(Args) = {cg_herm48_kernel<0, true, true, false>, cg_herm48_kernel<0, true, true, true>};
+            return {c.dense48 ? dense[freq_dot] : cg_herm48_kernel<0, true, false>, h48::kThreadsH, lds48d, "fused mean solve (48x48)"};
+        }
         case PersistentPick::herm48: {
-            void (*const dense[2])(Args) = {cg_herm48_kernel<0, false, true>, cg_herm48_kernel<1, false, true>};
+            void (*const dense[2][2])(Args) = {{cg_herm48_kernel<0, false, true, false>, cg_herm48_kernel<1, false, true, false>},
+                                               {cg_herm48_kernel<0, false, true, true>, cg_herm48_kernel<1, false, true, true>}};
             void (*const fft2d[2])(Args) = {cg_herm48_kernel<0, false, false>, cg_herm48_kernel<1, false, false>};
-            return {(c.dense48 ? dense : fft2d)[variant != 0], h48::kThreadsH, c.dense48 ? lds48d : (size_t)h48::kLdsElems * sizeof(double2),
-                    "persistent CG (48x48, Hermitian)"};
+            return {(c.dense48 ? dense[freq_dot] : fft2d)[variant != 0], h48::kThreadsH,
+                    c.dense48 ? lds48d : (size_t)h48::kLdsElems * sizeof(double2), "persistent CG (48x48, Hermitian)"};
         }
         case PersistentPick::herm64:
             return {variant == 0 ? cg_herm64_kernel<0> : cg_herm64_kernel<1>, h64::kThreadsH, (size_t)h64::kLdsElems * sizeof(double2),

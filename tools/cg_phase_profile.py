@@ -43,9 +43,17 @@ if len(sys.argv) > 1 and sys.argv[1] == "herm":
     beta, lazy = cg_solve_mean_async(oph, wsh, 0.1, vh[tuple((s - 1) // 2 for s in vh.shape)].real, bh, 1e-300, max_iter=iters, early_stop=False)
     assert int(lazy) == iters
     assert lib.efgp_debug_cg_stamps(out) == 0
-    names = {0: "A: ws*p, row transforms (h+1 lines)", 1: "B/C: packed column transforms, spectrum", 2: "D: unpack, row transforms, A u",
-             3: "<p,Ap>: wave sums, LDS, barrier", 4: "alpha, x r z updates, partial sums", 5: "<r,r>, <r,z>: wave sums, LDS, barrier",
-             7: "norm test, beta, p update"}
+    # cg_herm48_kernel, a single system: per-frequency Toeplitz products between the row transforms.  Default arm (round 7):
+    # <p,Ap> in the row-frequency domain, slot 6 in place of slot 3, alpha's division inside D.  EFGP_CG48_MODE_DOT=1: the round 6
+    # iteration (slot 3).  EFGP_CG48_FFT2D=1 / cg_herm64_kernel: slot 1 is the packed column transforms B / C.
+    mode_dot = os.environ.get("EFGP_CG48_MODE_DOT") is not None
+    print("arm: " + ("<p,Ap> over the modes behind D (EFGP_CG48_MODE_DOT=1)" if mode_dot else "<p,Ap> in the row-frequency domain"))
+    names = {0: "A: ws*p, row transforms (h+1 lines)" + ("" if mode_dot else ", <p,p> partials"),
+             1: "per-frequency Toeplitz products (or B/C)",
+             2: "D: row transforms, A u" + ("" if mode_dot else "; alpha = rz / pAp"),
+             3: "<p,Ap>: wave sums, LDS, barrier", 4: "alpha, x r z updates, partial sums" if mode_dot else "x r z updates, partial sums",
+             5: "<r,r>, <r,z>: wave sums, LDS, barrier",
+             6: "<p,Ap>: frequency terms, wave sum, LDS, barrier", 7: "norm test, beta, p update"}
 herm_names = names if len(sys.argv) > 1 and sys.argv[1] == "herm" else None
 names = herm_names or {0: "load ws*p -> LDS", 1: "fwd pass 0 (last dim)", 2: "fwd pass 1 (+fused mid)", 3: "fwd pass 2",
          4: "inv pass 0 (rest)", 5: "inv pass 1", 6: "inv pass 2", 7: "vector updates + reductions", 8: "crop + A u"}
