@@ -746,6 +746,92 @@ def variance_contract(x_new, h, mtot, ws, gamma):
     return out
 
 
+def _raster_args(what, axes, h, n_modes):
+    """The checked per-axis arguments of the raster entries: (list of 1-D axes, spacings, mode counts)."""
+    if torch.is_tensor(axes) or not hasattr(axes, "__len__"):
+        axes = [axes]
+    axes = [a if torch.is_tensor(a) else torch.as_tensor(a) for a in axes]
+    d = len(axes)
+    if not 1 <= d <= 3:
+        raise ValueError(f"{what}: axes must hold 1, 2 or 3 coordinate vectors (got {d})")
+    shape = tuple(int(m) for m in (_per_axis(n_modes) or (n_modes,)))
+    if len(shape) != d:
+        raise ValueError(f"{what}: n_modes has {len(shape)} mode counts for {d} axes")
+    hv = _per_axis(h)
+    hv = tuple(float(v) for v in hv) if hv is not None else (float(h),) * d
+    if len(hv) != d:
+        raise ValueError(f"{what}: h has {len(hv)} spacings for {d} axes")
+    for a, ax in enumerate(axes):
+        if ax.ndim != 1:
+            raise ValueError(f"{what}: axes[{a}] must be 1-D (got shape {tuple(ax.shape)})")
+        if ax.numel() == 0:
+            raise ValueError(f"{what}: axes[{a}] is empty")
+    if any(m < 1 for m in shape):
+        raise ValueError(f"{what}: n_modes must be positive (got {shape})")
+    return axes, hv, shape
+
+
+def raster_plan(n_axis, n_modes, nbatch=1, max_workspace_bytes=0):
+    """Slabs and workspace of a raster_type2 call on a raster of n_axis cells per axis (efgp_raster_plan, host only):
+    dict(slab_rows, slabs, workspace_bytes).  ValueError when the cap cannot hold the phase tables and one 16-row slab."""
+    n_axis = tuple(int(n) for n in (_per_axis(n_axis) or (n_axis,)))
+    shape = tuple(int(m) for m in (_per_axis(n_modes) or (n_modes,)))
+    if len(n_axis) != len(shape) or not 1 <= len(shape) <= 3:
+        raise ValueError(f"raster_plan: n_axis has {len(n_axis)} entries and n_modes {len(shape)}; both must have 1, 2 or 3")
+    rows, slabs, nbytes = C.c_int64(), C.c_int64(), C.c_int64()
+    check(lib().efgp_raster_plan(len(shape), _i64(shape), _i64(n_axis), int(nbatch), int(max_workspace_bytes), C.byref(rows), C.byref(slabs),
+                                 C.byref(nbytes)), "efgp_raster_plan")
+    return dict(slab_rows=rows.value, slabs=slabs.value, workspace_bytes=nbytes.value)
+
+
+def raster_type2(axes, h, n_modes, f, *, modeord=0, isign=+1, mode_scale=None, xcen=None, batched=None, max_workspace_bytes=0, out=None):
+    """Exact type-2 transform onto the rectilinear raster axes[0] x .. x axes[d-1] ("ij" order), real part only (efgp_raster_type2):
+
+        out[b, j0..] = Re sum_k (f[b,k] * mode_scale[k]) exp(isign 2 pi i sum_a h[a] k_a (axes[a][j_a] - xcen[a]))
+
+    axes: d one-dimensional tensors (any spacing, any order); h: one spacing or d; f (prod,) | (*n_modes) | (B, ...) complex;
+    returns float64 (*n_axis) or (B, *n_axis) on the GPU.  No window and no tolerance: the sum separates per axis.  Bitwise
+    repeatable, independent of max_workspace_bytes (0: the library's default cap of the pooled workspace).  `out`: a contiguous
+    float64 tensor of the result's size to write into."""
+    axes, hv, shape = _raster_args("raster_type2", axes, h, n_modes)
+    d, M = len(shape), math.prod(shape)
+    if not torch.is_tensor(f):
+        f = torch.as_tensor(f)
+    if f.numel() == 0 or f.numel() % M:
+        raise ValueError(f"raster_type2: f has {f.numel()} entries, the mode box {shape} has {M}")
+    if batched is None:
+        batched = not (f.ndim == 1 or tuple(f.shape) == shape)
+    if not batched and f.numel() != M:
+        raise ValueError(f"raster_type2: f has {f.numel()} entries, the mode box {shape} has {M}")
+    if xcen is not None:
+        xc = _per_axis(xcen)
+        xc = tuple(float(v) for v in xc) if xc is not None else (float(xcen),) * d
+        if len(xc) != d:
+            raise ValueError(f"raster_type2: xcen has {len(xc)} entries for {d} axes")
+    if isign not in (-1, 1):
+        raise ValueError(f"raster_type2: isign must be +1 or -1 (got {isign})")
+    dev = compute_device(f, *axes)
+    sc = None
+    if mode_scale is not None:
+        if mode_scale.numel() != M:
+            raise ValueError(f"raster_type2: mode_scale has {mode_scale.numel()} entries, the mode box {shape} has {M}")
+        sc = _dc(mode_scale.reshape(-1), dev, _CD)
+    ff = _dc(f.reshape(-1, M), dev, _CD)
+    B = ff.shape[0]
+    n_axis = tuple(int(a.numel()) for a in axes)
+    ax = _dc(axes[0], dev, _RD) if d == 1 else torch.cat([a.to(device=dev, dtype=_RD) for a in axes])
+    if out is None:
+        out = torch.empty((B,) + n_axis, dtype=_RD, device=dev)
+    elif not (out.is_cuda and out.dtype is _RD and out.is_contiguous() and out.numel() == B * math.prod(n_axis)):
+        raise ValueError("raster_type2: out must be a contiguous float64 GPU tensor of the result's size")
+    with _on(dev):
+        check(lib().efgp_raster_type2(dev.index, d, _i64(shape), _f64(hv), _f64(xc) if xcen is not None else None, _i64(n_axis), _ptr(ax),
+                                      _ptr(ff), _ptr(sc) if sc is not None else None, B, int(isign), int(modeord), _ptr(out),
+                                      int(max_workspace_bytes), _stream(dev)), "efgp_raster_type2")
+    res = out.reshape((B,) + n_axis)
+    return res if batched else res[0]
+
+
 def cheb_interp(nodes_per_axis, weights_per_axis, node_values, x_new, clamp=True):
     """Tensor-product barycentric interpolation (efgp_cheb_interp): `nodes_per_axis` / `weights_per_axis` are d sequences (arrays,
     tensors) of the ascending nodes and their barycentric weights, `node_values` holds prod n_a doubles with the last axis fastest

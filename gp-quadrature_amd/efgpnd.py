@@ -32,7 +32,7 @@ from cg import ConjugateGradients
 from kernels.kernel_params import GPParams
 from utils.kernels import get_xis, get_xis_nd
 
-from efgp_hip import NufftPlan, PointSet, ToeplitzOp, lanczos, lag_sums, variance_rhs, variance_contract, cg_solve, cg_solve_lazy, cg_solve_mean_async, cg_solve_mean_fused, vdot_real, compute_device, rademacher_fill, gradient_prepare, gradient_assemble, hermitian_normal_rows, normal_row_offset, spectral_weights_nd
+from efgp_hip import NufftPlan, PointSet, ToeplitzOp, lanczos, lag_sums, variance_rhs, variance_contract, cg_solve, cg_solve_lazy, cg_solve_mean_async, cg_solve_mean_fused, vdot_real, compute_device, rademacher_fill, gradient_prepare, gradient_assemble, hermitian_normal_rows, normal_row_offset, spectral_weights_nd, raster_type2
 from efgp_hip.dist import PointShards
 from efgp_hip.ops import _per_axis
 
@@ -1517,6 +1517,68 @@ class EFGPND(nn.Module):
             st["cg_capped"] = [i for i, v in enumerate(st["cg_iters"]) if v >= st["cg_max_iterations"]]
         return st
 
+    def _draw_weight_blocks(self, nsamples, prior, seed, cg_tolerance, keep, transform):
+        """The weight draws of `sample_paths` and `sample_paths_grid`, in blocks of `_SAMPLE_BLOCK` rows: w (nb, M) of every block
+        goes through `transform` (the type-2 of the caller's points) -> (list of its outputs, max_iter, tol); the last two are None
+        for the prior.  `keep`: None or the lists of `return_state`.  Sets `_last_sample_stats`."""
+        st = self._fit_state
+        dev = self._devdata["dev"]
+        d, M = st["d"], st["ws"].numel()
+        shape = st["shape"]
+        max_iter = tol = None
+        seed_e1, seed_e2 = _derive_seed(seed, 1), _derive_seed(seed, 2)
+        block = _SAMPLE_BLOCK[d]
+        sig = st["sig"]
+        sols = []
+        if not prior:
+            tol = float(cg_tolerance) if cg_tolerance is not None else self.opts.get("cg_tolerance", 1e-4)
+            points = self._layout()
+            # kept while the grid spacing, the tolerance and the layout object stay what the plan was made with (a refit
+            # replaces _fit_state; what the plan depends on is h)
+            tol1 = min(float(self.nufft_eps), _CONV_TOL)
+            sp = self._sample_plan
+            if sp is None or sp[0] != (st["plan_h"], tol1) or sp[2] is not points:
+                self._sample_plan = sp = ((st["plan_h"], tol1), NufftPlan(self._devdata["x"], st["plan_h"], tol1, points=points), points)
+            plan_x = sp[1]
+            max_iter = int(self.opts.get("max_cg_iterations", 1000))
+            diag = None
+            if self.opts.get("mean_cg_preconditioner", True):
+                cidx = _center_flat(st["v"])
+                diag, _ = gradient_prepare(st["ws"], None, st["v"].reshape(-1)[cidx:cidx + 1], sig, want_diag=True, want_rhs=False)
+            sroot = math.sqrt(sig)
+        outs = []
+        for r0 in range(0, nsamples, block):
+            nb = min(block, nsamples - r0)
+            if prior:
+                w = hermitian_normal_rows(dev, seed_e2, nb, M, a=0.0, b=1.0, index_offset=normal_row_offset(2 * r0))
+            else:
+                fz = plan_x.type1_normal(seed_e1, nb, shape, index_offset=normal_row_offset(r0)).reshape(nb, M)
+                rhs = hermitian_normal_rows(dev, seed_e2, nb, M, a=sroot, ws=st["ws"], fz=fz, b=sig,
+                                            index_offset=normal_row_offset(2 * r0))
+                delta, its = cg_solve_lazy(self._toeplitz._op, st["ws"], sig, 0, rhs, None, tol,
+                                           max_iter=max_iter, early_stop=True, diag=diag,
+                                           batched=True, hermitian=True)
+                its.settle()                         # reads the counts only where the solve may hold dead rows
+                sols.append(its)
+                # The solution of a conjugate-even system is conjugate-even.  The Hermitian kernels iterate on the full vector
+                # and control only its even part: over the ~1000 iterations these broad-spectrum right-hand sides take at
+                # N = 1e6 the odd part grows from rounding to 1e-5..1e-3 of the solution (the fit's 10-300 iterations never
+                # show it).  It drops out of Re F(ws w) anyway; projecting it out makes delta and the weights what they mean.
+                delta = delta.reshape(nb, M)
+                delta = 0.5 * (delta + delta.flip(1).conj())
+                w = delta + st["beta"].reshape(1, M)
+                if keep is not None:
+                    keep["delta"].append(delta)
+                    keep["rhs"].append(rhs)
+            if keep is not None:
+                keep["weights"].append(w)
+            outs.append(transform(w))
+        self._last_sample_stats = dict(seed=seed, nsamples=nsamples, prior=bool(prior), blocks=-(-nsamples // block))
+        if not prior:
+            self._last_sample_stats["cg_iters"] = sols
+            self._last_sample_stats["cg_max_iterations"] = max_iter
+        return outs, max_iter, tol
+
     def sample_paths(self, x_new: torch.Tensor, nsamples: int, *, prior: bool = False, seed: Optional[int] = None,
                      cg_tolerance: Optional[float] = None, return_state: bool = False):
         """Draws of the latent function at x_new -> (nsamples, B), from the posterior (default) or the prior, in the weight space
@@ -1561,7 +1623,6 @@ class EFGPND(nn.Module):
         rdtype = self.x.dtype
         dev = self._devdata["dev"]
         xn = _dev_points(x_new, dev)
-        d, M = st["d"], st["ws"].numel()
         shape = st["shape"]
         pkey = (xn.data_ptr(), tuple(xn.shape), xn._version, st["plan_h"], float(self.nufft_eps))
         if self._predict_plan is not None and self._predict_plan[0] == pkey:
@@ -1569,59 +1630,11 @@ class EFGPND(nn.Module):
         else:
             plan_new = NufftPlan(xn, st["plan_h"], float(self.nufft_eps))
             self._predict_plan = (pkey, plan_new)
-        seed_e1, seed_e2 = _derive_seed(seed, 1), _derive_seed(seed, 2)
-        block = _SAMPLE_BLOCK[d]
-        sig = st["sig"]
-        sols = []
-        if not prior:
-            tol = float(cg_tolerance) if cg_tolerance is not None else self.opts.get("cg_tolerance", 1e-4)
-            points = self._layout()
-            # kept while the grid spacing, the tolerance and the layout object stay what the plan was made with (a refit
-            # replaces _fit_state; what the plan depends on is h)
-            tol1 = min(float(self.nufft_eps), _CONV_TOL)
-            sp = self._sample_plan
-            if sp is None or sp[0] != (st["plan_h"], tol1) or sp[2] is not points:
-                self._sample_plan = sp = ((st["plan_h"], tol1), NufftPlan(self._devdata["x"], st["plan_h"], tol1, points=points), points)
-            plan_x = sp[1]
-            max_iter = int(self.opts.get("max_cg_iterations", 1000))
-            diag = None
-            if self.opts.get("mean_cg_preconditioner", True):
-                cidx = _center_flat(st["v"])
-                diag, _ = gradient_prepare(st["ws"], None, st["v"].reshape(-1)[cidx:cidx + 1], sig, want_diag=True, want_rhs=False)
-            sroot = math.sqrt(sig)
-        outs = []
         keep = dict(weights=[], delta=[], rhs=[]) if return_state else None
-        for r0 in range(0, nsamples, block):
-            nb = min(block, nsamples - r0)
-            if prior:
-                w = hermitian_normal_rows(dev, seed_e2, nb, M, a=0.0, b=1.0, index_offset=normal_row_offset(2 * r0))
-            else:
-                fz = plan_x.type1_normal(seed_e1, nb, shape, index_offset=normal_row_offset(r0)).reshape(nb, M)
-                rhs = hermitian_normal_rows(dev, seed_e2, nb, M, a=sroot, ws=st["ws"], fz=fz, b=sig,
-                                            index_offset=normal_row_offset(2 * r0))
-                delta, its = cg_solve_lazy(self._toeplitz._op, st["ws"], sig, 0, rhs, None, tol,
-                                           max_iter=max_iter, early_stop=True, diag=diag,
-                                           batched=True, hermitian=True)
-                its.settle()                         # reads the counts only where the solve may hold dead rows
-                sols.append(its)
-                # The solution of a conjugate-even system is conjugate-even.  The Hermitian kernels iterate on the full vector
-                # and control only its even part: over the ~1000 iterations these broad-spectrum right-hand sides take at
-                # N = 1e6 the odd part grows from rounding to 1e-5..1e-3 of the solution (the fit's 10-300 iterations never
-                # show it).  It drops out of Re F(ws w) anyway; projecting it out makes delta and the weights what they mean.
-                delta = delta.reshape(nb, M)
-                delta = 0.5 * (delta + delta.flip(1).conj())
-                w = delta + st["beta"].reshape(1, M)
-                if keep is not None:
-                    keep["delta"].append(delta)
-                    keep["rhs"].append(rhs)
-            if keep is not None:
-                keep["weights"].append(w)
-            outs.append(plan_new.type2(w, shape, real_only=True, batched=True, mode_scale=st["ws"]))
+        outs, max_iter, tol = self._draw_weight_blocks(
+            nsamples, prior, seed, cg_tolerance, keep,
+            lambda w: plan_new.type2(w, shape, real_only=True, batched=True, mode_scale=st["ws"]))
         out = outs[0] if len(outs) == 1 else torch.cat(outs)       # one block: the transform's own output, no copy
-        self._last_sample_stats = dict(seed=seed, nsamples=nsamples, prior=bool(prior), blocks=-(-nsamples // block))
-        if not prior:
-            self._last_sample_stats["cg_iters"] = sols
-            self._last_sample_stats["cg_max_iterations"] = max_iter
         res = out.to(device=self.device, dtype=rdtype)
         if not return_state:
             return res
@@ -1636,6 +1649,104 @@ class EFGPND(nn.Module):
                 warnings.warn(f"sample_paths: {len(stats['cg_capped'])} of {nsamples} solves reached max_cg_iterations = {max_iter} "
                               f"without meeting the tolerance {tol:g}; raise opts['max_cg_iterations']", RuntimeWarning, stacklevel=2)
         return res, state
+
+    # -- maps on rectilinear grids ---------------------------------------------------------------------
+    def _grid_axes(self, axes, what):
+        """The d coordinate vectors of a rectilinear raster as float64 tensors (where the caller has them); ValueError for a wrong
+        count, an axis that is not 1-D or is empty, and non-finite coordinates."""
+        if self.opts.get("shard_points", False):
+            raise NotImplementedError(f"{what} does not support opts['shard_points']: the raster is evaluated on one device")
+        if axes is None:
+            raise ValueError(f"axes must be provided for {what}")
+        d_model = 1 if self.x.ndim == 1 else self.x.shape[1]
+        if torch.is_tensor(axes) or isinstance(axes, np.ndarray):
+            axes = [axes] if (d_model == 1 and axes.ndim == 1) else list(axes)
+        axes = [torch.as_tensor(a).to(torch.float64) for a in axes]
+        if len(axes) != d_model:
+            raise ValueError(f"{what}: {len(axes)} axes given, the model was built on {d_model} dimensions")
+        for a, ax in enumerate(axes):
+            if ax.ndim != 1:
+                raise ValueError(f"{what}: axes[{a}] must be 1-D (got shape {tuple(ax.shape)})")
+            if ax.numel() == 0:
+                raise ValueError(f"{what}: axes[{a}] is empty")
+        fin = [torch.isfinite(ax).all() for ax in axes]
+        for a, ok in enumerate(torch.stack([f.to(fin[0].device) for f in fin]).tolist()):       # one read-back for all axes
+            if not ok:
+                raise ValueError(f"{what}: axes[{a}] has non-finite coordinates")
+        return axes
+
+    def predict_grid(self, axes, *, return_variance: bool = True, variance_method: str = "stochastic", hutchinson_probes: int = 1_000,
+                     variance_probes: Optional[torch.Tensor] = None, force_recompute: bool = False):
+        """Posterior mean and latent variance on the rectilinear raster axes[0] x .. x axes[d-1] -> (mean, var), both of shape
+        (n_0, .., n_{d-1}) in "ij" order: what `predict` gives at `meshgrid(*axes, indexing="ij")`, without the (prod n, d)
+        coordinate tensor, the plan over it and the spreading window.  On a tensor product of coordinates the transform
+        separates per axis (`efgp_hip.raster_type2`: phase tables, a contraction per leading axis, a real GEMM on the f64 matrix
+        cores), so the map is exact to rounding -- `nufft_eps` plays no part in it.
+
+        axes: d one-dimensional tensors or arrays (any spacing, any order); a single tensor for a 1-D model.  "stochastic" variance:
+        the Hutchinson lag sums of `predict` (same probe handling: `variance_probes` (J, M) of +-1 may be injected), evaluated on
+        the raster in FFT order; "regular": the per-point solves of `predict`, fed 8192 raster cells at a time in row-major order.
+        return_variance=False returns NaN of the raster's shape as a stride-0 view."""
+        axes = self._grid_axes(axes, "predict_grid")
+        self._compute_common_parameters(force_recompute=force_recompute)
+        st = self._fit_state
+        rdtype = self.x.dtype
+        dev = self._devdata["dev"]
+        ax = [a.to(dev) for a in axes]
+        n_axis = tuple(int(a.numel()) for a in ax)
+        mean = raster_type2(ax, st["plan_h"], st["shape"], st["beta"], mode_scale=st["ws"])        # F (ws * beta) on the raster
+        out_mean = mean.to(device=self.device, dtype=rdtype)
+        if not return_variance:
+            if self._nan_scalar is None or self._nan_scalar.device != self.device or self._nan_scalar.dtype != rdtype:
+                self._nan_scalar = torch.full((1,), float("nan"), device=self.device, dtype=rdtype)
+            return out_mean, self._nan_scalar.expand(n_axis)
+        A_var = create_A_var(st["ws"], self._toeplitz, st["sig"], torch.complex128)
+        cg_tol, max_it = self.opts.get("cg_tolerance", 1e-4), self.opts.get("max_cg_iterations", 1000)
+        shape = st["shape"] if st["ard"] else None
+        method = variance_method.lower()
+        if method == "stochastic":
+            est = diag_sums_nd(A_var, hutchinson_probes, self._xis.to(torch.float64), max_it, cg_tol, st["ws"], probes=variance_probes,
+                               shape=shape)
+            var = raster_type2(ax, st["plan_h"], tuple(est.shape), est.detach(), modeord=1)
+        elif method == "regular":
+            cells, parts = prod(n_axis), []
+            for lo in range(0, cells, 8192):                     # the coordinates of 8192 cells at a time: no (prod n, d) tensor
+                idx = torch.arange(lo, min(cells, lo + 8192), device=dev)
+                cols = []
+                for a in reversed(range(len(ax))):
+                    cols.append(ax[a][idx % n_axis[a]])
+                    idx = idx // n_axis[a]
+                xb = torch.stack(cols[::-1], dim=1)
+                parts.append(compute_prediction_variance(
+                    x_new=xb, xis=None, ws=st["ws"], A_var=A_var, cg_tol=cg_tol, max_cg_iter=max_it, variance_method="regular",
+                    h=st["plan_h"], xcen=None, hutchinson_probes=hutchinson_probes, nufft_eps=self.nufft_eps, device=dev,
+                    rdtype=torch.float64, cdtype=torch.complex128, shape=shape))
+            var = torch.cat(parts).reshape(n_axis)
+        else:
+            raise ValueError(f"Variance method '{variance_method}' not implemented. Choose 'regular' or 'stochastic'.")
+        return out_mean, var.to(device=self.device, dtype=rdtype)
+
+    def sample_paths_grid(self, axes, nsamples: int, *, prior: bool = False, seed: Optional[int] = None,
+                          cg_tolerance: Optional[float] = None):
+        """Draws of the latent function on the rectilinear raster axes[0] x .. x axes[d-1] -> (nsamples, n_0, .., n_{d-1}): the
+        weight draws of `sample_paths` (same seed, same weights), evaluated by the exact raster transform of `predict_grid`
+        instead of a type-2 NUFFT over materialised points.  Arguments as in `sample_paths`; `last_sample_stats` is set alike."""
+        nsamples = int(nsamples)
+        if nsamples < 1:
+            raise ValueError(f"nsamples must be at least 1 (got {nsamples})")
+        axes = self._grid_axes(axes, "sample_paths_grid")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        seed = int(seed)
+        self._compute_common_parameters()
+        st = self._fit_state
+        dev = self._devdata["dev"]
+        ax = [a.to(dev) for a in axes]
+        outs, _, _ = self._draw_weight_blocks(
+            nsamples, prior, seed, cg_tolerance, None,
+            lambda w: raster_type2(ax, st["plan_h"], st["shape"], w, batched=True, mode_scale=st["ws"]))
+        out = outs[0] if len(outs) == 1 else torch.cat(outs)
+        return out.to(device=self.device, dtype=self.x.dtype)
 
     def sample_posterior(self, x_new: torch.Tensor, nsamples: int, method: str = "dense", seed: Optional[int] = None):
         """Posterior samples at x_new as a numpy array (B, nsamples).  method="dense": the O(N^3) sampler of the reference

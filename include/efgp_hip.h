@@ -436,6 +436,23 @@ int efgp_variance_rhs_nd(int device, int dim, const int64_t* n_modes, const doub
                          void* rhs, void* stream);
 int efgp_variance_contract_nd(int device, int dim, const int64_t* n_modes, const double* h, const double* x_new, int64_t npts,
                               const void* ws, const void* gamma, double* out, void* stream);
+/* Type-2 transform onto a rectilinear raster: the output points are the tensor product of `dim` coordinate vectors (n_axis[a]
+ * doubles each, concatenated on the device in `axes`; any spacing, any order), real float64 output only:
+ *     out[b, j0..j_{dim-1}] = Re sum_k (f[b,k] * mode_scale[k]) * exp(isign * 2 pi i * sum_a h[a] * k_a * (axis_a[j_a] - xcen[a]))
+ * f (nbatch, prod n_modes) complex128, modes stored as efgp_nufft_type2 stores them (modeord 0: -(n/2) .. (n-1)/2, 1: FFT order;
+ * counts even, odd or 1), mode_scale (prod n_modes) complex128 or NULL.  The sum separates per axis (phase tables, a contraction
+ * per leading axis, a real GEMM on the f64 matrix cores for the last one): no window, no tolerance, exact to rounding; a call is
+ * bitwise repeatable and independent of the slab count.  Tables and intermediates live in a pooled workspace of at most
+ * max_workspace_bytes (0: 256 MiB), the leading raster axis being processed in slabs of whole 16-row tiles; a cap that cannot hold
+ * the tables and one such slab is EFGP_EINVAL (the message names the bytes needed) before anything is launched.
+ * efgp_raster_plan is the host-side planning alone: slab height, slab count and workspace bytes of such a call. */
+int efgp_raster_type2(int device, int dim, const int64_t* n_modes, const double* h /* d, host */,
+                      const double* xcen_host /* d or NULL */, const int64_t* n_axis /* d */,
+                      const double* axes /* device: the d coordinate vectors, concatenated */,
+                      const void* f, const void* mode_scale /* or NULL */, int nbatch, int isign, int modeord,
+                      double* out /* (nbatch, n_axis...) */, int64_t max_workspace_bytes /* 0: default */, void* stream);
+int efgp_raster_plan(int dim, const int64_t* n_modes, const int64_t* n_axis, int nbatch, int64_t max_workspace_bytes,
+                     int64_t* slab_rows_out, int64_t* slabs_out, int64_t* workspace_bytes_out);   /* host only */
 /* Rows on the symmetric mode box of nmodes = mtot^d entries (odd; flat index j, the negated frequency at nmodes - 1 - j) for the
  * path sampler, one launch for all rows:
  *     out[s, j] = a * ws[j] * fz[s, j] + b * e[s, j],
