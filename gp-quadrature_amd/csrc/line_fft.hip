@@ -21,8 +21,6 @@
 namespace efgp {
 
 constexpr int kFftThreads = 256;
-constexpr int kFftMaxLine = 4096;            // two LDS buffers of one line: 128 KB
-constexpr int kFftMaxFactors = 12;
 
 struct OwnFftPass {
     const double2* src;      // lines of n_src stored entries (may alias dst when n_src == n_dst == n)
@@ -212,31 +210,6 @@ __global__ __launch_bounds__(kFftThreads) void own_fft_pass_kernel(OwnFftPass a)
     }
 }
 
-static bool factorize(int64_t n, int* fac, int* nfac) {
-    int k = 0;
-    while (n % 4 == 0 && k < kFftMaxFactors) {
-        fac[k++] = 4;
-        n /= 4;
-    }
-    for (int r : {2, 3, 5})
-        while (n % r == 0 && k < kFftMaxFactors) {
-            fac[k++] = r;
-            n /= r;
-        }
-    *nfac = k;
-    return n == 1;
-}
-
-bool own_fft_supported(int rank, const int64_t* n) {
-    static const bool off = std::getenv("EFGP_FFT_ROCFFT") != nullptr;        // test / comparison hook: every transform through hipFFT
-    if (off || rank < 1 || rank > 3) return false;
-    for (int a = 0; a < rank; ++a) {
-        int fac[kFftMaxFactors], nf;
-        if (n[a] < 1 || n[a] > kFftMaxLine || !factorize(n[a], fac, &nf)) return false;
-    }
-    return true;
-}
-
 static const double2* twiddle_table(DeviceCtx* ctx, int64_t n, hipStream_t stream) {
     auto it = ctx->twiddles.find(n);
     if (it != ctx->twiddles.end()) return (const double2*)it->second;
@@ -289,7 +262,7 @@ static int launch_pass(DeviceCtx* ctx, const double2* src, double2* dst, int64_t
     p.n = (int)len;
     p.n_src = (int)n_src;
     p.n_dst = (int)n_dst;
-    factorize(len, p.fac, &p.nfac);
+    fft_factorize(len, p.fac, &p.nfac);
     p.stride = stride;
     p.nouter = outer;
     p.ld = (int)len + 1;

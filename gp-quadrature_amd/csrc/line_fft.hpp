@@ -4,7 +4,13 @@
 
 namespace efgp {
 
-// true when every axis length factors into 2, 3, 5 and fits one LDS line (EFGP_FFT_ROCFFT=1 switches the in-house path off)
+constexpr int kFftMaxLine = 4096;            // two LDS buffers of one line: 128 KB
+constexpr int kFftMaxFactors = 12;
+// The next two are arithmetic plus a hook and live in nufft_plan_host.cpp, where the host-only planners reach them.
+// radices (4 first, then 2, 3, 5) of n into fac[0 .. *nfac); false when n has another factor or more than kFftMaxFactors
+bool fft_factorize(int64_t n, int* fac, int* nfac);
+// true when every axis length factors into 2, 3, 5 and fits one LDS line (EFGP_FFT_ROCFFT=1, read once per process, switches the
+// in-house path off)
 bool own_fft_supported(int rank, const int64_t* n);
 // twiddle tables of the axis lengths (allocates and copies once per length: call before a stream capture)
 int own_fft_prepare(DeviceCtx* ctx, int rank, const int64_t* n, hipStream_t stream);

@@ -22,6 +22,7 @@
 #include "common.hpp"
 #include "es_kernel.hpp"
 #include "nufft_dev.hpp"
+#include "nufft_plan_host.hpp"
 #include "points_layout.hpp"
 #include "spread_mfma.hpp"
 #include "small_dft.hpp"
@@ -185,7 +186,7 @@ __global__ __launch_bounds__(kSpreadThreads) void spread_kernel(SpreadArgs a) {
 // positions hold 16 different classes until the rarest class runs out (~86 % of a 4096-point window).
 // The window keeps the gather of x and the strengths inside ~100 KB.  Depends only on (x, fine grid, W, launch
 // geometry): built once per plan and reused by every pass.  (32 classes over 32-lane groups measured no better.)
-constexpr int kOrderWindow = 4096;
+// (kOrderWindow: nufft_plan_host.hpp)
 
 template <int D, int NC>
 __global__ __launch_bounds__(kSpreadThreads) void class_order_kernel(GridGeom g, int W, const double* __restrict__ x, int64_t npts,
@@ -595,17 +596,7 @@ __global__ __launch_bounds__(1024) void reduce_slabs_kernel(const double* __rest
 //   points, and for every tile segment inside it accumulates a (T+W-1)^d LDS tile with the same fixed-point
 //   atomics as the LDS-resident spreader and adds the tile to the int64 global grid.
 // ------------------------------------------------------------------------------------------
-struct TileGeom {
-    int d;
-    int nf[3];
-    int T[3];        // tile size in cells
-    int nt[3];       // tiles per dimension
-    int ext[3];      // T + W - 1: cells an LDS tile spans per dimension (1 for unused dims)
-    int nbins;
-    int W;
-    double scale[3];
-    double xcen[3];
-};
+// (TileGeom: nufft_plan_host.hpp)
 
 template <int D>
 __device__ __forceinline__ int tile_of_point(const TileGeom& t, const double* __restrict__ x, int64_t n) {
@@ -1283,8 +1274,7 @@ __global__ void deconvolve_pair_kernel(const double2* __restrict__ fine, int64_t
 // stage 2 and the epilogue.  Small grids keep one workgroup per tile (the exchange costs more than it saves there).
 // LOG2NF = 7: grids up to 128 x 128 (lane = x1, eight x0 classes); LOG2NF = 8 (round 3: the finer grids dense point sets take,
 // 144..256 cells per axis): 256 lanes per row, four x0 classes, the rows of a class in rounds of 16 loads.
-constexpr int kG2MMaxNf = 256;
-constexpr int kG2MMaxH = 32;                 // modes k in [-32, 32] per axis
+// (kG2MMaxNf, kG2MMaxH: nufft_plan_host.hpp)
 constexpr int kG2MThreads = 1024;
 
 struct G2MArgs {
@@ -1538,7 +1528,7 @@ __global__ __launch_bounds__(kG2MThreads) void grid_to_modes_kernel(G2MArgs a) {
 //                       (two columns of C = 2 nf0 values, every load in flight at once), then the epilogue of
 //                       grid_to_modes_kernel (parts 0 | 3 | 4): the modes k and -k it pairs are both in this workgroup.
 // Sums of <= 256 terms with exact table twiddles, fixed order: equal to the FFT sequence to rounding, reproducible.
-constexpr int kG2RRows = 4;
+// (kG2RRows: nufft_plan_host.hpp)
 constexpr int kG2RThreads = 1024;
 constexpr int kR2MThreads = 256;
 
@@ -1948,8 +1938,7 @@ __global__ __launch_bounds__(kInterpThreads) void interp_real_halo_kernel(Interp
 // ds_read2_b64 (8-byte alignment): twice the LDS cycles per byte (MI355X_MICROARCH section LDS), and the gather is
 // LDS-bound (PMC, round 1).  No processing order is needed: points are streamed as the caller holds them, so x
 // loads and result stores stay coalesced and no per-plan ordering pass exists.
-// 160 KiB of LDS hold 10240 16-byte elements: at most ten per thread in the image fill.
-constexpr int kPairFillTrips = (160 * 1024 / 16 + kInterpThreads - 1) / kInterpThreads;
+// 160 KiB of LDS hold 10240 16-byte elements: at most ten per thread in the image fill (kPairFillTrips, nufft_plan_host.hpp).
 
 template <int W>
 __global__ __launch_bounds__(kInterpThreads) void interp_real2_pair_kernel(InterpArgs a) {
@@ -2039,8 +2028,6 @@ struct WindowSet {          // device copies of the window data for one (toleran
     int64_t nf[3] = {0, 0, 0};
 };
 
-constexpr int64_t kDensePoints = 4000000;
-
 struct ClassOrder {         // see class_order_kernel
     int64_t nf[3];
     int W;
@@ -2091,12 +2078,7 @@ static void free_window(WindowSet* w) {
 // only on (tolerance, dimension, mode box), not on the points, so they are cached per device.
 static int get_window(efgp_nufft_s* plan, const int64_t* n_modes, hipStream_t stream, WindowSet** out) {
     const int d = plan->dim;
-    // from 4e6 points on a 2-D plan takes the finer grid / narrower window (N = 1e7, mtot = 23: spread + gather 316 -> 276 us on
-    // the same box).  The accumulator -> modes step behind them grows with the grid: as ONE launch it went from 20 to 47-60 us
-    // (180 x 180 cells) and ate the gain -- the two-launch form (grid_rows_kernel + rows_modes_kernel) takes 12 / 17 us.
-    const char* dense_env = std::getenv("EFGP_DENSE_POINTS");           // experiments: another threshold for the dense-sigma rule
-    const int64_t dense_from = dense_env ? std::max<int64_t>(1, std::atoll(dense_env)) : kDensePoints;
-    const bool dense = d == 2 && plan->npts >= dense_from && std::getenv("EFGP_NO_DENSE_SIGMA") == nullptr;
+    const bool dense = window_dense(d, plan->npts);
     for (void* vp : plan->ctx->window_cache) {
         WindowSet* w = (WindowSet*)vp;
         bool same = w->dim == d && w->tol == plan->tol && w->dense == dense;
@@ -2107,17 +2089,17 @@ static int get_window(efgp_nufft_s* plan, const int64_t* n_modes, hipStream_t st
             return EFGP_OK;
         }
     }
+    WindowPlan wp;
+    plan_window(d, n_modes, plan->tol, dense, &wp);
     auto* w = new WindowSet();
     w->tol = plan->tol;
     w->dim = d;
     w->dense = dense;
-    double sigma_min = 1e30;
     for (int a = 0; a < 3; ++a) {
-        w->nm[a] = a < d ? n_modes[a] : 1;
-        w->nf[a] = a < d ? es_fine_size(n_modes[a], plan->tol, d, dense) : 1;
-        if (a < d) sigma_min = std::min(sigma_min, (double)w->nf[a] / (double)w->nm[a]);
+        w->nm[a] = wp.nm[a];
+        w->nf[a] = wp.nf[a];
     }
-    es_make_params(plan->tol, sigma_min, &w->p, d);
+    w->p = wp.p;
     const int W = w->p.w, deg = w->p.degree;
     // two tables: [kMaxDegree+1][W] (rows above `deg` stay zero: padded Horner), then the first ceil(W/2)
     // polynomials again as [kMaxDegree+1][sym_row(W)] for window_eval
@@ -2181,6 +2163,30 @@ static GridGeom make_geom(const efgp_nufft_s* plan, const WindowSet* w) {
         g.cells *= w->nf[a];
     }
     return g;
+}
+
+// the plan and its device in the planner's plain numbers (nufft_plan_host.hpp)
+static NufftSite make_site(const efgp_nufft_s* plan) {
+    NufftSite s;
+    s.dim = plan->dim;
+    s.npts = plan->npts;
+    s.tol = plan->tol;
+    s.num_cu = plan->ctx->num_cu;
+    s.max_lds = plan->ctx->max_lds;
+    for (int a = 0; a < 3; ++a) {
+        s.h[a] = plan->h[a];
+        s.xcen[a] = plan->xcen[a];
+    }
+    if (const efgp_points_s* pts = plan->points) {
+        s.has_layout = true;
+        for (int a = 0; a < 3; ++a) {
+            s.lo[a] = pts->lo[a];
+            s.hi[a] = pts->hi[a];
+        }
+        for (const SortedLevel* l : pts->levels)
+            if (s.nlevels < kMaxLevels) s.level_bands[s.nlevels++] = l->nbands;
+    }
+    return s;
 }
 
 static ModeGeom make_modes(const efgp_nufft_s* plan, const WindowSet* w, const int64_t* nm, int modeord) {
@@ -2451,14 +2457,6 @@ static hipError_t launch_interp_halo_d(int W, dim3 grid, size_t lds_bytes, hipSt
     return hipErrorInvalidValue;
 }
 
-// Rows and even row pitch of one parity copy of interp_real2_pair_kernel, and the bytes of the two copies: the size of its
-// LDS and of the image that modes_to_grid_real_kernel writes for it.
-static int interp_pair_rows(int nf0, int W) { return nf0 + W - 1; }
-static int interp_pair_pitch(int nf1, int W) { return (nf1 + 2 * ((W + 1) / 2) + 1) & ~1; }
-static size_t interp_pair_lds_bytes(int nf0, int nf1, int W) {
-    return 2 * (size_t)interp_pair_rows(nf0, W) * (size_t)interp_pair_pitch(nf1, W) * sizeof(double);
-}
-
 static hipError_t launch_interp_pair(int W, dim3 grid, size_t lds_bytes, hipStream_t s, const InterpArgs& a) {
     switch (W) {
 #define EFGP_CASE(w_)                                                                                               \
@@ -2493,45 +2491,7 @@ static hipError_t launch_interp_d(int W, bool cplx, bool use_lds, dim3 grid, siz
     return hipErrorInvalidValue;
 }
 
-// ---- tiled path: geometry, binning, launch -------------------------------------------------------
-// force_tile > 0: use that tile size (1 = bins are single cells, for the cell-sorted spreader)
-static bool make_tile_geom(const efgp_nufft_s* plan, const WindowSet* w, int channels, size_t lds_budget, TileGeom* out,
-                           int force_tile = 0) {
-    TileGeom t;
-    const int d = plan->dim, W = w->p.w;
-    t.d = d;
-    t.W = W;
-    // largest cubic-ish tile whose (T+W-1)^d * channels * 8 B fits the LDS budget
-    const double cells_max = (double)lds_budget / (8.0 * channels);
-    int ext = (int)std::floor(std::pow(cells_max, 1.0 / d));
-    while (ext > W && std::pow((double)ext, d) > cells_max) --ext;
-    int Tmax = ext - (W - 1);
-    if (force_tile > 0) Tmax = force_tile;
-    if (Tmax < 1 || (force_tile == 0 && Tmax < 2)) return false;
-    t.nbins = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (a < d) {
-            t.nf[a] = (int)w->nf[a];
-            t.nt[a] = (t.nf[a] + Tmax - 1) / Tmax;
-            t.T[a] = (t.nf[a] + t.nt[a] - 1) / t.nt[a];
-            t.ext[a] = t.T[a] + W - 1;
-            t.scale[a] = plan->h[a] * (double)w->nf[a];
-            t.xcen[a] = plan->xcen[a];
-            t.nbins *= t.nt[a];
-        } else {
-            t.nf[a] = 1;
-            t.nt[a] = 1;
-            t.T[a] = 1;
-            t.ext[a] = 1;
-            t.scale[a] = 0.0;
-            t.xcen[a] = 0.0;
-        }
-    }
-    if (t.nbins > 16384) return false;          // LDS histograms of the binning kernels (2 x 64 KB)
-    *out = t;
-    return true;
-}
-
+// ---- tiled path: binning, launch (the geometry: make_tile_geom, nufft_plan_host.cpp) -----------------
 static void free_binset(DeviceCtx* ctx, BinSet* b) {
     if (!b) return;
     pool_free(ctx, b->xs, b->xs_bytes);
@@ -2548,8 +2508,7 @@ static int balance_tiles(efgp_nufft_s* plan, BinSet* b, hipStream_t stream) {
     const TileGeom& t = b->t;
     if (b->balanced) return EFGP_OK;
     b->balanced = true;
-    if (!(t.T[0] > 1 && plan->dim >= 2 && plan->npts >= (int64_t)kOrderWindow * 16 && std::getenv("EFGP_NO_CLASS_ORDER") == nullptr))
-        return EFGP_OK;
+    if (!tile_class_order_wanted(plan->dim, plan->npts, t)) return EFGP_OK;
     double* xs2 = (double*)pool_alloc(ctx, b->xs_bytes);
     int* order2 = (int*)pool_alloc(ctx, b->order_bytes);
     if (xs2 && order2) {
@@ -2658,7 +2617,6 @@ static hipError_t launch_tile_d(int W, dim3 grid, size_t lds_bytes, hipStream_t 
 }
 
 // the cell kernel unrolls its Horner loop: degrees are padded up to W + 2 or W + 4 (zero rows in the table)
-constexpr int kCellMaxW = 8;       // register budget: RH^2 accumulators per channel + RH (DEG+1) coefficients
 template <int W>
 static hipError_t launch_cell_w(int channels, int degree, dim3 grid, hipStream_t s, const CellSpreadArgs& a) {
     if (degree <= W + 2) {
@@ -2690,58 +2648,6 @@ static char* scale_slot(DeviceCtx* ctx, hipStream_t stream) {
     return misc;
 }
 
-// Level of the plan's point layout the MFMA spreader can use for this fine grid, or nullptr (no layout, not 2-D,
-// window wider than the register tile, too few points per run to amortise the tile flushes, EFGP_NO_MFMA_SPREAD).
-// *band_cells = bound on the height of the level's bands in fine cells: 1 for dense point sets (>= 192 points per run at
-// one-cell bands: the spreader then needs W + 1 tile columns, fits three waves per SIMD and stores seven zeros less per point),
-// else 8 (the tile's 16 columns hold the 8-cell stencil at offsets 0..8).  EFGP_MFMA_BAND_CELLS = 1 | 8 forces one.
-static SortedLevel* pick_level(efgp_nufft_s* plan, const WindowSet* w, const GridGeom& g, hipStream_t stream, int* band_cells) {
-    efgp_points_s* pts = plan->points;
-    if (!pts || plan->dim != 2 || w->p.w > kMfmaMaxW || plan->npts < 32768 || std::getenv("EFGP_NO_MFMA_SPREAD")) return nullptr;
-    double span[2], far = 0.0;
-    for (int a = 0; a < 2; ++a) {
-        span[a] = (pts->hi[a] - pts->lo[a]) * std::fabs(g.scale[a]);
-        far = std::max(far, std::max(std::fabs(pts->hi[a] - plan->xcen[a]), std::fabs(pts->lo[a] - plan->xcen[a])) * std::fabs(g.scale[a]));
-    }
-    if (!(far < 1e9) || !(g.scale[0] > 0.0) || !(g.scale[1] > 0.0)) return nullptr;      // cell indices are kept in 32-bit ints
-    const char* force = std::getenv("EFGP_MFMA_BAND_CELLS");
-    const int forced = force ? std::atoi(force) : 0;
-    int nb = 0, cells = 0;
-    for (int hb : {1, 8}) {
-        if (forced && forced != hb) continue;
-        int n = 1;
-        while (span[1] / n > (double)hb - 1e-6 && n <= kMaxBands) n *= 2;
-        if (n > kMaxBands) continue;
-        const double per_run = (double)plan->npts / ((double)n * std::max(1.0, span[0]));
-        if (per_run < (forced ? 1.0 : (hb == 1 ? 192.0 : 24.0))) continue;
-        nb = n;
-        cells = hb;
-        if (hb == 8) {
-            // A level costs a sort of the N points (2 ms at N = 1e6) and 28 B per point.  A gradient step makes two plans on one
-            // model -- the Toeplitz box (4 m + 1 modes) and the probe box (mtot modes) on a grid half as fine -- whose coarsest
-            // levels differ by a factor two: the probe plan takes the pair plan's level when it exists (bands 2-4 cells high instead
-            // of 4-8: a few more run ends per band, no second sort; round 4: the layout-building step 4.3 -> 2.4 ms).
-            bool have = false;
-            for (const SortedLevel* l : pts->levels) have = have || l->nbands == n;
-            for (int f = 2; !have && f <= 4; f *= 2) {
-                const double per_run_f = (double)plan->npts / ((double)(n * f) * std::max(1.0, span[0]));
-                if (n * f > kMaxBands || per_run_f < 24.0) break;
-                for (const SortedLevel* l : pts->levels)
-                    if (l->nbands == n * f) {
-                        nb = n * f;
-                        have = true;
-                    }
-            }
-        }
-        break;
-    }
-    if (!nb) return nullptr;
-    SortedLevel* lvl = nullptr;
-    if (points_level(pts, nb, stream, &lvl) != EFGP_OK) return nullptr;
-    *band_cells = cells;
-    return lvl;
-}
-
 // What the caller wants from the transformed grid; when the pass runs on the MFMA spreader's single int64 grid and the grid
 // is small, spread_and_fft hands the accumulator straight to grid_to_modes_kernel and sets `done` (no fine grid is produced).
 struct G2MRequest {
@@ -2765,19 +2671,21 @@ static void apply_crop(const G2MRequest* req, ModeGeom& m, int64_t& cells) {
     }
 }
 
-static bool g2m_eligible(const efgp_nufft_s* plan, const GridGeom& g, const G2MRequest* req) {
-    if (!req || plan->dim != 2 || std::getenv("EFGP_NO_GRID_TO_MODES")) return false;
-    if (g.nf[0] > kG2MMaxNf || g.nf[1] > kG2MMaxNf) return false;
-    for (int a = 0; a < 2; ++a) {
-        if (req->ma.nm[a] / 2 > kG2MMaxH) return false;
-        if (req->part == 4 && req->mb.nm[a] / 2 > kG2MMaxH) return false;
+// the request as the planner sees it
+static ModeBoxes mode_boxes(const G2MRequest& req) {
+    ModeBoxes b;
+    b.part = req.part;
+    for (int a = 0; a < 3; ++a) {
+        b.nma[a] = req.ma.nm[a];
+        b.nmb[a] = req.part == 4 ? req.mb.nm[a] : 1;
     }
-    return true;
+    return b;
 }
 
 // gacc != null: from the MFMA spreader's int64 accumulator (converted, cleared by the kernel); else from the reduced complex grid
-static int g2m_launch(DeviceCtx* ctx, const GridGeom& g, G2MRequest* req, long long* gacc, const double2* fine, const double* scale,
-                      int channels, int nbatch, int isign, unsigned int* ticket, long long acc_words, hipStream_t stream) {
+static int g2m_launch(DeviceCtx* ctx, const Type1Plan& pl, const GridGeom& g, G2MRequest* req, long long* gacc, const double2* fine,
+                      const double* scale, int channels, int nbatch, int isign, unsigned int* ticket, long long acc_words,
+                      hipStream_t stream) {
     G2MArgs ga;
     ga.gacc = gacc;
     ga.fine = fine;
@@ -2785,8 +2693,8 @@ static int g2m_launch(DeviceCtx* ctx, const GridGeom& g, G2MRequest* req, long l
     ga.channels = channels;
     ga.nf0 = (int)g.nf[0];
     ga.nf1 = (int)g.nf[1];
-    ga.h0 = (int)std::max(req->ma.nm[0] / 2, req->part == 4 ? req->mb.nm[0] / 2 : (int64_t)0);
-    ga.h1 = (int)std::max(req->ma.nm[1] / 2, req->part == 4 ? req->mb.nm[1] / 2 : (int64_t)0);
+    ga.h0 = pl.g2m_h[0];
+    ga.h1 = pl.g2m_h[1];
     ga.part = req->part;
     ga.rows_limit = req->rows_limit;
     ga.sign = isign < 0 ? -1 : 1;
@@ -2795,8 +2703,7 @@ static int g2m_launch(DeviceCtx* ctx, const GridGeom& g, G2MRequest* req, long l
     ga.out_a = (double2*)req->out_a;
     ga.out_b = (double2*)req->out_b;
     ga.ticket = ticket;
-    if (std::getenv("EFGP_G2M_V1") == nullptr) {
-        // round 3: two launches -- rows of the accumulator over the chip, then one workgroup per column pair of the mode box
+    if (pl.g2m_two_launch) {
         G2RArgs ra;
         ra.gacc = gacc;
         ra.fine = fine;
@@ -2829,18 +2736,10 @@ static int g2m_launch(DeviceCtx* ctx, const GridGeom& g, G2MRequest* req, long l
     }
     const unsigned tiles = (unsigned)(ga.h0 / 2 + 1);
     const bool small = ga.nf0 <= 128 && ga.nf1 <= 128;
-    // stage-1 split, measured (rocprofv3, launch average): 96 x 96 grid 20.0 / 27.7 / 32.4 / 45.7 us at 1 / 2 / 4 / 8 workgroups
-    // per tile -- the shares' round trip through memory (two device-scope fences, an atomic) costs more than a quarter of stage 1
-    // saves; 180 x 180 grid 59.8 / 51.2 / 47.5 / 56.2 us.
-    int split = small ? 1 : 4;
-    if (const char* e = std::getenv("EFGP_G2M_SPLIT")) split = std::max(1, std::min(16, std::atoi(e)));
-    while (split > 1 && (int64_t)tiles * nbatch * split > 4096) split /= 2;
+    const int split = pl.g2m_split;            // (the tickets of a split launch fit kTicketBytes: plan_type1)
     constexpr size_t kTicketBytes = 65536;
     ga.partial = nullptr;
     ga.tile_ticket = nullptr;
-    if (split > 1) {
-        if ((size_t)tiles * nbatch * sizeof(unsigned int) > kTicketBytes) split = 1;
-    }
     if (split > 1) {
         const size_t bytes = kTicketBytes + (size_t)nbatch * tiles * split * 4 * ga.nf1 * sizeof(double2);
         char* base = (char*)scratch(ctx, SLOT_G2M, bytes);
@@ -2868,7 +2767,7 @@ static int g2m_launch(DeviceCtx* ctx, const GridGeom& g, G2MRequest* req, long l
 // `acc` != null: the caller's spread left its sums in the int64 accumulator and has NOT converted them to `fine`; the pruned
 // transform's first pass reads (and, if asked, clears) the accumulator itself -- one pass over the grid less per type-1
 // transform (reduce_slabs_kernel: 197 us of a 3-D pair transform at 240^3); every other route converts first.
-static int transform_fine(efgp_nufft_s* plan, const GridGeom& g, double2* fine, int nbatch, int isign, hipStream_t stream,
+static int transform_fine(efgp_nufft_s* plan, const Type1Plan& pl, const GridGeom& g, double2* fine, int nbatch, int isign, hipStream_t stream,
                           G2MRequest* req, const double* scale, double2** fine_out, const FftAccSource* acc = nullptr) {
     auto convert = [&]() -> int {
         if (!acc) return EFGP_OK;
@@ -2878,43 +2777,32 @@ static int transform_fine(efgp_nufft_s* plan, const GridGeom& g, double2* fine, 
         EFGP_HIP_CHECK(hipGetLastError());
         return EFGP_OK;
     };
-    if (g2m_eligible(plan, g, req)) {
-        const int rcc = convert();
-        if (rcc != EFGP_OK) return rcc;
-        *fine_out = nullptr;
-        return g2m_launch(plan->ctx, g, req, nullptr, fine, scale, 2, nbatch, isign, nullptr, 0, stream);
-    }
-    // In-house pruned transform when the caller said which modes it wants: every pass keeps only the bins of the (larger) mode
-    // box, so the strided passes and the extraction behind them run on a fraction of the grid (line_fft.hip).
-    if (req && own_fft_supported(plan->dim, g.nf) && std::getenv("EFGP_NO_PRUNED_FFT") == nullptr) {
-        int64_t nc[3] = {1, 1, 1}, wk = nbatch;
-        bool smaller = false;
-        for (int a = 0; a < plan->dim; ++a) {
-            int64_t hmax = req->ma.nm[a] / 2;
-            if (req->part == 4) hmax = std::max(hmax, req->mb.nm[a] / 2);
-            nc[a] = std::min<int64_t>(2 * hmax + 1, g.nf[a]);
-            smaller = smaller || nc[a] < g.nf[a];
-            wk *= a == plan->dim - 1 ? nc[a] : g.nf[a];
-        }
-        if (smaller) {
-            double2* work = (double2*)scratch(plan->ctx, SLOT_FFT_WORK, (size_t)wk * sizeof(double2));
+    int rcc = EFGP_OK;
+    switch (pl.after) {
+        case AfterSpread::g2m_from_acc:        // (spread_on_layout launches that one itself)
+        case AfterSpread::g2m:
+            if ((rcc = convert()) != EFGP_OK) return rcc;
+            *fine_out = nullptr;
+            return g2m_launch(plan->ctx, pl, g, req, nullptr, fine, scale, 2, nbatch, isign, nullptr, 0, stream);
+        case AfterSpread::pruned_from_acc:
+        case AfterSpread::pruned: {
+            // every pass keeps only the bins of the (larger) mode box, so the strided passes and the extraction behind them run on
+            // a fraction of the grid (line_fft.hip)
+            double2* work = (double2*)scratch(plan->ctx, SLOT_FFT_WORK, (size_t)pl.work_cells * sizeof(double2));
             if (!work) return EFGP_ENOMEM;
             double2* res = nullptr;
-            const bool fuse = acc && g.nf[plan->dim - 1] > 1 && std::getenv("EFGP_NO_FFT_FROM_ACC") == nullptr;
-            if (!fuse) {
-                const int rcc = convert();
-                if (rcc != EFGP_OK) return rcc;
-            }
-            const int rcp = own_fft_pruned_forward(plan->ctx, plan->dim, g.nf, nc, nbatch, fine, work, isign < 0, &res, stream, fuse ? acc : nullptr);
+            const bool fuse = pl.after == AfterSpread::pruned_from_acc;
+            if (!fuse && (rcc = convert()) != EFGP_OK) return rcc;
+            const int rcp = own_fft_pruned_forward(plan->ctx, plan->dim, g.nf, pl.nc, nbatch, fine, work, isign < 0, &res, stream, fuse ? acc : nullptr);
             if (rcp != EFGP_OK) return rcp;
             req->cropped = true;
-            for (int a = 0; a < 3; ++a) req->crop_nf[a] = nc[a];
+            for (int a = 0; a < 3; ++a) req->crop_nf[a] = pl.nc[a];
             *fine_out = res;
             return EFGP_OK;
         }
+        case AfterSpread::fft: break;
     }
-    const int rcc = convert();
-    if (rcc != EFGP_OK) return rcc;
+    if ((rcc = convert()) != EFGP_OK) return rcc;
     const int rc = fft_c2c(plan->ctx, plan->dim, g.nf, nbatch, fine, isign < 0, stream);      // in-house line kernels, hipFFT beyond their sizes
     if (rc != EFGP_OK) return rc;
     *fine_out = fine;
@@ -3031,6 +2919,7 @@ struct SpreadCall {           // one spread_and_fft call as its four routes see 
     double2** fine_out;
     bool want_scale;                  // the caller asked where the pass's scale block is (type1_pair: deconvolve_pair_kernel reads it)
     const double* scale = nullptr;    // ... and this is the answer; stays null for a caller that did not ask
+    Type1Plan pl;                     // the pass as planned (nufft_plan_host.cpp): the routes execute it
     void publish_scale(const double* d_scale) {
         if (want_scale) scale = d_scale;
     }
@@ -3071,7 +2960,7 @@ static void int64_grid_converted(DeviceCtx* ctx, const Int64Grid& a) {
 
 // 2-D plans made on a per-model point layout (efgp_nufft_create_on): MFMA register accumulation over
 // (band, x_0)-sorted points, no per-plan sorting (spread_mfma.hip)
-static int spread_on_layout(SpreadCall& s, SortedLevel* lvl, int band_cells) {
+static int spread_on_layout(SpreadCall& s, SortedLevel* lvl) {
     efgp_nufft_s* plan = s.plan;
     efgp_points_s* pts = plan->points;
     const SpreadJob& job = s.job;
@@ -3086,8 +2975,7 @@ static int spread_on_layout(SpreadCall& s, SortedLevel* lvl, int band_cells) {
     int rc = acquire_int64_grid(s, &a);
     if (rc != EFGP_OK) return rc;
     double* d_scale = (double*)a.misc;
-    // the global int64 grid sums over ALL points: the scale is bounded with N
-    ScaleJob sj = scale_job(job, plan->npts, 61, d_scale);
+    ScaleJob sj = scale_job(job, s.pl.sum_points, s.pl.sum_bits, d_scale);
     const bool cached_max = job.need_max && ys && pts->d_values_max;
     if (cached_max && job.ones_channel) {
         // the fit-time pair on the attached targets: max|y|, N and the bit budget are fixed per model, so the scale block is
@@ -3112,11 +3000,11 @@ static int spread_on_layout(SpreadCall& s, SortedLevel* lvl, int band_cells) {
     }
     EFGP_HIP_CHECK(hipGetLastError());
     s.publish_scale(d_scale);
-    rc = spread_mfma_launch(plan->ctx, lvl, band_cells, ys, job.src, s.g, s.w->p.w, s.w->d_coef, s.w->p.degree, job.channels, s.nbatch,
+    rc = spread_mfma_launch(plan->ctx, lvl, s.pl.level.band_cells, ys, job.src, s.g, s.w->p.w, s.w->d_coef, s.w->p.degree, job.channels, s.nbatch,
                             (unsigned long long*)a.gacc, d_scale, stream);
     if (rc != EFGP_OK) return rc;
-    if (g2m_eligible(plan, s.g, s.req)) {
-        rc = g2m_launch(plan->ctx, s.g, s.req, a.gacc, nullptr, d_scale, job.channels, s.nbatch, s.isign, (unsigned int*)(a.misc + 40),
+    if (s.pl.after == AfterSpread::g2m_from_acc) {
+        rc = g2m_launch(plan->ctx, s.pl, s.g, s.req, a.gacc, nullptr, d_scale, job.channels, s.nbatch, s.isign, (unsigned int*)(a.misc + 40),
                         (long long)(a.acc_bytes / sizeof(long long)), stream);
         if (rc != EFGP_OK) return rc;
         int64_grid_converted(plan->ctx, a);
@@ -3125,22 +3013,12 @@ static int spread_on_layout(SpreadCall& s, SortedLevel* lvl, int band_cells) {
     }
     const FftAccSource accsrc{a.gacc, job.channels, s.g.cells, (const double*)d_scale, 1};     // converted (and cleared) by whoever reads it
     int64_grid_converted(plan->ctx, a);
-    return transform_fine(plan, s.g, a.fine, s.nbatch, s.isign, stream, s.req, s.scale, s.fine_out, &accsrc);
+    return transform_fine(plan, s.pl, s.g, a.fine, s.nbatch, s.isign, stream, s.req, s.scale, s.fine_out, &accsrc);
 }
 
-// 2-D with many points per fine-grid cell: register accumulation over base-cell-sorted points.
-// Opt-in (EFGP_CELLSORT=1): the kernel itself is 1.2-1.7x faster than the LDS-atomic spreader at >= 250 points
-// per cell, but the per-plan counting sort it needs (0.15 ms at N=1e6, 0.6 ms at N=1e7) only pays off after
-// several passes over the same plan; see LABNOTES.md section 4.1.
-static bool cell_sort_wanted(const SpreadCall& s, TileGeom* cg) {
-    const efgp_nufft_s* plan = s.plan;
-    const EsParams& p = s.w->p;
-    const char* force = std::getenv("EFGP_CELLSORT");
-    const bool use_cells = force && force[0] == '1' && !strength_is_normal(s.job.src.mode) && plan->dim == 2 && p.w <= kCellMaxW &&
-                           p.degree <= p.w + 4 && s.g.cells <= 16384 && plan->npts > 0;
-    return use_cells && make_tile_geom(plan, s.w, s.job.channels, (size_t)plan->ctx->max_lds - 4096, cg, 1);
-}
-static int spread_cell_sorted(SpreadCall& s, const TileGeom& cg) {
+// 2-D with many points per fine-grid cell: register accumulation over base-cell-sorted points (opt-in, see plan_type1)
+static int spread_cell_sorted(SpreadCall& s) {
+    const TileGeom& cg = s.pl.tile;
     efgp_nufft_s* plan = s.plan;
     DeviceCtx* ctx = plan->ctx;
     const WindowSet* w = s.w;
@@ -3187,11 +3065,12 @@ static int spread_cell_sorted(SpreadCall& s, const TileGeom& cg) {
     hipLaunchKernelGGL((reduce_slabs_kernel<false>), dim3(rb, nbatch), dim3(512), 0, stream, (const double*)gacc, 1,
                        channels, g.cells, (const double*)nullptr, fine);
     EFGP_HIP_CHECK(hipGetLastError());
-    return transform_fine(plan, g, fine, nbatch, s.isign, stream, s.req, s.scale, s.fine_out);
+    return transform_fine(plan, s.pl, g, fine, nbatch, s.isign, stream, s.req, s.scale, s.fine_out);
 }
 
 // grids beyond LDS with many points: tile-sorted points + LDS tiles, added to one global int64 grid
-static int spread_tiled(SpreadCall& s, const TileGeom& tg) {
+static int spread_tiled(SpreadCall& s) {
+    const TileGeom& tg = s.pl.tile;
     efgp_nufft_s* plan = s.plan;
     DeviceCtx* ctx = plan->ctx;
     const WindowSet* w = s.w;
@@ -3205,8 +3084,7 @@ static int spread_tiled(SpreadCall& s, const TileGeom& tg) {
     if (rc != EFGP_OK) return rc;
     double* d_scale = (double*)a.misc;
     s.publish_scale(d_scale);
-    // the global int64 grid sums over ALL points: bound the scale with N instead of points per workgroup
-    enqueue_scale(s.job, scale_job(s.job, plan->npts, 61, d_scale), a.misc, stream);
+    enqueue_scale(s.job, scale_job(s.job, s.pl.sum_points, s.pl.sum_bits, d_scale), a.misc, stream);
     EFGP_HIP_CHECK(hipGetLastError());
     TileSpreadArgs ta;
     ta.t = tg;
@@ -3237,30 +3115,22 @@ static int spread_tiled(SpreadCall& s, const TileGeom& tg) {
     }
     const FftAccSource accsrc{a.gacc, channels, s.g.cells, (const double*)d_scale, 1};     // converted (and cleared) by whoever reads it
     int64_grid_converted(ctx, a);
-    return transform_fine(plan, s.g, a.fine, s.nbatch, s.isign, stream, s.req, s.scale, s.fine_out, &accsrc);
+    return transform_fine(plan, s.pl, s.g, a.fine, s.nbatch, s.isign, stream, s.req, s.scale, s.fine_out, &accsrc);
 }
 
 // fine grids inside LDS: one slab per workgroup, summed by reduce_slabs_kernel; grids beyond LDS with few points: global atomics
 // on one slab.  Also the route of a plan without points (zeroed slab, plain reduction).
-static int spread_lds_or_global(SpreadCall& s, bool use_lds, size_t lds_bytes) {
+static int spread_lds_or_global(SpreadCall& s) {
     efgp_nufft_s* plan = s.plan;
     DeviceCtx* ctx = plan->ctx;
     const WindowSet* w = s.w;
     const GridGeom& g = s.g;
-    const int channels = s.job.channels, nbatch = s.nbatch, mode = s.job.src.mode;
+    const int channels = s.job.channels, nbatch = s.nbatch;
     hipStream_t stream = s.stream;
-    int nwg = 1;
-    if (use_lds) {
-        int per_cu = std::max(1, std::min(2, (int)((size_t)ctx->max_lds / std::max<size_t>(lds_bytes, 1))));
-        // LDS-atomic bound: spread the points over as many CUs as there are full 1024-point chunks (each workgroup also
-        // pays a 147-KB zero + flush, ~5 us, so not below one point per thread)
-        int64_t want = (plan->npts + kSpreadThreads - 1) / kSpreadThreads;
-        nwg = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)ctx->num_cu * per_cu, want));
-    } else {
-        int64_t want = (plan->npts + kSpreadThreads - 1) / kSpreadThreads;
-        nwg = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)ctx->num_cu * 8, want));
-    }
-    const int nslab = use_lds ? nwg : 1;
+    const Type1Plan& pl = s.pl;
+    const bool use_lds = pl.use_lds;
+    const bool raw48 = pl.spreader == Spreader::lds_pad_raw48, use_pad = raw48 || pl.spreader == Spreader::lds_pad_61;
+    const int nwg = pl.nwg, nslab = pl.nslab;
     const size_t slab_bytes = (size_t)nbatch * nslab * channels * (size_t)g.cells * sizeof(double);
     double* slabs = (double*)scratch(ctx, SLOT_SLABS, slab_bytes);
     double2* fine = (double2*)scratch(ctx, SLOT_FINE, (size_t)nbatch * (size_t)g.cells * sizeof(double2));
@@ -3269,22 +3139,10 @@ static int spread_lds_or_global(SpreadCall& s, bool use_lds, size_t lds_bytes) {
     double* d_scale = (double*)misc;                                  // [0] S0, [1] 1/S0, [2] S1, [3] 1/S1
     if (!use_lds) EFGP_HIP_CHECK(hipMemsetAsync(slabs, 0, slab_bytes, stream));
 
-    const int64_t per = (plan->npts + nwg - 1) / std::max(nwg, 1);
-    // padded-row variant when the padded grid still fits LDS; 48-bit raw accumulation when its rounding
-    // floor (points per workgroup * 2^-47 relative to max|c|) stays two orders below the requested tolerance
-    const int64_t nlast = g.nf[plan->dim - 1];
-    const size_t pad_bytes = (size_t)channels * (size_t)(g.cells / nlast) * (size_t)(nlast + w->p.w - 1) * sizeof(double);
-    const bool use_pad = use_lds && pad_bytes + 4608 <= (size_t)ctx->max_lds && std::getenv("EFGP_NO_PAD") == nullptr;   // + class lists
-    const bool raw48 = use_pad && (double)per * std::ldexp(1.0, -47) <= 0.01 * plan->tol && std::getenv("EFGP_NO_RAW48") == nullptr &&
-                       !strength_is_normal(mode);     // normals: max|c| is 8.6 typical magnitudes, the raw floor would be that much coarser
     if (plan->npts > 0) {      // (both forms: LDS tiles per workgroup, or one global int64 grid)
         s.publish_scale(d_scale);
         // fixed-point scale from max |c| (device side, no host round trip)
-        // raw48: every workgroup's sums stay below 2^46 and reduce_slabs_kernel adds at most 512 of them in int64.
-        // Otherwise the bound must hold for the SUM OVER ALL SLABS (reduce_slabs_kernel adds them in plain int64):
-        // bounding only one workgroup's share let same-sign strengths (the all-ones channel, clustered points) wrap
-        // the total, e.g. 1-D, N = 1e6, tol <= 1e-9: 512 slabs x 2^61 / 1954 points each.
-        enqueue_scale(s.job, scale_job(s.job, raw48 ? per : plan->npts, raw48 ? 46 : 61, d_scale), misc, stream);
+        enqueue_scale(s.job, scale_job(s.job, pl.sum_points, pl.sum_bits, d_scale), misc, stream);
         EFGP_HIP_CHECK(hipGetLastError());
     }
 
@@ -3300,20 +3158,19 @@ static int spread_lds_or_global(SpreadCall& s, bool use_lds, size_t lds_bytes) {
     a.nslab = nslab;
     a.scale = d_scale;
     a.order = nullptr;
-    // per-plan bank-balanced order (d >= 2, enough points for the one-off pass to pay)
-    if (use_pad && plan->dim >= 2 && plan->npts >= (int64_t)kOrderWindow * 64 && std::getenv("EFGP_NO_CLASS_ORDER") == nullptr) {
-        int rc = get_class_order(plan, w, g, nwg, per, stream, &a.order);
+    if (pl.class_order) {
+        int rc = get_class_order(plan, w, g, nwg, pl.per, stream, &a.order);
         if (rc != EFGP_OK) return rc;
     }
     dim3 grid(nwg, nbatch);
     hipError_t e = hipSuccess;
     if (plan->npts > 0 && use_pad) {
         KernelTimer timer("spread", stream);
-        e = by_dim(plan->dim, [&](auto D) { return launch_spread_pad_d<decltype(D)::value>(w->p.w, raw48, grid, pad_bytes, stream, a); });
+        e = by_dim(plan->dim, [&](auto D) { return launch_spread_pad_d<decltype(D)::value>(w->p.w, raw48, grid, pl.pad_bytes, stream, a); });
     } else if (plan->npts > 0) {
         KernelTimer timer("spread", stream);
         e = by_dim(plan->dim, [&](auto D) {
-            return launch_spread_d<decltype(D)::value>(w->p.w, use_lds, grid, use_lds ? lds_bytes : 0, stream, a);
+            return launch_spread_d<decltype(D)::value>(w->p.w, use_lds, grid, use_lds ? pl.lds_bytes : 0, stream, a);
         });
     } else {
         EFGP_HIP_CHECK(hipMemsetAsync(slabs, 0, slab_bytes, stream));
@@ -3330,28 +3187,28 @@ static int spread_lds_or_global(SpreadCall& s, bool use_lds, size_t lds_bytes) {
         hipLaunchKernelGGL((reduce_slabs_kernel<false>), dim3(blocks, nbatch), dim3(512), 0, stream, slabs, nslab,
                            channels, g.cells, (const double*)d_scale, fine);
     EFGP_HIP_CHECK(hipGetLastError());
-    return transform_fine(plan, g, fine, nbatch, s.isign, stream, s.req, s.scale, s.fine_out);
+    return transform_fine(plan, s.pl, g, fine, nbatch, s.isign, stream, s.req, s.scale, s.fine_out);
 }
 
 // spread + reduce + FFT; leaves the transformed fine grids in SLOT_FINE (*fine_out), or the requested modes in the request's
-// outputs (req->done).  The routes are tried in this order; the first whose predicate holds runs the pass.
+// outputs (req->done).  plan_type1 chose the route; a layout level that cannot be made sends the pass to the route it would have
+// taken without a layout.
 static int spread_and_fft(efgp_nufft_s* plan, WindowSet* w, const SpreadJob& job, int nbatch, int isign, hipStream_t stream,
                           double2** fine_out, G2MRequest* req, const double** scale_out = nullptr) {
     SpreadCall s{plan, w, make_geom(plan, w), job, nbatch, isign, stream, req, fine_out, scale_out != nullptr};
-    const size_t lds_bytes = (size_t)job.channels * (size_t)s.g.cells * sizeof(double);
-    const bool use_lds = lds_bytes <= (size_t)plan->ctx->max_lds && plan->npts > 0;
-    int band_cells = 8;
-    TileGeom tg;
+    const NufftSite site = make_site(plan);
+    const ModeBoxes boxes = req ? mode_boxes(*req) : ModeBoxes();
+    const bool normal = strength_is_normal(job.src.mode);
+    s.pl = plan_type1(site, w->nf, w->p, job.channels, normal, nbatch, req ? &boxes : nullptr);
+    SortedLevel* lvl = nullptr;
+    if (s.pl.spreader == Spreader::layout && points_level(plan->points, s.pl.level.nbands, stream, &lvl) != EFGP_OK)
+        s.pl = plan_type1(site, w->nf, w->p, job.channels, normal, nbatch, req ? &boxes : nullptr, /*allow_layout*/ false);
     int rc;
-    if (SortedLevel* lvl = pick_level(plan, w, s.g, stream, &band_cells)) {
-        rc = spread_on_layout(s, lvl, band_cells);
-    } else if (cell_sort_wanted(s, &tg)) {
-        rc = spread_cell_sorted(s, tg);
-    } else if (!use_lds && plan->npts >= 32768 && std::getenv("EFGP_NO_TILES") == nullptr &&
-               make_tile_geom(plan, w, job.channels, (size_t)plan->ctx->max_lds - 4096, &tg)) {
-        rc = spread_tiled(s, tg);         // else global atomics (small N)
-    } else {
-        rc = spread_lds_or_global(s, use_lds, lds_bytes);
+    switch (s.pl.spreader) {
+        case Spreader::layout: rc = spread_on_layout(s, lvl); break;
+        case Spreader::cells: rc = spread_cell_sorted(s); break;
+        case Spreader::tiles: rc = spread_tiled(s); break;
+        default: rc = spread_lds_or_global(s); break;
     }
     if (scale_out) *scale_out = s.scale;
     return rc;
@@ -3682,38 +3539,9 @@ static int type2_check(const efgp_nufft_t* plan, const void* f, int nbatch, cons
     return EFGP_OK;
 }
 
-// How the gather will hold the fine grid in LDS.  Decided before the grid is filled: the grid kernel may write the gather's image.
-struct GatherRoute {
-    bool cplx;
-    bool direct_grid;     // small 2-D real-output transforms: the real fine grid by ONE dense-DFT launch instead of precorrect + two FFT kernels
-    bool use_halo;        // real outputs: halo-padded LDS copy when it fits (no wrap arithmetic in the gather)
-    bool use_pair;        // 2-D real outputs whose two parity copies fit LDS: aligned 16-byte reads, no processing order
-    bool use_image;       // ... and the grid kernel writes those two copies itself, laid out as the gather holds them: the fill is a flat copy
-    size_t lds_bytes, pair_bytes;
-};
-static GatherRoute pick_gather(const efgp_nufft_s* plan, const WindowSet* w, const GridGeom& g, int nbatch, const int64_t* n_modes,
-                               int real_only) {
-    const size_t max_lds = (size_t)plan->ctx->max_lds;
-    GatherRoute r;
-    r.direct_grid = real_only && nbatch == 1 && plan->dim == 2 &&
-                    modes_to_grid_real_eligible((int)g.nf[0], (int)g.nf[1], (int)n_modes[0], (int)n_modes[1]);
-    r.cplx = !real_only;
-    r.lds_bytes = (size_t)g.cells * (r.cplx ? sizeof(double2) : sizeof(double));
-    size_t halo_cells = 1;
-    for (int a_ = 0; a_ < plan->dim; ++a_) halo_cells *= (size_t)(g.nf[a_] + w->p.w - 1);
-    r.use_halo = !r.cplx && halo_cells * sizeof(double) <= max_lds && std::getenv("EFGP_NO_HALO") == nullptr;
-    if (r.use_halo) r.lds_bytes = halo_cells * sizeof(double);
-    r.pair_bytes = plan->dim == 2 ? interp_pair_lds_bytes((int)g.nf[0], (int)g.nf[1], w->p.w) : 0;
-    r.use_pair = r.use_halo && plan->dim == 2 && r.pair_bytes <= max_lds && std::getenv("EFGP_NO_PAIR_GATHER") == nullptr;
-    if (r.use_pair) r.lds_bytes = r.pair_bytes;
-    r.use_image = r.direct_grid && r.use_pair && r.pair_bytes <= (size_t)kPairFillTrips * kInterpThreads * sizeof(double2) &&
-                  std::getenv("EFGP_NO_GATHER_IMAGE") == nullptr;
-    return r;
-}
-
 // the fine grid from the modes: one dense-DFT launch (with or without the gather's image), else corrected modes + the in-house
 // pruned transform, else corrected modes on the full grid + the FFT in place
-static int modes_to_fine(efgp_nufft_s* plan, const WindowSet* w, const GridGeom& g, const GatherRoute& r, const void* f,
+static int modes_to_fine(efgp_nufft_s* plan, const WindowSet* w, const GridGeom& g, const Type2Plan& r, const void* f,
                          const void* mode_scale, int nbatch, const int64_t* n_modes, int isign, int modeord, int real_only, double2* fine,
                          hipStream_t stream) {
     DeviceCtx* ctx = plan->ctx;
@@ -3729,24 +3557,16 @@ static int modes_to_fine(efgp_nufft_s* plan, const WindowSet* w, const GridGeom&
     int threads = 256;
     // In-house pruned transform: the corrected modes go to a compact array (the 2 (nm/2) + 1 lowest bins per axis), the passes
     // expand it axis by axis, slowest first -- only the last, contiguous pass writes the full grid (line_fft.hip).
-    int64_t nc[3] = {1, 1, 1}, ccells = 1, region = nbatch;
-    bool smaller = false;
-    for (int a = 0; a < plan->dim; ++a) {
-        nc[a] = std::min<int64_t>(2 * (n_modes[a] / 2) + 1, g.nf[a]);
-        smaller = smaller || nc[a] < g.nf[a];
-        ccells *= nc[a];
-        region *= a == plan->dim - 1 ? nc[a] : g.nf[a];
-    }
-    if (smaller && own_fft_supported(plan->dim, g.nf) && std::getenv("EFGP_NO_PRUNED_FFT") == nullptr) {
-        double2* work = (double2*)scratch(ctx, SLOT_FFT_WORK, (size_t)2 * (size_t)region * sizeof(double2));
+    if (r.grid == GridSource::pruned) {
+        double2* work = (double2*)scratch(ctx, SLOT_FFT_WORK, (size_t)2 * (size_t)r.region * sizeof(double2));
         if (!work) return EFGP_ENOMEM;
         ModeGeom mc = m;
-        for (int a = 0; a < plan->dim; ++a) mc.nf[a] = nc[a];
-        int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((ccells + threads - 1) / threads, 2048));
+        for (int a = 0; a < plan->dim; ++a) mc.nf[a] = r.nc[a];
+        int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((r.ccells + threads - 1) / threads, 2048));
         hipLaunchKernelGGL(precorrect_kernel, dim3(blocks, nbatch), dim3(threads), 0, stream, (const double2*)f,
-                           (const double2*)mode_scale, mc, real_only ? 1 : 0, ccells, work);
+                           (const double2*)mode_scale, mc, real_only ? 1 : 0, r.ccells, work);
         EFGP_HIP_CHECK(hipGetLastError());
-        return own_fft_pruned_backward(ctx, plan->dim, nc, g.nf, nbatch, work, fine, work, region, isign < 0, stream);
+        return own_fft_pruned_backward(ctx, plan->dim, r.nc, g.nf, nbatch, work, fine, work, r.region, isign < 0, stream);
     }
     int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((g.cells + threads - 1) / threads, 2048));
     hipLaunchKernelGGL(precorrect_kernel, dim3(blocks, nbatch), dim3(threads), 0, stream, (const double2*)f,
@@ -3791,15 +3611,11 @@ static int gather_tiled(efgp_nufft_s* plan, const WindowSet* w, const GridGeom& 
 
 // the fine grid to the points: tiles when the grid is beyond LDS and the points are many; else the pair, the halo or the plain
 // gather, from LDS when the grid fits and through L2 when not
-static int gather(efgp_nufft_s* plan, const WindowSet* w, const GridGeom& g, const GatherRoute& r, const double2* fine, int nbatch,
+static int gather(efgp_nufft_s* plan, const WindowSet* w, const GridGeom& g, const Type2Plan& r, const double2* fine, int nbatch,
                   void* out, hipStream_t stream) {
-    DeviceCtx* ctx = plan->ctx;
     const size_t lds_bytes = r.lds_bytes;
-    const bool use_lds = lds_bytes <= (size_t)ctx->max_lds;
-    TileGeom tg;
-    if (!use_lds && plan->npts >= 32768 && std::getenv("EFGP_NO_TILES") == nullptr &&
-        make_tile_geom(plan, w, r.cplx ? 2 : 1, (size_t)ctx->max_lds - 4096, &tg))
-        return gather_tiled(plan, w, g, tg, r.cplx, fine, nbatch, out, stream);
+    const bool use_lds = r.use_lds;
+    if (r.gather == Gather::tiles) return gather_tiled(plan, w, g, r.tile, r.cplx, fine, nbatch, out, stream);
     InterpArgs a;
     a.x = plan->x;
     a.npts = plan->npts;
@@ -3809,24 +3625,12 @@ static int gather(efgp_nufft_s* plan, const WindowSet* w, const GridGeom& g, con
     a.fine = fine;
     a.image = r.use_image ? (const double*)fine : nullptr;
     a.out = out;
-    const int thr = use_lds ? kInterpThreads : kInterpThreadsGlobal;
-    int64_t want = (plan->npts + thr - 1) / thr;
-    int nwg;
-    if (use_lds) {
-        int per_cu = std::max(1, std::min(4, (int)((size_t)ctx->max_lds / std::max<size_t>(lds_bytes, 1))));
-        // each workgroup pays one fine-grid copy into LDS: keep >= 2 points per thread
-        int64_t cap = std::max<int64_t>(1, plan->npts / (2 * kInterpThreads));
-        nwg = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((int64_t)ctx->num_cu * per_cu, want), cap));
-    } else {
-        nwg = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)ctx->num_cu * 8, want));
-    }
     a.order = nullptr;
-    if (r.use_halo && !r.use_pair && plan->dim >= 2 && plan->npts >= (int64_t)kOrderWindow * 64 &&
-        std::getenv("EFGP_NO_CLASS_ORDER") == nullptr) {
+    if (r.class_order) {
         int rc = get_class_order(plan, w, g, 0, 0, stream, &a.order);
         if (rc != EFGP_OK) return rc;
     }
-    dim3 grid(nwg, nbatch);
+    dim3 grid(r.nwg, nbatch);
     hipError_t e;
     KernelTimer timer("interp", stream);
     if (r.use_pair) {
@@ -3856,9 +3660,8 @@ static int type2_impl(efgp_nufft_t* plan, const void* f, const void* mode_scale,
     rc = get_window(plan, n_modes, stream, &w);
     if (rc != EFGP_OK) return rc;
     const GridGeom g = make_geom(plan, w);
-    const GatherRoute r = pick_gather(plan, w, g, nbatch, n_modes, real_only);
-    const size_t fine_bytes = (size_t)nbatch * (size_t)g.cells * sizeof(double2);
-    double2* fine = (double2*)scratch(plan->ctx, SLOT_FINE, r.use_image ? std::max(fine_bytes, r.pair_bytes) : fine_bytes);
+    const Type2Plan r = plan_type2(make_site(plan), w->nf, w->p, n_modes, nbatch, real_only != 0);
+    double2* fine = (double2*)scratch(plan->ctx, SLOT_FINE, r.fine_bytes);
     if (!fine) return EFGP_ENOMEM;
     rc = modes_to_fine(plan, w, g, r, f, mode_scale, nbatch, n_modes, isign, modeord, real_only, fine, stream);
     if (rc != EFGP_OK) return rc;

@@ -9,11 +9,12 @@
 // Reference operation replaced: the mode placement / correction + FFT inside finufft type 2 (efgpnd.py:1533-1536).
 #include "small_dft.hpp"
 
+#include "nufft_plan_host.hpp"
+
 #include <algorithm>
 
 namespace efgp {
 
-constexpr int kDftMaxNf = 128;
 constexpr int kDftThreads = 256;
 
 // ---- type 2 side -------------------------------------------------------------------------------------------------
@@ -111,9 +112,6 @@ __global__ __launch_bounds__(kDftThreads) void modes_to_grid_real_kernel(M2GArgs
     }
 }
 
-bool modes_to_grid_real_eligible(int nf0, int nf1, int nm0, int nm1) {
-    return nf0 <= kDftMaxNf && nf1 <= kDftMaxNf && nm0 <= 64 && nm1 <= 64 && std::getenv("EFGP_NO_DIRECT_DFT") == nullptr;
-}
 
 int modes_to_grid_real_launch(DeviceCtx* ctx, const double2* f, const double2* mul, int nm0, int nm1, int modeord, int isign,
                               const double* fac0, const double* fac1, int nf0, int nf1, double2* fine, double* image, int p0, int p1,

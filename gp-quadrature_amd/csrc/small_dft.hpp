@@ -9,6 +9,5 @@ namespace efgp {
 int modes_to_grid_real_launch(DeviceCtx* ctx, const double2* f, const double2* mul, int nm0, int nm1, int modeord, int isign,
                               const double* fac0, const double* fac1, int nf0, int nf1, double2* fine, double* image, int p0, int p1,
                               hipStream_t stream);
-bool modes_to_grid_real_eligible(int nf0, int nf1, int nm0, int nm1);
 
 }  // namespace efgp

@@ -474,7 +474,7 @@ int spread_mfma_launch(DeviceCtx* ctx, const SortedLevel* lvl, int band_cells, c
     // waves and compact rows 231-241 us; a software-pipelined one-wave-per-SIMD variant with double-buffered rows that
     // interleaves the polynomials of batch n + 1 with the MFMAs of batch n 288-296 us -- the compiler's conservative
     // s_waitcnt vmcnt(0) at the merge of its two paths exposes the HBM latency of the prefetched points.)
-    // Round 3, bands at most ONE cell high (band_cells = 1; pick_level chooses it for dense point sets): 13.2 KB of rows per
+    // Round 3, bands at most ONE cell high (band_cells = 1; plan_level chooses it for dense point sets): 13.2 KB of rows per
     // wave and 168 VGPRs -> three workgroups of four waves per CU.
     int waves = 4, per_cu = (band_cells == 1 && !strength_is_normal(src.mode)) ? 3 : 2;
     if (const char* e1 = std::getenv("EFGP_MFMA_WAVES")) waves = std::max(1, std::min(kMfmaMaxWaves, std::atoi(e1)));

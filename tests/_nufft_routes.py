@@ -1,9 +1,12 @@
 """The host dispatch of csrc/nufft.hip restated in Python, the named cases of tests/test_gpu_nufft_options.py and their points.
 
-The restated predicates (spread_and_fft, spread_lds_or_global, g2m_eligible, transform_fine, pick_level's per_run rule, pick_gather,
-modes_to_fine, gather, make_tile_geom) take the window of a case from the library's own host functions, so
+The restated predicates (csrc/nufft_plan_host.cpp: plan_type1, plan_type2, plan_level's per_run rule, make_tile_geom) take the
+window of a case from the library's own host functions, so
 tests/test_nudft_reference_host.py::test_geometry_of_the_cases can assert on a machine without a GPU that every case lands on the
 route it is named for.  LDS per workgroup is 160 KB and the chip has 256 compute units, as on the MI355X.
+
+The library's own planner (csrc/nufft_plan_host.cpp) is held to these functions field by field in tests/test_nufft_plan_host.py,
+which hands LDS_BYTES and NUM_CU to the planner's check program.
 """
 import math
 
@@ -57,17 +60,30 @@ def tile_geom(nf, W, channels, force_tile=0):
     return nt, T
 
 
-def band_level(nf, N, span_periods, forced):
-    """pick_level's band count for a forced band height, or None: bands of at most `forced` fine cells along axis 1, at least one
-    point per run (unforced: 192 for one-cell bands, 24 for eight-cell ones).  span_periods: extent of the points per axis in periods."""
+def band_rule(nf, N, span_periods, forced=0):
+    """plan_level's (band count, band height) or None: bands of at most 1 or 8 fine cells along axis 1, the first height with enough
+    points per run -- 192 for one-cell bands, 24 for eight-cell ones; a forced height (1 | 8) from one point per run on.
+    span_periods: extent of the points per axis in periods.  (A level the model already holds is not known here.)"""
     span = [s * n for s, n in zip(span_periods, nf)]
-    n = 1
-    while span[1] / n > forced - 1e-6 and n <= MAX_BANDS:
-        n *= 2
-    if n > MAX_BANDS:
-        return None
-    per_run = N / (n * max(1.0, span[0]))
-    return n if per_run >= 1.0 else None
+    for hb in (1, 8):
+        if forced and forced != hb:
+            continue
+        n = 1
+        while span[1] / n > hb - 1e-6 and n <= MAX_BANDS:
+            n *= 2
+        if n > MAX_BANDS:
+            continue
+        per_run = N / (n * max(1.0, span[0]))
+        if per_run < (1.0 if forced else 192.0 if hb == 1 else 24.0):
+            continue
+        return n, hb
+    return None
+
+
+def band_level(nf, N, span_periods, forced):
+    """band_rule's band count for a forced band height (0: the unforced rule), or None."""
+    rule = band_rule(nf, N, span_periods, forced)
+    return rule[0] if rule else None
 
 
 def _after_spread(nm, nf, has_acc, env):
@@ -81,32 +97,50 @@ def _after_spread(nm, nf, has_acc, env):
     return "fft"
 
 
-def type1_route(nm, tol, N, channels, dense=False, layout_band=0, span_periods=None, env=()):
-    """(spreader, what follows it) of one type-1 pass: spread_and_fft and spread_lds_or_global.  nm: the (larger) requested box."""
+def type1_route(nm, tol, N, channels, dense=False, layout_band=0, span_periods=None, env=(), normal=False):
+    """(spreader, what follows it) of one type-1 pass: plan_type1.  nm: the (larger) requested box; layout_band: 0 no point layout,
+    1 | 8 a layout with that band height forced, -1 a layout and the unforced rule; normal: generated normal strengths."""
     nf, W = window(nm, tol, dense)
     d = len(nm)
     cells = math.prod(nf)
     lds_bytes = channels * cells * 8
     use_lds = lds_bytes <= LDS_BYTES and N > 0
-    if layout_band and d == 2 and W <= MFMA_MAX_W and N >= 32768 and band_level(nf, N, span_periods, layout_band):
+    if (layout_band and d == 2 and W <= MFMA_MAX_W and N >= 32768 and "EFGP_NO_MFMA_SPREAD" not in env
+            and band_level(nf, N, span_periods, max(layout_band, 0))):
         return "layout", _after_spread(nm, nf, True, env)
-    if "EFGP_CELLSORT" in env and d == 2 and W <= CELL_MAX_W and cells <= 16384 and tile_geom(nf, W, channels, 1):
+    if ("EFGP_CELLSORT" in env and not normal and d == 2 and W <= CELL_MAX_W and cells <= 16384 and N > 0
+            and tile_geom(nf, W, channels, 1)):
         return "cells", _after_spread(nm, nf, False, env)           # (the library also wants degree <= W + 4: not visible from here)
-    if not use_lds and N >= 32768 and tile_geom(nf, W, channels):
+    if not use_lds and N >= 32768 and "EFGP_NO_TILES" not in env and tile_geom(nf, W, channels):
         return "tiles", _after_spread(nm, nf, True, env)
     if not use_lds:
         return "global", _after_spread(nm, nf, False, env)
+    use_pad, raw48 = _lds_slabs(nf, W, tol, N, channels, env, normal)[:2]
+    return ("lds_pad_raw48" if raw48 else "lds_pad_61" if use_pad else "lds_plain"), _after_spread(nm, nf, False, env)
+
+
+def _lds_slabs(nf, W, tol, N, channels, env, normal):
+    """plan_lds_or_global for a grid inside LDS: (padded rows, 48-bit raw sums, workgroups, points per workgroup)."""
+    cells = math.prod(nf)
+    lds_bytes = channels * cells * 8
     per_cu = max(1, min(2, LDS_BYTES // max(lds_bytes, 1)))
     nwg = max(1, min(NUM_CU * per_cu, (N + 1023) // 1024))
     per = (N + nwg - 1) // nwg
     pad_bytes = channels * (cells // nf[-1]) * (nf[-1] + W - 1) * 8
     use_pad = pad_bytes + 4608 <= LDS_BYTES and "EFGP_NO_PAD" not in env
-    raw48 = use_pad and per * 2.0 ** -47 <= 0.01 * tol
-    return ("lds_pad_raw48" if raw48 else "lds_pad_61" if use_pad else "lds_plain"), _after_spread(nm, nf, False, env)
+    raw48 = use_pad and per * 2.0 ** -47 <= 0.01 * tol and "EFGP_NO_RAW48" not in env and not normal
+    return use_pad, raw48, nwg, per
+
+
+def class_order_wanted(route, d, N, env=()):
+    """The plan's bank-balanced processing order: kOrderWindow * 64 points or more, d >= 2, on the padded-row spreaders (type 1)
+    or the halo gather that is not the pair gather (type 2).  route: a spreader of type1_route or a gather of type2_route."""
+    return (route in ("lds_pad_raw48", "lds_pad_61", "halo") and d >= 2 and N >= ORDER_WINDOW * 64
+            and "EFGP_NO_CLASS_ORDER" not in env)
 
 
 def type2_route(nm, tol, N, B, real_only, dense=False, env=()):
-    """(how the fine grid is made, which gather reads it): pick_gather, modes_to_fine and gather."""
+    """(how the fine grid is made, which gather reads it): plan_type2."""
     nf, W = window(nm, tol, dense)
     d = len(nm)
     cells = math.prod(nf)
@@ -125,7 +159,7 @@ def type2_route(nm, tol, N, B, real_only, dense=False, env=()):
     grid = ("image" if use_image else "direct" if direct else
             "pruned" if smaller and _own_fft_supported(nf) and "EFGP_NO_PRUNED_FFT" not in env else "fft")
     use_lds = lds_bytes <= LDS_BYTES
-    if not use_lds and N >= 32768 and tile_geom(nf, W, 1 if real_only else 2):
+    if not use_lds and N >= 32768 and "EFGP_NO_TILES" not in env and tile_geom(nf, W, 1 if real_only else 2):
         return grid, "tiles"
     return grid, ("pair" if use_pair else "halo" if use_halo else "lds" if use_lds else "l2")
 
