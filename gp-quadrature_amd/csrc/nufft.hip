@@ -1531,6 +1531,7 @@ __global__ __launch_bounds__(kG2MThreads) void grid_to_modes_kernel(G2MArgs a) {
 // (kG2RRows: nufft_plan_host.hpp)
 constexpr int kG2RThreads = 1024;
 constexpr int kR2MThreads = 256;
+constexpr int kR2MThreadsWide = 512;         // rows_modes_kernel<false>: 8 (2 h0 + 1) tasks in one pass up to 63 modes
 
 struct G2RArgs {
     long long* gacc;          // [nbatch][channels][nf0 * nf1]   (null: `fine`)
@@ -1544,7 +1545,60 @@ struct G2RArgs {
     double2* cbuf;            // [nbatch][nf0][2 h1 + 1]
 };
 
-template <bool FINE>
+// The multiply-add chains of the two kernels, written once for both of their arms (below): one term of the four real sums
+// of a row transform, one term of a complex column sum.
+__device__ __forceinline__ void g2r_acc(double& P, double& Q, double& R, double& S, const double2 g, const double2 tw) {
+    P = fma(g.x, tw.x, P);
+    Q = fma(g.x, tw.y, Q);
+    R = fma(g.y, tw.x, R);
+    S = fma(g.y, tw.y, S);
+}
+__device__ __forceinline__ void r2m_acc(double& sx, double& sy, const double2 cv, const double2 tw) {
+    sx = fma(cv.x, tw.x, fma(-cv.y, tw.y, sx));
+    sy = fma(cv.x, tw.y, fma(cv.y, tw.x, sy));
+}
+// kDftGroup terms of such a chain from x on (n <= kDftGroup of them live): every LDS operand is read before the first
+// multiply-add, the table indices come from integer additions up front, the multiply-adds run in the order of the plain loop.
+// Reads past the n-th term repeat it and are not used.
+// SKEW: both arrays are stored with one element of padding behind every sixteen (dft_skew).  A ds_read_b128 serves sixteen
+// lanes per LDS cycle, each from one of sixteen 16-byte slots; in grid_rows_kernel the eight segments of a row start a multiple
+// of sixteen elements apart (nf1 = 128) and the table indices k (16 s + j) of lanes that differ in the segment s only are a
+// multiple of sixteen apart as well, so the lanes of a group fall on ONE slot at up to eight addresses: eight cycles instead of
+// one, on every read.  The padding moves them to different slots (measured: 7.6 -> 5.0 us for the kernel; the batching alone
+// gave 0.2).  rows_modes_kernel reads one value per column (a broadcast) and its table at consecutive strides: no padding.
+constexpr int kDftGroup = 8;
+__host__ __device__ __forceinline__ constexpr int dft_skew(int i) { return i + (i >> 4); }
+constexpr int kDftSkewTable = dft_skew(256);             // a skewed table of 256 twiddles
+template <bool FULL, bool SKEW, typename Acc>
+__device__ __forceinline__ void dft_group(const double2* __restrict__ v, const double2* __restrict__ T, int x, int n, int& idx,
+                                          int step, int nf, Acc acc) {
+    double2 g[kDftGroup], tw[kDftGroup];
+#pragma unroll
+    for (int j = 0; j < kDftGroup; ++j) {
+        const int xx = x + (FULL ? j : min(j, n - 1));
+        g[j] = v[SKEW ? dft_skew(xx) : xx];
+        tw[j] = T[SKEW ? dft_skew(idx) : idx];
+        idx += step;
+        if (idx >= nf) idx -= nf;
+    }
+    __builtin_amdgcn_sched_barrier(0);                  // (the scheduler would hold six of the reads back among the multiply-adds)
+#pragma unroll
+    for (int j = 0; j < kDftGroup; ++j)
+        if (FULL || j == 0 || j < n) acc(g[j], tw[j]);                 // n >= 1
+}
+
+// SERIAL = false (default) keeps every sum's partition and term order and takes dependent round trips out: the accumulator
+// loads (from memory: device-scope atomics wrote the data) and their zero stores are issued first and the twiddle table is
+// computed in their shadow, by other waves where the rows leave half of the workgroup free; the contraction reads its LDS
+// operands kDftGroup terms ahead, from rows and a table padded against bank conflicts (dft_skew; the LDS grows by 17 + nf1 / 4
+// elements).  SERIAL = true (EFGP_SMALL_DFT_SERIAL) is the first version's statement order and layout; same bits.
+static_assert(kG2RRows * kG2MMaxNf <= kG2RThreads, "one accumulator cell per thread");
+__host__ __device__ __forceinline__ constexpr int g2r_row_pitch(int nf1) { return dft_skew(nf1) + 1; }    // skewed rows, staggered
+static size_t g2r_lds_bytes(int nf1, bool serial) {
+    return serial ? (256 + (size_t)kG2RRows * nf1) * sizeof(double2)
+                  : ((size_t)kDftSkewTable + (size_t)kG2RRows * g2r_row_pitch(nf1)) * sizeof(double2);
+}
+template <bool FINE, bool SERIAL>
 __global__ __launch_bounds__(kG2RThreads) void grid_rows_kernel(G2RArgs a) {
     extern __shared__ double2 g2r_lds[];
     const int tid = threadIdx.x, b = blockIdx.y;
@@ -1552,14 +1606,43 @@ __global__ __launch_bounds__(kG2RThreads) void grid_rows_kernel(G2RArgs a) {
     const int nk1 = 2 * h1 + 1;
     const int64_t cells = (int64_t)nf0 * nf1;
     double2* const T = g2r_lds;                         // w1^q, q < nf1 <= 256
-    double2* const Row = T + 256;                       // [kG2RRows][nf1] (re, im) of the owned rows
-    for (int q = tid; q < nf1; q += kG2RThreads) {
-        double sn, cs;
-        sincospi((double)a.sign * 2.0 * (double)q / (double)nf1, &sn, &cs);
-        T[q] = make_double2(cs, sn);
-    }
+    double2* const Row = T + (SERIAL ? 256 : kDftSkewTable);   // [kG2RRows][nf1] (re, im) of the owned rows; !SERIAL: both skewed
+    const int row_pitch = SERIAL ? nf1 : g2r_row_pitch(nf1);
     const int x0_lo = (int)blockIdx.x * kG2RRows;
-    {
+    if constexpr (!SERIAL) {
+        const double s0 = FINE ? 1.0 : a.scale[1], s1 = FINE ? 1.0 : a.scale[3];
+        const int o = tid;
+        const int r = o / nf1, x1 = o - r * nf1, x0 = x0_lo + r;
+        const bool cell = o < kG2RRows * nf1, live = cell && x0 < nf0;
+        double2 v = make_double2(0.0, 0.0);
+        long long ire = 0, iim = 0;
+        if (live) {
+            if (FINE) {
+                v = a.fine[(int64_t)b * cells + (int64_t)x0 * nf1 + x1];
+            } else {
+                long long* g = a.gacc + (int64_t)b * a.channels * cells + (int64_t)x0 * nf1 + x1;
+                ire = g[0];
+                if (a.channels == 2) iim = g[cells];
+                g[0] = 0;                                           // the next pass finds a zeroed accumulator
+                if (a.channels == 2) g[cells] = 0;
+            }
+        }
+        const int q = kG2RRows * nf1 <= kG2RThreads / 2 ? tid - kG2RThreads / 2 : tid;     // the table on the waves without a cell
+        if (q >= 0 && q < nf1) {
+            double sn, cs;
+            sincospi((double)a.sign * 2.0 * (double)q / (double)nf1, &sn, &cs);
+            T[dft_skew(q)] = make_double2(cs, sn);
+        }
+        if (FINE) asm volatile("" : "+v"(v.x), "+v"(v.y));           // the loads are waited for here, behind the table, not above it
+        else asm volatile("" : "+v"(ire), "+v"(iim));
+        if (!FINE && live) v = make_double2((double)ire * s0, (double)iim * s1);
+        if (cell) Row[r * row_pitch + dft_skew(x1)] = v;
+    } else {
+        for (int q = tid; q < nf1; q += kG2RThreads) {
+            double sn, cs;
+            sincospi((double)a.sign * 2.0 * (double)q / (double)nf1, &sn, &cs);
+            T[q] = make_double2(cs, sn);
+        }
         const double s0 = FINE ? 1.0 : a.scale[1], s1 = FINE ? 1.0 : a.scale[3];
         for (int o = tid; o < kG2RRows * nf1; o += kG2RThreads) {
             const int r = o / nf1, x1 = o - r * nf1, x0 = x0_lo + r;
@@ -1594,15 +1677,19 @@ __global__ __launch_bounds__(kG2RThreads) void grid_rows_kernel(G2RArgs a) {
         int idx = (int)(((long long)k1 * xa) % nf1);
         double P = 0.0, Q = 0.0, R = 0.0, S = 0.0;
         if (on) {
-            const double2* row = Row + r * nf1;
-            for (int x = xa; x < xe; ++x) {
-                const double2 g = row[x], tw = T[idx];
-                P = fma(g.x, tw.x, P);
-                Q = fma(g.x, tw.y, Q);
-                R = fma(g.y, tw.x, R);
-                S = fma(g.y, tw.y, S);
-                idx += k1;
-                if (idx >= nf1) idx -= nf1;
+            const double2* row = Row + r * row_pitch;
+            if constexpr (SERIAL) {
+                for (int x = xa; x < xe; ++x) {
+                    const double2 g = row[x], tw = T[idx];
+                    g2r_acc(P, Q, R, S, g, tw);
+                    idx += k1;
+                    if (idx >= nf1) idx -= nf1;
+                }
+            } else {
+                const auto acc = [&](const double2 g, const double2 tw) { g2r_acc(P, Q, R, S, g, tw); };
+                int x = xa;
+                for (; x + kDftGroup <= xe; x += kDftGroup) dft_group<true, true>(row, T, x, kDftGroup, idx, k1, nf1, acc);
+                if (x < xe) dft_group<false, true>(row, T, x, xe - x, idx, k1, nf1, acc);
             }
         }
 #pragma unroll
@@ -1621,24 +1708,49 @@ __global__ __launch_bounds__(kG2RThreads) void grid_rows_kernel(G2RArgs a) {
     }
 }
 
-__global__ __launch_bounds__(kR2MThreads) void rows_modes_kernel(G2RArgs a) {
-    __shared__ double2 T[256], Cc[2][256], Hs[2][2 * kG2MMaxH + 2], part[2][4][2 * kG2MMaxH + 2];
+// The four quarter sums of one mode, combined.
+__device__ __forceinline__ double2 r2m_quarters(const double2 (*p)[2 * kG2MMaxH + 2], int r) {
+    return make_double2((p[0][r].x + p[1][r].x) + (p[2][r].x + p[3][r].x), (p[0][r].y + p[1][r].y) + (p[2][r].y + p[3][r].y));
+}
+
+// SERIAL = false (default, kR2MThreadsWide threads): the 8 nk0 tasks of a box of up to 63 modes make one pass, the LDS
+// operands are read kDftGroup terms ahead, and the epilogue thread adds the quarter sums of its mode and of the partner itself
+// (one barrier behind the products instead of three).  SERIAL = true (EFGP_SMALL_DFT_SERIAL, kR2MThreads threads) is the first
+// version's statement order.  Same partition, same term order, same bits.
+static_assert(2 * kG2MMaxNf <= kR2MThreadsWide, "one value of C per thread");
+template <bool SERIAL>
+__global__ __launch_bounds__(SERIAL ? kR2MThreads : kR2MThreadsWide) void rows_modes_kernel(G2RArgs a) {
+    constexpr int NT = SERIAL ? kR2MThreads : kR2MThreadsWide;
+    __shared__ double2 T[256], Cc[2][256], part[2][4][2 * kG2MMaxH + 2];
     const int tid = threadIdx.x, b = blockIdx.y, k1 = (int)blockIdx.x;             // column pair +-k1, k1 = 0..h1
     const int nf0 = a.nf0, h0 = a.h0, h1 = a.h1;
     const int nk0 = 2 * h0 + 1, nk1 = 2 * h1 + 1;
     const double2* C = a.cbuf + (int64_t)b * nf0 * nk1;
-    for (int o = tid; o < 2 * nf0; o += kR2MThreads) {                           // every load issued before any is used
-        const int col = o >= nf0 ? 1 : 0, x0 = o - col * nf0;
-        Cc[col][x0] = C[(int64_t)x0 * nk1 + (col ? h1 - k1 : h1 + k1)];
-    }
-    for (int q = tid; q < nf0; q += kR2MThreads) {
-        double sn, cs;
-        sincospi((double)a.sign * 2.0 * (double)q / (double)nf0, &sn, &cs);
-        T[q] = make_double2(cs, sn);
+    if constexpr (SERIAL) {
+        for (int o = tid; o < 2 * nf0; o += NT) {                                // every load issued before any is used
+            const int col = o >= nf0 ? 1 : 0, x0 = o - col * nf0;
+            Cc[col][x0] = C[(int64_t)x0 * nk1 + (col ? h1 - k1 : h1 + k1)];
+        }
+        for (int q = tid; q < nf0; q += NT) {
+            double sn, cs;
+            sincospi((double)a.sign * 2.0 * (double)q / (double)nf0, &sn, &cs);
+            T[q] = make_double2(cs, sn);
+        }
+    } else {                                                                      // the load stays in a register across the table
+        const int col = tid >= nf0 ? 1 : 0, x0 = tid - col * nf0;
+        const bool ld = tid < 2 * nf0;
+        double2 cv = make_double2(0.0, 0.0);
+        if (ld) cv = C[(int64_t)x0 * nk1 + (col ? h1 - k1 : h1 + k1)];
+        if (tid < nf0) {
+            double sn, cs;
+            sincospi((double)a.sign * 2.0 * (double)tid / (double)nf0, &sn, &cs);
+            T[tid] = make_double2(cs, sn);
+        }
+        if (ld) Cc[col][x0] = cv;
     }
     __syncthreads();
     // H[k0][col] = sum_x0 Cc[col][x0] w0^(k0 x0): task = (col, k0, quarter of x0)
-    for (int o = tid; o < 8 * nk0; o += kR2MThreads) {
+    for (int o = tid; o < 8 * nk0; o += NT) {
         const int qtr = o / (2 * nk0), rc = o - qtr * 2 * nk0;
         const int col = rc / nk0, r = rc - col * nk0;
         int st = (r - h0) % nf0;
@@ -1646,28 +1758,38 @@ __global__ __launch_bounds__(kR2MThreads) void rows_modes_kernel(G2RArgs a) {
         const int xa = (nf0 * qtr) / 4, xe = (nf0 * (qtr + 1)) / 4;
         int idx = (int)(((long long)st * xa) % nf0);
         double sx = 0.0, sy = 0.0;
-        for (int x = xa; x < xe; ++x) {
-            const double2 cv = Cc[col][x], tw = T[idx];
-            sx = fma(cv.x, tw.x, fma(-cv.y, tw.y, sx));
-            sy = fma(cv.x, tw.y, fma(cv.y, tw.x, sy));
-            idx += st;
-            if (idx >= nf0) idx -= nf0;
+        if constexpr (SERIAL) {
+            for (int x = xa; x < xe; ++x) {
+                const double2 cv = Cc[col][x], tw = T[idx];
+                r2m_acc(sx, sy, cv, tw);
+                idx += st;
+                if (idx >= nf0) idx -= nf0;
+            }
+        } else {
+            const auto acc = [&](const double2 cv, const double2 tw) { r2m_acc(sx, sy, cv, tw); };
+            int x = xa;
+            for (; x + kDftGroup <= xe; x += kDftGroup) dft_group<true, false>(Cc[col], T, x, kDftGroup, idx, st, nf0, acc);
+            if (x < xe) dft_group<false, false>(Cc[col], T, x, xe - x, idx, st, nf0, acc);
         }
         part[col][qtr][r] = make_double2(sx, sy);
     }
     __syncthreads();
-    for (int o = tid; o < 2 * nk0; o += kR2MThreads) {
-        const int col = o / nk0, r = o - col * nk0;
-        Hs[col][r] = make_double2((part[col][0][r].x + part[col][1][r].x) + (part[col][2][r].x + part[col][3][r].x),
-                                  (part[col][0][r].y + part[col][1][r].y) + (part[col][2][r].y + part[col][3][r].y));
+    __shared__ double2 Hs[2][2 * kG2MMaxH + 2];                                  // SERIAL only
+    if constexpr (SERIAL) {
+        for (int o = tid; o < 2 * nk0; o += NT) {
+            const int col = o / nk0, r = o - col * nk0;
+            Hs[col][r] = r2m_quarters(part[col], r);
+        }
+        __syncthreads();
     }
-    __syncthreads();
     // epilogue (as grid_to_modes_kernel): mode (k0, +-k1) with its partner (-k0, -+k1) in the other column
-    for (int o = tid; o < 2 * nk0; o += kR2MThreads) {
+    for (int o = tid; o < 2 * nk0; o += NT) {
         const int col = o / nk0, r = o - col * nk0;
         if (col == 1 && k1 == 0) continue;                                       // -0 duplicates +0
         const int k0 = r - h0, kk1 = col ? -k1 : k1;
-        const double2 H = Hs[col][r], G = Hs[k1 == 0 ? 0 : 1 - col][nk0 - 1 - r];
+        const int gcol = k1 == 0 ? 0 : 1 - col, gr = nk0 - 1 - r;
+        const double2 H = SERIAL ? Hs[col][r] : r2m_quarters(part[col], r);
+        const double2 G = SERIAL ? Hs[gcol][gr] : r2m_quarters(part[gcol], gr);
         int64_t t;
         double f;
         if (a.part == 0) {
@@ -2724,12 +2846,17 @@ static int g2m_launch(DeviceCtx* ctx, const Type1Plan& pl, const GridGeom& g, G2
         ra.cbuf = (double2*)scratch(ctx, SLOT_G2M, (size_t)nbatch * ga.nf0 * nk1 * sizeof(double2));
         if (!ra.cbuf) return EFGP_ENOMEM;
         ctx->g2m_zeroed_for = nullptr;                   // (the one-launch kernel's counters share this slot)
-        const size_t lds = (256 + (size_t)kG2RRows * ga.nf1) * sizeof(double2);
         const dim3 grid((ga.nf0 + kG2RRows - 1) / kG2RRows, nbatch);
-        if (gacc) hipLaunchKernelGGL((grid_rows_kernel<false>), grid, dim3(kG2RThreads), lds, stream, ra);
-        else hipLaunchKernelGGL((grid_rows_kernel<true>), grid, dim3(kG2RThreads), lds, stream, ra);
+        // comparison hook, read per call: the first version's statement order inside the two kernels (same launches, same bits)
+        const bool serial = std::getenv("EFGP_SMALL_DFT_SERIAL") != nullptr;
+        const size_t lds = g2r_lds_bytes(ga.nf1, serial);
+        if (gacc && serial) hipLaunchKernelGGL((grid_rows_kernel<false, true>), grid, dim3(kG2RThreads), lds, stream, ra);
+        else if (gacc) hipLaunchKernelGGL((grid_rows_kernel<false, false>), grid, dim3(kG2RThreads), lds, stream, ra);
+        else if (serial) hipLaunchKernelGGL((grid_rows_kernel<true, true>), grid, dim3(kG2RThreads), lds, stream, ra);
+        else hipLaunchKernelGGL((grid_rows_kernel<true, false>), grid, dim3(kG2RThreads), lds, stream, ra);
         EFGP_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(rows_modes_kernel, dim3(ga.h1 + 1, nbatch), dim3(kR2MThreads), 0, stream, ra);
+        if (serial) hipLaunchKernelGGL(rows_modes_kernel<true>, dim3(ga.h1 + 1, nbatch), dim3(kR2MThreads), 0, stream, ra);
+        else hipLaunchKernelGGL(rows_modes_kernel<false>, dim3(ga.h1 + 1, nbatch), dim3(kR2MThreadsWide), 0, stream, ra);
         EFGP_HIP_CHECK(hipGetLastError());
         req->done = true;
         return EFGP_OK;
