@@ -113,9 +113,29 @@ struct Args {
             stamp_prev = now__;                                              \
         }                                                                    \
     } while (0)
+// the same from thread `who` of block 0, for a phase that thread 0's wave does not carry (cg_herm48_pairs_kernel), and a restart
+// of the thread's clock behind a wait that another thread accounts for
+#define EFGP_STAMP_BY(slot, who)                                             \
+    do {                                                                     \
+        if (blockIdx.x == 0 && threadIdx.x == (who)) {                       \
+            const long long now__ = (long long)__builtin_readcyclecounter(); \
+            a.stamps[slot] += now__ - stamp_prev;                            \
+            stamp_prev = now__;                                              \
+        }                                                                    \
+    } while (0)
+#define EFGP_STAMP_RESTART(who)                                                                                  \
+    do {                                                                                                         \
+        if (blockIdx.x == 0 && threadIdx.x == (who)) stamp_prev = (long long)__builtin_readcyclecounter();       \
+    } while (0)
 #else
 #define EFGP_STAMP(slot) \
     do {                 \
+    } while (0)
+#define EFGP_STAMP_BY(slot, who) \
+    do {                         \
+    } while (0)
+#define EFGP_STAMP_RESTART(who) \
+    do {                        \
     } while (0)
 #endif
 
@@ -1258,6 +1278,8 @@ __global__ __launch_bounds__(h64::kThreadsH) void cg_herm64_kernel(Args a) {
 // Hermitian Toeplitz products over k0 on 192 lanes with their coefficients in registers (dense48_coeffs), row transforms D --
 // two line-transform phases per application instead of four.  The packed column transforms B / C below remain for batches (the
 // resident coefficients cost the second workgroup per CU: 256 + 16 registers) and behind EFGP_CG48_FFT2D=1.
+// Round 9: that single system runs on eight waves, the Toeplitz products on waves of their own from sums and differences of lags at
+// half the multiply-adds (cg_herm48_pairs_kernel below; EFGP_CG48_LAG_COEFFS=1 keeps the 256-thread kernel).
 //
 // A 48-point line lives in 8 adjacent lanes as 48 = 6 x 8, in two mirrored factorizations so that every pruned stage is a
 // radix-8 butterfly with four live legs (dft8_in4 / dft8_out4 of the 64-point kernel) on SIX lanes holding positions j + 6 t,
@@ -1286,6 +1308,12 @@ constexpr int kReread = 8;               // row of the multiply-adds in front of
 constexpr int LDV = 49;                  // pitch of the prologue's 48 x 48 grid (vhat48_lines)
 constexpr int kLdsElemsDense = F * LDV + (kThreadsH / 8) * LX;      // the prologue's grid + 32 line slots: 73 KB
 static_assert(2 * G_ELEMS + NR * LX <= kLdsElemsDense, "the iteration's G, Yh and row scratch alias the prologue's grid");
+// eight waves with paired lags (round 9, cg_herm48_pairs_kernel): waves 0-1 the row role, waves 2..7 the dense role, lane =
+// (f1, group g): groups 0..3 (waves 2-4) own the rows 2 g and 2 g + 1, groups 4..7 (waves 5-7) the row 8 + (g - 4)
+constexpr int kThreadsP = 512, kRowWavesP = 2, kPairWavesP = 3;
+constexpr int NDP = kThreadsP - 64 * kRowWavesP;       // dense lanes: 48 frequencies x 8 groups
+static_assert(NDP == 8 * F && 64 * kPairWavesP == 4 * F, "no wave mixes two-row and one-row groups");
+constexpr int kLdsElemsPairs = F * LDV + (kThreadsP / 8) * LX;      // the prologue's grid + 64 line slots: 111 KB
 
 // forward DFT-6 in natural order: even / odd split into two DFT-3
 __device__ __forceinline__ void dft3(double2 b0, double2 b1, double2 b2, double2& x0, double2& x1, double2& x2) {
@@ -1537,6 +1565,86 @@ __device__ __forceinline__ void dense48_coeffs(double2* lds2, const double2 (&tw
         }
         cf[i] = c;
     }
+}
+
+// The inverse pass of dense48_coeffs and the fetch of one lag for the eight-wave kernel (cg_herm48_pairs_kernel, round 9), which runs
+// the pass on 512 threads (64 line slots, one pass) and makes sums and differences of lags out of the same c(l0, f1): the same
+// statements per line and per lag.  They stand beside dense48_coeffs, not inside it: called from there, the 256-thread kernels no
+// longer compiled to the instructions they had (the schedule moved in five instantiations, profiles/r9_cg48_lag_pairs_ab.txt).
+template <int NT>
+__device__ __forceinline__ void dense48_inverse_pass(double2* lds2, const double2 (&tw)[5]) {
+    constexpr int SLOTS = NT / 8, PASSES = (F + SLOTS - 1) / SLOTS;
+    double2* const buf = lds2;                       // [48][LDV]
+    double2* const scr = lds2 + F * LDV;             // [SLOTS lines][writer 9 j + value]
+    const int tid = threadIdx.x, slot = tid >> 3, j = tid & 7;
+    double2* const wr = scr + slot * LX + 9 * j;
+    const double2* const rd = scr + slot * LX + j;
+    double2 u6[6], x8[8];
+#pragma unroll
+    for (int ps = 0; ps < PASSES; ++ps) {
+        const int line = slot + ps * SLOTS;
+        const bool act = line < F;
+#pragma unroll
+        for (int t = 0; t < 6; ++t) u6[t] = act ? s64::conjd(buf[(j + 8 * t) * LDV + line]) : make_double2(0.0, 0.0);
+        dft6(u6);
+#pragma unroll
+        for (int t = 1; t < 6; ++t) u6[t] = cmulp(u6[t], tw[t - 1]);
+        wave_sync();
+#pragma unroll
+        for (int t = 0; t < 6; ++t) wr[t] = u6[t];
+        wave_sync();
+        s64::load8_all<9>(rd, x8);
+        dft_fwd<8>(x8);
+        if (act && j < 6) {
+#pragma unroll
+            for (int t = 0; t < 8; ++t) buf[(j + 6 * t) * LDV + line] = s64::conjd(x8[t]);
+        }
+    }
+}
+// c(l, f1) out of the grid the inverse pass leaves, wc = w48^((n - 1) f1): negative lags as conjugates of the positive ones, lag 0
+// real, lags beyond the Toeplitz vector zero
+__device__ __forceinline__ double2 lag_coeff(const double2* buf, double2 wc, int n, int f1, int l) {
+    const int al = l < 0 ? -l : l;
+    double2 c = make_double2(0.0, 0.0);
+    if (al <= n - 1) {
+        const double2 r = buf[(al + n - 1) * LDV + f1];
+        c = make_double2(fma(r.y, wc.y, r.x * wc.x), fma(-r.x, wc.y, r.y * wc.x));       // r conj(wc)
+        if (l < 0) c.y = -c.y;
+        if (l == 0) c.y = 0.0;
+    }
+    return c;
+}
+
+// Paired lags (round 9).  With G[m] = a + i b the two terms of an input row m >= 1,
+//     c(k0 - m) G[m] + c(k0 + m) conj G[m] = S a + i Q b,      S(k0, m) = c(k0 - m) + c(k0 + m),  Q(k0, m) = c(k0 - m) - c(k0 + m),
+// cost four multiply-adds instead of eight: Re += S.x a - Q.y b, Im += S.y a + Q.x b.  S and Q belong to one output row (they are
+// not Toeplitz-shared between the rows of a lane): c(k0), eleven S and eleven Q are 46 doubles per output, rounded once here.
+constexpr int NM = NR - 1;               // input rows m = 1..11
+struct PairCoeffs {
+    double2 c0;                          // c(k0): the m = 0 term, c(k0) Re G[0]
+    double2 S[NM], Q[NM];
+};
+__device__ __forceinline__ void pair_coeffs(const double2* buf, double2 wc, int n, int f1, int k0, PairCoeffs& pc) {
+    pc.c0 = lag_coeff(buf, wc, n, f1, k0);
+#pragma unroll
+    for (int m = 1; m < NR; ++m) {
+        const double2 cm = lag_coeff(buf, wc, n, f1, k0 - m), cp = lag_coeff(buf, wc, n, f1, k0 + m);
+        pc.S[m - 1] = cadd(cm, cp);
+        pc.Q[m - 1] = csub(cm, cp);
+    }
+}
+// Yh[k0] of one frequency from the twelve rows gm[m] = G[m]: two statements for m = 0 (the imaginary part of G[0] is dropped, as in
+// cg_herm48_kernel), four multiply-adds per m >= 1
+__device__ __forceinline__ double2 pair_product(const PairCoeffs& pc, const double2 (&gm)[NR]) {
+    double2 acc = make_double2(pc.c0.x * gm[0].x, pc.c0.y * gm[0].x);
+#pragma unroll
+    for (int m = 1; m < NR; ++m) {
+        acc.x = fma(pc.S[m - 1].x, gm[m].x, acc.x);
+        acc.y = fma(pc.S[m - 1].y, gm[m].x, acc.y);
+        acc.x = fma(-pc.Q[m - 1].y, gm[m].y, acc.x);
+        acc.y = fma(pc.Q[m - 1].x, gm[m].y, acc.y);
+    }
+    return acc;
 }
 }  // namespace h48
 
@@ -1939,6 +2047,356 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
                 s_rcp = 1.0 / (rzn + 1e-16);
             }
         }
+        // cg.py:132 / 229: the test sits before (single) or after (batched) this update; p is not an output
+        const double beta = div_rcp(rzn, rz + 1e-16, rcp_rz);
+#pragma unroll
+        for (int s = 0; s < KS; ++s) pv[s] = make_double2(zv[s].x + beta * pv[s].x, zv[s].y + beta * pv[s].y);
+        rz = rzn;
+    }
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        if (ok[s]) {
+            a.x[base + idx[s]] = xv[s];
+            if (k0 > 0) a.x[base + (M - 1 - idx[s])] = s64::conjd(xv[s]);     // mode -k
+        }
+    }
+    if (tid == 0) a.iters[row] = it;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Round 9: the single-system dense solve on EIGHT waves with paired lags (the default; EFGP_CG48_LAG_COEFFS=1 selects
+// cg_herm48_kernel<.., true, true> above).  The iteration is that kernel's FREQ_DOT iteration -- A, barrier, per-frequency Toeplitz
+// products, barrier, D and the updates, barrier -- with the products on waves of their own: 384 lanes (waves 2..7) instead of 192,
+// four multiply-adds per (output row, input row) instead of eight (h48::pair_product).  Each role runs its own loop, selected per
+// wave, so that a wave keeps only its role's state in registers: the row waves the CG vectors, the dense waves 46 doubles of
+// coefficients per output row.  Every role executes the same workgroup barriers in the same order -- one behind the coefficients, two
+// per operator application, one behind the sums in front of the loop, three per iteration -- and reads s_stop behind the same one.
+//
+// Dense role, NOUT output rows per lane (2: waves 2-4, rows kd = 2 g, 2 g + 1; 1: waves 5-7, row kd = g + 4).  The last wave is the
+// one with the least to do: it also takes the norm test and the reciprocal for the next beta (the duties of cg_herm48_kernel's idle
+// wave 3).
+template <int NOUT>
+__device__ __forceinline__ void pairs_dense_role(const Args& a, double2* lds2, double* red, double* s_part, double* s_rcp, int* s_stop) {
+    using namespace h48;
+    using h64::div_rcp;
+    const double2* const Gb = lds2;
+    double2* const Tb = lds2 + G_ELEMS;
+    const int n = a.g.n[0];
+    const int tid = threadIdx.x, lane = tid & 63, d = tid - 64 * kRowWavesP;
+    const int f1d = d % F, grp = d / F, kd = NOUT == 2 ? 2 * grp : grp + 4;
+    const bool duty = tid >= kThreadsP - 64;
+    PairCoeffs pc[NOUT];
+    {
+        const double2 wc = a.g.tw[0][((n - 1) * f1d) % F];
+#pragma unroll
+        for (int o = 0; o < NOUT; ++o) pair_coeffs(lds2, wc, n, f1d, kd + o, pc[o]);
+    }
+    __syncthreads();                                      // the iteration's G / Yh / scratch alias the prologue's grid
+#ifdef EFGP_CG_STAMPS
+    long long stamp_prev = 0;
+#endif
+    const double2* const g0 = Gb + f1d;
+    double2* const t0 = Tb + kd * LDR + f1d;
+    // one operator application, as the dense lanes see it; false: the stopping decision of the last iteration was "stop"
+    auto products = [&]() __attribute__((always_inline)) -> bool {
+        __syncthreads();                                  // barrier 1: G and the row lanes' shares of <u,u> are written
+        if (*s_stop) return false;
+        EFGP_STAMP_RESTART(64 * kRowWavesP);
+        double2 gm[NR], acc[NOUT], gk[NOUT];
+#pragma unroll
+        for (int m = 0; m < NR; ++m) gm[m] = g0[m * LDR];
+#pragma unroll
+        for (int o = 0; o < NOUT; ++o) acc[o] = pair_product(pc[o], gm);
+        // G of the lane's own rows once more (kd differs between the lanes of a wave: gm[kd + o] is no register)
+#pragma unroll
+        for (int o = 0; o < NOUT; ++o) gk[o] = g0[(kd + o) * LDR];
+        t0[0] = make_double2(acc[0].x, kd == 0 ? 0.0 : -acc[0].y);       // conj Yh: D transforms conjugated inputs
+        if constexpr (NOUT == 2) t0[LDR] = make_double2(acc[1].x, -acc[1].y);
+        EFGP_STAMP_BY(1, 64 * kRowWavesP);
+        // Re(conj G Yh): row 0 once and from the real parts only, the others twice (rows beyond h have G = 0)
+        const double t0r = kd == 0 ? gk[0].x * acc[0].x : 2.0 * fma(gk[0].y, acc[0].y, gk[0].x * acc[0].x);
+        if constexpr (NOUT == 2) s_part[d] = fma(2.0, fma(gk[1].y, acc[1].y, gk[1].x * acc[1].x), t0r);
+        else s_part[d] = t0r;
+        __syncthreads();                                  // barrier 2: Yh and the summands of <u, A u> are written
+        EFGP_STAMP_BY(6, 64 * kRowWavesP);
+        return true;
+    };
+    if (!a.zero_x0) products();
+    __syncthreads();                                      // the row waves' sums in front of the loop
+    const double rz = red[0] + red[4], bb = red[1] + red[5], asym = red[2] + red[6], ws_bad = red[3] + red[7];
+    if (!(asym <= 1e-16 * bb) || ws_bad != 0.0) return;   // refused (the row lanes write the NaNs and the -2)
+    const double bn = sqrt(bb);
+    const double den = bn > 0.0 ? bn : 1.0;
+    const double den_eps = den + 1e-16, rcp_den = 1.0 / den_eps;
+    if (duty && lane == 0) *s_rcp = 1.0 / (rz + 1e-16);
+    for (int it = 0; it < a.max_iter;) {
+        if (!products()) break;
+        __syncthreads();                                  // barrier 3: the row waves' sums of <r,r> and <r,z>
+        ++it;
+        if (duty) {
+            const double rr = red[0] + red[1], rzn = red[2] + red[3];
+            const double ratio = div_rcp(sqrt(rr), den_eps, rcp_den);
+            const bool conv = a.early_stop && ((ratio < a.tol) || (a.batched && sqrt(rr) < 1e-12));
+            if (lane == 0) {
+                if (a.hist && blockIdx.x == 0 && it <= a.hist_cap) a.hist[it - 1] = ratio;
+                *s_stop = conv ? 1 : 0;
+                *s_rcp = 1.0 / (rzn + 1e-16);
+            }
+        }
+    }
+}
+
+// Register budget: 512 threads are two waves per SIMD, which an allocation of up to 256 VGPR + AGPR still admits on gfx950
+// (__launch_bounds__(512) is that limit).  The two-row dense lanes are the tight role: 184 registers of coefficients, 48 of G, 8 of
+// accumulators; no role may spill (scratch 0 -- profiles/r9_cg48_lag_pairs_ab.txt records the compiler's figures).
+template <int VARIANT, bool FUSED = false>
+__global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a) {
+    using namespace h48;
+    using h64::dft8_in4;
+    using h64::div_rcp;
+    constexpr int KS = 4;
+    extern __shared__ double2 lds2[];
+    // the row waves' wave sums: [4 wave + i] in front of the loop (<r,z>, <b,b>, the two refusal sums), [wave] and [2 + wave] in the
+    // iteration (<r,r>, <r,z>).  The other waves hold no modes; adding their zeros would keep the bits, so they are not added.
+    __shared__ double red[4 * kRowWavesP];
+    __shared__ double s_rcp;             // 1 / (<r,z> + 1e-16) for the next beta, computed by the last wave during A
+    __shared__ int s_stop;               // convergence decision of the last completed iteration, taken by the last wave during A
+    // the lanes' summands of <u, A u>.  [0, NDP): the Toeplitz terms of the dense lanes, written between barriers 1 and 2;
+    // [NDP, NDP + 96): wgt * sigma^2 sum |u|^2 of every row lane, written in A.  Read behind barrier 2 by the row lanes in D.
+    __shared__ double s_part[NDP + 8 * NR];
+    double2* const Gb = lds2;                    // G[k0][f1], k0 = 0..11 (rows beyond h are zero), f1 = 0..47
+    double2* const Tb = lds2 + G_ELEMS;          // conj Yh[k0][f1], pitch LDR
+    double2* const Qb = Tb + G_ELEMS;            // the row lines' exchange scratch
+    const int n = a.g.n[0], h = (n - 1) / 2, M = a.g.M;
+    const int row = blockIdx.x;
+    const int64_t base = (int64_t)row * M;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int k0 = tid >> 3, j = tid & 7;
+
+    double2 twr[5];                      // w48^(lane-in-line * t), t = 1..5 (35 at most: no wrap)
+#pragma unroll
+    for (int t = 1; t < 6; ++t) twr[t - 1] = a.g.tw[0][j * t];
+    if (tid == 0) {
+        s_stop = 0;
+        s_rcp = 0.0;
+    }
+    // the operator's spectrum, made here (one pass per dimension on 64 line slots) or from memory -- the same numbers -- and one
+    // inverse pass along f0: the same statements with and without FUSED
+    if (FUSED) {
+        vhat48_lines<kThreadsP, true>(a.vsrc, a.vL0, a.vL1, 1.0 / 2304.0, a.vhat_out, lds2);
+    } else {
+#pragma unroll
+        for (int k = 0; k < (F * F + kThreadsP - 1) / kThreadsP; ++k) {
+            const int t = tid + k * kThreadsP, i0 = t / F, i1 = t - i0 * F;
+            if (t < F * F) lds2[i0 * LDV + i1] = a.vhat[t];
+        }
+    }
+    __syncthreads();
+    dense48_inverse_pass<kThreadsP>(lds2, twr);
+    __syncthreads();
+    if (wave >= kRowWavesP + kPairWavesP) {
+        pairs_dense_role<1>(a, lds2, red, s_part, &s_rcp, &s_stop);
+        return;
+    }
+    if (wave >= kRowWavesP) {
+        pairs_dense_role<2>(a, lds2, red, s_part, &s_rcp, &s_stop);
+        return;
+    }
+
+    // row role (12 lines x 8 lanes: wave 0 and half of wave 1): lane = k0 * 8 + j, the vector lives in the lanes j < 6.  From here
+    // to the end the statements on these lanes are cg_herm48_kernel's, but for the summands of <u, A u> (more of them) and the
+    // wave sums (two waves)
+    const bool row_role = tid < 8 * NR, vec_role = row_role && j < 6;
+    const int k0s = row_role ? k0 : 0;
+    double2* const xw = Qb + k0s * LX + 9 * j;
+    const double2* const xr = Qb + k0s * LX + j;
+    // vector slots of a row lane j < 6: positions j + 6 t, t in {0, 1, 6, 7} <-> k1 = j, j + 6, j - 12, j - 6
+    double2 xv[KS], rv[KS], pv[KS];
+    double wsr[KS], dg[KS], rdg[KS];     // ws is real here (checked below): ws * u costs two multiplies
+    bool ok[KS];
+    int idx[KS];
+    const bool precond = a.diag != nullptr || a.diag_scale != nullptr;
+    const double wgt = k0 == 0 ? 1.0 : 2.0;
+    double ws_bad = 0.0;                 // > 0: ws is not real and even
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        const int k1 = s == 0 ? j : (s == 1 ? j + 6 : (s == 2 ? j - 12 : j - 6));
+        ok[s] = vec_role && k0 <= h && k1 <= h && -k1 <= h;
+        idx[s] = ok[s] ? (k0 + h) * n + (k1 + h) : 0;
+        double ws_im = 0.0;
+        if (ok[s] && FUSED) {
+            // ws = sqrt(S h^d) is real and even by construction: node idx and its mirror M - 1 - idx get the same value
+            xv[s] = make_double2(0.0, 0.0);
+            const double2 w = make_double2(spectral_weight_at(a.wk_kind, a.g.d, a.wk_nu, a.wk_ell, a.wk_c0, a.wk_h, a.wk_mtot, idx[s]), 0.0);
+            a.ws_out[idx[s]] = w;
+            a.ws_out[M - 1 - idx[s]] = w;
+            wsr[s] = w.x;
+            dg[s] = jacobi_entry(a, w, idx[s]);
+        } else if (ok[s]) {
+            xv[s] = a.zero_x0 ? make_double2(0.0, 0.0) : a.x0[base + idx[s]];
+            const double2 w = a.ws[idx[s]], wm = a.ws[M - 1 - idx[s]];
+            wsr[s] = w.x;
+            ws_im = w.y * w.y + (w.x - wm.x) * (w.x - wm.x) + wm.y * wm.y;
+            dg[s] = jacobi_entry(a, w, idx[s]);
+        } else {
+            xv[s] = make_double2(0.0, 0.0);
+            wsr[s] = 0.0;
+            dg[s] = 1.0;
+        }
+        ws_bad += ws_im;
+        rdg[s] = 1.0 / dg[s];
+        rv[s] = pv[s] = make_double2(0.0, 0.0);
+    }
+    __syncthreads();                                      // the dense lanes have their coefficients: G / Yh / scratch may be written
+
+#ifdef EFGP_CG_STAMPS
+    long long stamp_prev = (long long)__builtin_readcyclecounter();
+#endif
+    int stop = 0;
+    double rcp_rz = 0.0;
+    double rz = 0.0;
+    double alpha_fd = 0.0;               // rz / (<u, A u> + 1e-16) of the last operator application, formed inside D
+    auto apply_A = [&](const double2 (&u)[KS], double2 (&Au)[KS]) __attribute__((always_inline)) {
+        double2 v[8], u6[6];
+        EFGP_STAMP(7);
+        // A ("6x8"): rows k0 >= 0, modes k1 wrapped to positions k1 mod 48 -> G[k0][f1]
+        if (row_role) {
+            dft8_in4(make_double2(wsr[0] * u[0].x, wsr[0] * u[0].y), make_double2(wsr[1] * u[1].x, wsr[1] * u[1].y),
+                     make_double2(wsr[2] * u[2].x, wsr[2] * u[2].y), make_double2(wsr[3] * u[3].x, wsr[3] * u[3].y), v);
+            // u6[k2] = G[k0][j + 8 k2], and the lane's share of the sigma^2 <u,u> of <u, A u> (the slots without a mode hold zeros)
+            const double uu = exchange_8to6_norm(v, u6, j < 6, xw, xr, twr, u, VARIANT == 0 ? wgt * a.sigmasq : wgt);
+            double2* g0 = Gb + k0 * LDR + j;
+#pragma unroll
+            for (int t = 0; t < 6; ++t) g0[8 * t] = u6[t];
+            s_part[NDP + tid] = uu;
+        }
+        __syncthreads();                                  // barrier 1
+        stop = s_stop;
+        rcp_rz = s_rcp;
+        if (stop) return;                                 // uniform: the iteration that just started is abandoned
+        EFGP_STAMP(0);
+        __syncthreads();                                  // barrier 2: the dense waves' products (pairs_dense_role stamps them)
+        EFGP_STAMP_RESTART(0);
+        // D ("8x6"): row k0 >= 0 of the result from Yh[k0]; conjugated inputs, forward transform
+        if (row_role) {
+            // <u, A u> and the step length in the block of D.  The 480 summands: fifteen per lane here, then over the 32 lanes (both
+            // row waves have their lanes 0..31 in this block) and the division inside the exchange.  All twenty-one reads go out
+            // together, the summands first.
+            double pt[15];
+            const double* sp = s_part + (lane & 31);
+#pragma unroll
+            for (int t = 0; t < 15; ++t) pt[t] = sp[32 * t];
+            const double2* tp = Tb + k0 * LDR + j;
+#pragma unroll
+            for (int t = 0; t < 6; ++t) u6[t] = tp[8 * t];
+            __builtin_amdgcn_sched_barrier(0);
+            double tsum = (((pt[0] + pt[1]) + (pt[2] + pt[3])) + ((pt[4] + pt[5]) + (pt[6] + pt[7]))) + ((pt[8] + pt[9]) + (pt[10] + pt[11]));
+            if (VARIANT == 1) tsum /= a.sigmasq;
+            const double uAu = tsum + ((pt[12] + pt[13]) + pt[14]);
+            dft6(u6);
+            // lanes j < 6: v[k2] = conj Y[k0][j + 6 k2], k2 in {0, 1, 6, 7}, and rz / (<u, A u> + 1e-16); a warm start's first
+            // application has rz = 0 and drops the value
+            alpha_fd = exchange_6to8_quot(u6, v, xw, xr, twr, uAu, rz);
+            const double2 y[KS] = {s64::conjd(v[0]), s64::conjd(v[1]), s64::conjd(v[6]), s64::conjd(v[7])};
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                const double2 gg = make_double2(wsr[s] * y[s].x, wsr[s] * y[s].y);
+                double2 val;
+                if (VARIANT == 0) val = make_double2(gg.x + a.sigmasq * u[s].x, gg.y + a.sigmasq * u[s].y);
+                else val = make_double2(gg.x / a.sigmasq + u[s].x, gg.y / a.sigmasq + u[s].y);
+                // the lanes j >= 6 of a line only lend their radix-6 stages: what they read in the radix-8 stage is stale scratch
+                Au[s] = ok[s] ? val : make_double2(0.0, 0.0);
+            }
+        } else {
+            alpha_fd = 0.0;                               // these lanes hold no modes: their vectors are zero and stay zero
+#pragma unroll
+            for (int s = 0; s < KS; ++s) Au[s] = make_double2(0.0, 0.0);
+        }
+        EFGP_STAMP(2);
+    };
+
+    double2 Ap[KS];
+    if (a.zero_x0) {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) Ap[s] = make_double2(0.0, 0.0);
+    } else {
+        apply_A(xv, Ap);
+    }
+    double bb = 0.0, asym = 0.0;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        if (ok[s]) {
+            double2 bv = a.b[base + idx[s]];
+            double2 bm = a.b[base + (M - 1 - idx[s])];                 // mode -k: must be the conjugate
+            if (a.b_times_ws) {
+                bv = make_double2(wsr[s] * bv.x, wsr[s] * bv.y);
+                bm = make_double2(wsr[s] * bm.x, wsr[s] * bm.y);
+            }
+            asym += (bv.x - bm.x) * (bv.x - bm.x) + (bv.y + bm.y) * (bv.y + bm.y);
+            rv[s] = csub(bv, Ap[s]);
+            pv[s] = precond ? make_double2(div_rcp(rv[s].x, dg[s], rdg[s]), div_rcp(rv[s].y, dg[s], rdg[s])) : rv[s];
+            rz += rv[s].x * pv[s].x + rv[s].y * pv[s].y;
+            bb += bv.x * bv.x + bv.y * bv.y;
+        }
+    }
+    rz = wave_sum(rz * wgt);
+    bb = wave_sum(bb * wgt);
+    asym = wave_sum(asym);
+    ws_bad = wave_sum(ws_bad);
+    if (lane == 0) {
+        red[4 * wave] = rz;
+        red[4 * wave + 1] = bb;
+        red[4 * wave + 2] = asym;
+        red[4 * wave + 3] = ws_bad;
+    }
+    __syncthreads();                                      // the sums in front of the loop
+    rz = red[0] + red[4];
+    bb = red[1] + red[5];
+    asym = red[2] + red[6];
+    ws_bad = red[3] + red[7];
+    if (!(asym <= 1e-16 * bb) || ws_bad != 0.0) {
+        // not the coefficients of a real function (rounding leaves ~1e-32 |b|^2): refuse loudly instead of solving another system
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            if (ok[s]) {
+                a.x[base + idx[s]] = make_double2(__builtin_nan(""), __builtin_nan(""));
+                a.x[base + (M - 1 - idx[s])] = make_double2(__builtin_nan(""), __builtin_nan(""));
+            }
+        }
+        if (tid == 0) a.iters[row] = -2;
+        return;
+    }
+    int it = 0;
+    for (; it < a.max_iter;) {
+        apply_A(pv, Ap);
+        if (stop) break;
+        const double alpha = alpha_fd;                    // from D straight into the updates
+        double rr = 0.0, rzn = 0.0;
+        double2 zv[KS];
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            xv[s].x += alpha * pv[s].x;
+            xv[s].y += alpha * pv[s].y;
+            rv[s].x -= alpha * Ap[s].x;
+            rv[s].y -= alpha * Ap[s].y;
+            zv[s] = precond ? make_double2(div_rcp(rv[s].x, dg[s], rdg[s]), div_rcp(rv[s].y, dg[s], rdg[s])) : rv[s];
+            rr += rv[s].x * rv[s].x + rv[s].y * rv[s].y;
+            rzn += rv[s].x * zv[s].x + rv[s].y * zv[s].y;
+        }
+        rr *= wgt;
+        rzn *= wgt;
+        EFGP_STAMP(4);
+        rr = wave_sum(rr);
+        rzn = wave_sum(rzn);
+        if (lane == 0) {
+            red[wave] = rr;
+            red[2 + wave] = rzn;
+        }
+        __syncthreads();                                  // barrier 3
+        rzn = red[2] + red[3];
+        EFGP_STAMP(5);
+        ++it;
         // cg.py:132 / 229: the test sits before (single) or after (batched) this update; p is not an output
         const double beta = div_rcp(rzn, rz + 1e-16, rcp_rz);
 #pragma unroll
@@ -2716,12 +3174,20 @@ static PickLaunch launch_of(const PersistentChoice& c, int variant, const Geom& 
     // EFGP_CG48_MODE_DOT=1 (read per call): the dense 48 x 48 kernels sum <p,Ap> over the modes behind D (the round 6 iteration, four
     // barriers) instead of forming it in the row-frequency domain (round 7, three)
     const bool freq_dot = std::getenv("EFGP_CG48_MODE_DOT") == nullptr;
+    // EFGP_CG48_LAG_COEFFS=1 (read per call): a single dense system runs on the 256-thread kernels with 25 resident lags (rounds 6 / 7)
+    // instead of the eight waves with paired lags (round 9).  EFGP_CG48_MODE_DOT=1 is an iteration of the 256-thread kernels only.
+    const bool pairs = c.dense48 && freq_dot && std::getenv("EFGP_CG48_LAG_COEFFS") == nullptr;
+    constexpr size_t lds48p = (size_t)h48::kLdsElemsPairs * sizeof(double2);
     switch (c.pick) {
         case PersistentPick::fused48: {
+            if (pairs) return {cg_herm48_pairs_kernel<0, true>, h48::kThreadsP, lds48p, "fused mean solve (48x48, eight waves)"};
             void (*const dense[2])(Args) = {cg_herm48_kernel<0, true, true, false>, cg_herm48_kernel<0, true, true, true>};
             return {c.dense48 ? dense[freq_dot] : cg_herm48_kernel<0, true, false>, h48::kThreadsH, lds48d, "fused mean solve (48x48)"};
         }
         case PersistentPick::herm48: {
+            if (pairs)
+                return {variant == 0 ? cg_herm48_pairs_kernel<0> : cg_herm48_pairs_kernel<1>, h48::kThreadsP, lds48p,
+                        "persistent CG (48x48, Hermitian, eight waves)"};
             void (*const dense[2][2])(Args) = {{cg_herm48_kernel<0, false, true, false>, cg_herm48_kernel<1, false, true, false>},
                                                {cg_herm48_kernel<0, false, true, true>, cg_herm48_kernel<1, false, true, true>}};
             void (*const fft2d[2])(Args) = {cg_herm48_kernel<0, false, false>, cg_herm48_kernel<1, false, false>};

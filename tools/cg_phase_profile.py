@@ -46,8 +46,12 @@ if len(sys.argv) > 1 and sys.argv[1] == "herm":
     # cg_herm48_kernel, a single system: per-frequency Toeplitz products between the row transforms.  Default arm (round 7):
     # <p,Ap> in the row-frequency domain, slot 6 in place of slot 3, alpha's division inside D.  EFGP_CG48_MODE_DOT=1: the round 6
     # iteration (slot 3).  EFGP_CG48_FFT2D=1 / cg_herm64_kernel: slot 1 is the packed column transforms B / C.
+    # Round 9 (default): cg_herm48_pairs_kernel, eight waves; slots 1 and 6 are stamped by the first dense lane (thread 128), the
+    # others by thread 0, whose clock restarts behind barrier 2.  EFGP_CG48_LAG_COEFFS=1: the 256-thread kernel of round 7.
     mode_dot = os.environ.get("EFGP_CG48_MODE_DOT") is not None
-    print("arm: " + ("<p,Ap> over the modes behind D (EFGP_CG48_MODE_DOT=1)" if mode_dot else "<p,Ap> in the row-frequency domain"))
+    pairs = not mode_dot and os.environ.get("EFGP_CG48_LAG_COEFFS") is None and os.environ.get("EFGP_CG48_FFT2D") is None
+    print("arm: " + ("<p,Ap> over the modes behind D (EFGP_CG48_MODE_DOT=1)" if mode_dot else "<p,Ap> in the row-frequency domain")
+          + ("; eight waves, paired lags" if pairs else "; 256 threads, 25 resident lags"))
     names = {0: "A: ws*p, row transforms (h+1 lines)" + ("" if mode_dot else ", <p,p> partials"),
              1: "per-frequency Toeplitz products (or B/C)",
              2: "D: row transforms, A u" + ("" if mode_dot else "; alpha = rz / pAp"),
