@@ -1,5 +1,5 @@
 // Spectral density of the built-in kernels at one node of the frequency grid xi = h (-m..m)^d (efgpnd.py:766-780,
-// kernels/*.py).  Shared by spectral_weights_kernel (variance_ops.hip) and the fused mean solve (cg_persistent.hip), so that
+// kernels/*.py).  Shared by spectral_weights_kernel (variance_ops.hip) and the fused mean solve (cg_herm.hip), so that
 // the weights the solve evaluates for itself are bitwise those of the standalone launch.
 #pragma once
 

@@ -615,7 +615,7 @@ __device__ __forceinline__ void wave_sync_lds() {
 // MUL = 4: the same with the two real spectra of every line already in LDS as double2 pairs, `mul`[k * mul_stride + l] (the
 // cooperative Hermitian solve keeps its workgroup's slice there: no global round trip inside the transform).
 // B = 48 (round 4): lines of 48 R points (96, 192, 384 = 3 * 2^k) -- the smallest smooth circulant grids between the powers of two.
-// The R interleaved sub-transforms are 48-point lines as 6 x 8 in eight lanes (cg_persistent.hip, cg_herm48_kernel: radix 6 on
+// The R interleaved sub-transforms are 48-point lines as 6 x 8 in eight lanes (cg_herm.hip, cg_herm48_kernel: radix 6 on
 // eight lanes, writer-side twiddles, radix 8 on six lanes), the sub-blocks of the exchanges are 48 entries long, and the combine
 // over r hands 48 / (8 R) = 3, 1.5, 0.75 butterflies to a lane (predicated beyond 48).
 __device__ __forceinline__ void dft3_inplace(double2 b0, double2 b1, double2 b2, double2& x0, double2& x1, double2& x2) {
@@ -1479,7 +1479,7 @@ __global__ __launch_bounds__(kLineThreads) void cg_coop2d_kernel(CoopArgs a) {
 //       T_q'[k0] = (T[k0] - conj T[-k0]) / i for k0 >= 0                       -> B2[k0][f1]
 //   Ri: rows k0 >= 0, inverse transform along dim 1, crop to |k1| <= h1, A u = ws .* (.) + sigma^2 u
 // Row k0 = 0 stores BOTH +k1 and -k1; its line G[0][.] is real only up to the anti-Hermitian rounding noise of the iterates,
-// so phase C keeps its real part only (the projection the 64 x 64 kernel needed, see cg_persistent.hip).  Dot products weigh
+// so phase C keeps its real part only (the projection the 64 x 64 kernel needed, see cg_herm.hip).  Dot products weigh
 // the rows k0 > 0 twice.  Same recurrences, stopping rule, barrier / all-reduce machinery as cg_coop2d_kernel; a right-hand
 // side that is not conjugate-even (or a ws that is not real and even) is refused: -2 iterations, NaN in x.
 // Launch geometry in CoopArgs: rows_wg = rows k0 per workgroup (of h0 + 1), cols_wg = column PAIRS per workgroup (of F1 / 2),

@@ -67,7 +67,7 @@ struct CgSolve {
     }
 };
 
-// single-launch CG with the FFT in LDS (cg_persistent.hip).  h48 (may be null): 2-D blocks <= 23 x 23, Hermitian solves run on the
+// single-launch CG with the FFT in LDS (cg_persistent.hip; the Hermitian kernels: cg_herm.hip).  h48 (may be null): 2-D blocks <= 23 x 23, Hermitian solves run on the
 // 48 x 48 grid.  lz: Lanczos mode.  fuse: 48 x 48 Hermitian mean solve only, ws and the spectrum made in the kernel.
 bool persistent_cg_eligible(const ToepGeom& g);
 int persistent_cg_launch(const ToepGeom& g, const double2* const* twiddles, const double2* vhat, const Herm48Operands* h48,

@@ -1,4 +1,4 @@
-"""<p, A p> of cg_herm48_kernel (csrc/cg_persistent.hip, FREQ_DOT) in the row-frequency domain, restated in numpy.
+"""<p, A p> of cg_herm48_kernel (csrc/cg_herm.hip, FREQ_DOT) in the row-frequency domain, restated in numpy.
 
 A = ws T ws + sigma^2 with ws real, so <p, A p> = sigma^2 <p, p> + <ws p, T ws p>.  The kernel keeps rows k0 >= 0 on 48 positions,
 weighs row 0 once and the others twice, and applies T as row transforms G[k0][f1], per-frequency Toeplitz products Yh[k0][f1] and

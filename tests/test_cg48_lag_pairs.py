@@ -1,4 +1,4 @@
-"""The paired-lag Toeplitz products of cg_herm48_pairs_kernel (csrc/cg_persistent.hip, round 9), restated in numpy.
+"""The paired-lag Toeplitz products of cg_herm48_pairs_kernel (csrc/cg_herm.hip, round 9), restated in numpy.
 
 For an output row k0 and an input row m >= 1 the per-frequency Hermitian Toeplitz product of tests/test_cg48_mixed_operator.py adds
 c(k0 - m) G[m] + c(k0 + m) conj G[m], eight multiply-adds.  With G[m] = a + i b this is S a + i Q b,

@@ -1,4 +1,4 @@
-"""The operator application of cg_herm48_kernel (csrc/cg_persistent.hip, DENSE), restated in numpy.
+"""The operator application of cg_herm48_kernel (csrc/cg_herm.hip, DENSE), restated in numpy.
 
 The Toeplitz product Y(k) = sum_k' v(k - k') g(k') of a conjugate-even g on a block of n x n modes (n <= 23) needs a transform
 in ONE dimension only: after the row transforms G[k0][f1] = sum_k1 g(k0, k1) w48^(f1 k1) the convolution over k0 is, for every

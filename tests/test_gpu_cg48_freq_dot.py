@@ -1,4 +1,4 @@
-"""GPU checks of <p, A p> formed in the row-frequency domain in cg_herm48_kernel (csrc/cg_persistent.hip, FREQ_DOT; round 7).
+"""GPU checks of <p, A p> formed in the row-frequency domain in cg_herm48_kernel (csrc/cg_herm.hip, FREQ_DOT; round 7).
 
 A single 48 x 48 Hermitian solve takes <p, A p> = sigma^2 <p, p> + <ws p, T ws p> from the numbers its per-frequency Toeplitz
 products read and produce (Parseval along k1), one phase early, and runs an iteration on three workgroup barriers.  The iteration

@@ -1,4 +1,4 @@
-"""GPU checks of the eight-wave 48 x 48 solve with paired-lag Toeplitz products (cg_herm48_pairs_kernel, csrc/cg_persistent.hip;
+"""GPU checks of the eight-wave 48 x 48 solve with paired-lag Toeplitz products (cg_herm48_pairs_kernel, csrc/cg_herm.hip;
 round 9).
 
 A single 48 x 48 Hermitian solve runs on 512 threads: the row lanes of waves 0-1 as before, the per-frequency Toeplitz products
@@ -173,6 +173,25 @@ def test_refusal_of_a_right_hand_side_that_is_not_conjugate_even(switch, monkeyp
     x, lazy = cg_solve_async(op, ws.cuda(), SIG, 0, bad.cuda(), torch.zeros_like(bad).cuda(), 1e-8, batched=False, hermitian=True)
     assert lazy.rows_tensor.tolist() == [-2]
     assert bool(torch.isnan(x.real).all())
+
+
+@pytest.mark.parametrize("switch", [False, True])
+@pytest.mark.parametrize("mtot", [3, 23])
+def test_refusal_of_weights_that_are_not_real(mtot, switch, monkeypatch):
+    """One entry of ws with an imaginary part of 1e-3: the row lanes' sum over |Im ws|^2 and |ws[k] - ws[-k]|^2 is positive, and
+    both arms refuse -- -2 iterations, every entry of the solution NaN.  The entry sits in a row k0 < 0, which no lane stores: the
+    lane that holds its mirror finds it."""
+    from efgp_hip import ToeplitzOp, cg_solve_mean_async
+    v, T, ws, fy, centre = _case(mtot)
+    op = ToeplitzOp(v.cuda())
+    assert op.cg_shape(hermitian=True) == [48, 48]
+    ws_bad = ws.clone()
+    ws_bad[1] = ws_bad[1] + 1e-3j
+    if switch:
+        monkeypatch.setenv(SWITCH, "1")
+    beta, lazy = cg_solve_mean_async(op, ws_bad.cuda(), SIG, None, fy.cuda(), 1e-8)
+    assert lazy.rows_tensor.tolist() == [-2]
+    assert bool(torch.isnan(beta.real).all()) and bool(torch.isnan(beta.imag).all())
 
 
 @pytest.mark.parametrize("switch", [False, True])

@@ -1,4 +1,4 @@
-"""GPU checks of the per-frequency Toeplitz application of cg_herm48_kernel (csrc/cg_persistent.hip, DENSE; round 6).
+"""GPU checks of the per-frequency Toeplitz application of cg_herm48_kernel (csrc/cg_herm.hip, DENSE; round 6).
 
 A single 48 x 48 Hermitian solve applies the operator as row transforms plus, for every row frequency, a 23 x 23 Hermitian
 Toeplitz product over k0 with coefficients resident in registers.  The application it replaces (packed column transforms on the

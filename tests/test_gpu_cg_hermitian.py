@@ -1,4 +1,4 @@
-"""GPU parity of the Hermitian 64 x 64 CG kernel (csrc/cg_persistent.hip: cg_herm64_kernel).
+"""GPU parity of the Hermitian 64 x 64 CG kernel (csrc/cg_herm.hip: cg_herm64_kernel).
 
 Every CG system of an EFGP model has a right-hand side D F* (real vector) (efgpnd.py:186-189, 792, 1657): coefficients of
 a real function on the symmetric mode grid.  The kernel solves such systems on real transforms (half the line

@@ -113,7 +113,7 @@ def test_adam_trajectory_matches_reference(name):
     with every NUFFT result carrying a relative error of 1e-11 / 1e-10 (oracle/gen_golden_r3.py stores those moves as `sens_cold_*`
     in <case>_r3.npz) -- with floors of 1e-9 (hyper-parameters) and 1e-8 of the gradient scale.  Round 2 had to allow 1e-5 here and
     called it rounding; it was the Hermitian 64 x 64 solver handing the anti-Hermitian rounding noise of its k0 = 0 row to the
-    operator (cg_persistent.hip, phase B): the true residual of these cg_tol = 1e-12 solves stalled at 2e-6 where the reference
+    operator (cg_herm.hip, phase B): the true residual of these cg_tol = 1e-12 solves stalled at 2e-6 where the reference
     reaches 7e-10.  With the projection in place the trajectory sits at the reference's own sensitivity (c2: 2.8e-9 against 4.7e-9)."""
     g, x, y = load_case(name)
     r2 = load_r2(name)
