@@ -74,6 +74,12 @@ def test_named_cases_are_planned_as_restated(plan_check, hooks):
                 assert grid == pick_grid, nm
         else:
             assert "pick" not in g, nm
+        # the Lanczos mode of the same block (efgp_lanczos): line1d and the Hermitian kernels are barred
+        lz_kernel = R.route(ns, herm, hooks, lanczos=True)[0]
+        if lz_kernel in PICKS:
+            assert lz_kernel in ("2d64", "generic") and g["lz_pick"] == PICKS[lz_kernel], nm
+        else:
+            assert "lz_pick" not in g and kernel not in PICKS, nm
         if kernel in ("coop", "coop_herm"):
             shape = _coop(g["coop"])
             assert shape["ok"] == 1 and shape["herm"] == (kernel == "coop_herm") and _grid(g["coop_grid"]) == grid, nm

@@ -1,5 +1,5 @@
 // Stand-alone host program for the planners of csrc/cg_plan_host.cpp: what efgp_toeplitz_create_ex decides for a block, the grid a
-// solve runs on, the kernel the persistent solve picks and the launch shape of the cooperative solve.  No device involved.
+// solve runs on, the kernel the persistent solve picks (pick=; lz_pick= in Lanczos mode) and the launch shape of the cooperative solve.  No device involved.
 //
 //   hipcc -x hip --cuda-host-only -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
 //       tools/cg_plan_check.cpp gp-quadrature_amd/csrc/cg_plan_host.cpp gp-quadrature_amd/csrc/es_kernel.cpp -o cg_plan_check
@@ -74,6 +74,9 @@ static void run_case(int dim, const int64_t* n, int herm, int nbatch, int num_cu
         CHECK(pick_persistent(grid, s, pl.h48, false, false, &c) == EFGP_OK);
         std::printf(" pick=%s dense48=%d", pick_name(c.pick), (int)c.dense48);
         print_grid("pick_grid", dim, grid.F);
+        PersistentChoice lz;          // the same solve in Lanczos mode (efgp_lanczos): no line1d, no Hermitian kernel
+        CHECK(pick_persistent(grid, s, pl.h48, true, false, &lz) == EFGP_OK);
+        std::printf(" lz_pick=%s", pick_name(lz.pick));
     } else if (pl.lines_ok) {
         print_coop("coop", coop_shape(pl.coop_small ? pl.g_co : pl.g, nbatch, herm != 0, num_cu, max_lds));
     }
