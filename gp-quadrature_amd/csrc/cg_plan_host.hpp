@@ -9,7 +9,7 @@
 
 namespace efgp {
 
-constexpr int kLineThreads = 256;             // threads of the line-transform and cooperative kernels (toeplitz_cg.hip)
+constexpr int kLineThreads = 256;             // threads of the line-transform and cooperative kernels (cg_multi.hip, cg_coop2d.hip)
 constexpr int kCoopMaxG = 64;                 // most workgroups per system of the cooperative solve
 constexpr int kCoopLoads = 16;                // grid elements a thread brings in per phase (lpbc F0 / 256 and lines F1 / 256 at most)
 

@@ -1,4 +1,4 @@
-"""The host dispatch of the CG solves (csrc/toeplitz_cg.hip: efgp_toeplitz_create_ex, cg_solve_sync, setup_apply, coop_enqueue;
+"""The host dispatch of the CG solves (csrc/toeplitz_cg.hip: efgp_toeplitz_create_ex, cg_solve_sync; csrc/cg_multi.hip: setup_apply; csrc/cg_coop2d.hip: coop_enqueue;
 csrc/cg_persistent.hip: persistent_cg_launch; csrc/cg_plan_host.cpp: the planners both call) restated in Python, and the named cases of
 tests/test_gpu_cg_routes.py.
 

@@ -1,4 +1,4 @@
-"""The CG systems of csrc/cg_persistent.hip, csrc/cg_herm.hip and csrc/toeplitz_cg.hip written down from the definition: the block Toeplitz matrix as a
+"""The CG systems of csrc/cg_persistent.hip, csrc/cg_herm.hip, csrc/cg_coop2d.hip and csrc/cg_multi.hip (operator: csrc/toeplitz_cg.hip) written down from the definition: the block Toeplitz matrix as a
 dense M x M array, A = D T D + sigma^2 I (variant 0) or D T D / sigma^2 + I (variant 1), a direct solve, and the oracle's CG loops
 (oracle/efgp_oracle.py: cg_single, cg_batched) driven by the dense matrix product -- no FFT, no circulant embedding anywhere.
 

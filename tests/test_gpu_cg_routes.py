@@ -1,4 +1,4 @@
-"""GPU: every route of the CG solves (csrc/cg_persistent.hip, csrc/cg_herm.hip, csrc/toeplitz_cg.hip) on non-cubic, even and edge blocks, held to a
+"""GPU: every route of the CG solves (csrc/cg_persistent.hip, csrc/cg_herm.hip, csrc/cg_coop2d.hip, csrc/cg_multi.hip; dispatch: csrc/toeplitz_cg.hip) on non-cubic, even and edge blocks, held to a
 dense solve.
 
 The reference of the dense cases is the block Toeplitz matrix written down from the definition (tests/_dense_toeplitz.py) -- not

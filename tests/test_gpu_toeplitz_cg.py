@@ -418,6 +418,38 @@ def test_every_cooperative_kernel_equals_the_multi_launch_iteration(n0, n1, nb, 
         assert worst < 1e-12, (variant, worst)
 
 
+@pytest.mark.parametrize("precond", [True, False])
+@pytest.mark.parametrize("n0,n1", [(33, 33), (33, 40)])
+def test_fused_mean_system_on_cooperative_grids(n0, n1, precond, monkeypatch):
+    """efgp_cg_solve_mean_async on the cooperative grids: the kernels' diag_scale, b_times_ws and zero_x0 arms, which
+    test_fused_mean_system_matches_general_solve (persistent grids only) does not reach.  (33, 33) runs cg_coop2d_herm_kernel<4, false>
+    with G = 6; (33, 40) has an even axis and runs cg_coop2d_kernel<4, false> under the Hermitian promise (the routes:
+    tests/test_dense_toeplitz_host.py), both on the (96, 96) grid.  Three forced iterations against the multi-launch iteration
+    (EFGP_NO_CG_COOP) given the materialised operands -- rhs = ws .* fy, diag = centre |ws|^2 + sigmasq, a zero start: relative l2
+    distance below 1e-12, the bound test_every_cooperative_kernel_equals_the_multi_launch_iteration holds the same kernels to
+    against the same partner over the same three iterations.  Measured: profiles/toeplitz_split_ab.txt."""
+    from efgp_hip import ToeplitzOp, cg_solve, cg_solve_mean_async
+    v, ws, b = _psd_system(n0, n1, 3 + n0, 1)
+    fy = b[0]
+    sig = 25.0
+    vd = v.cuda()
+    centre = vd[n0 - 1, n1 - 1].real                      # a view into v, as the fit passes it
+    op = ToeplitzOp(vd)
+    assert tuple(op.cg_shape(hermitian=True)) == (96, 96)
+    res = cg_solve_mean_async(op, ws.cuda(), sig, centre if precond else None, fy.cuda(), 1e-300, max_iter=3, early_stop=False)
+    assert res is not None
+    beta, lazy = res
+    rhs = (ws * fy).cuda()
+    diag = (float(centre) * ws.abs().pow(2).real + sig).cuda() if precond else None
+    monkeypatch.setenv("EFGP_NO_CG_COOP", "1")
+    xg, itg, _ = cg_solve(op, ws.cuda(), sig, 0, rhs, torch.zeros_like(rhs), 1e-300, max_iter=3, early_stop=False, diag=diag, batched=False)
+    monkeypatch.delenv("EFGP_NO_CG_COOP")
+    dist = _rel(beta, xg)
+    print(f"\nmean on coop grid {n0}x{n1} precond={precond}: iterations {int(lazy)} / {itg}, distance {dist:.3e}")
+    assert int(lazy) == itg == 3
+    assert dist < 1e-12, dist
+
+
 def _replay_system(d, mtot, hermitian):
     """Five right-hand sides on a (mtot,)*d block; Hermitian: conjugate-even rows and a real even ws (tests/test_gpu_cg_hermitian.py)."""
     x, v, T = _setup(d, mtot, N=300, seed=9)
