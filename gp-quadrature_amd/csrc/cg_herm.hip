@@ -135,6 +135,42 @@ __device__ __forceinline__ bool refused(double asym, double bb, double ws_bad) {
 
 // Vector slots of a row lane: positions j + STRIDE t of its line, t in {0, 1, 6, 7} <-> k1 = j, j + STRIDE, j - 2 STRIDE, j - STRIDE
 // (STRIDE 8: the 64-point lines, 6: the 48-point lines) of the row k0 >= 0; the modes -k are the conjugates and are not stored.
+// What a row lane reads from memory before its first residual, issued at kernel entry (cg_herm48_pairs_kernel, round 10): the round
+// trips run under the prologue instead of standing, one behind the other, between the prologue and the first iteration.  The slot
+// arithmetic is RowLanes::setup's; a lane or slot without a mode loads nothing.
+template <int STRIDE>
+struct EarlyLoads {
+    double2 bv[KS], bm[KS];              // b at the mode and at its mirror
+    double2 x0[KS], w[KS], wm[KS];       // !FUSED: the start vector (warm start only), ws at the mode and at its mirror
+    double dgv[KS], dscale;              // the Jacobi diagonal's entry, or the scalar it is made from
+
+    template <bool FUSED>
+    __device__ __forceinline__ void issue(const Args& a, bool role, int k0, int j) {
+        const int n = a.g.n[0], h = (n - 1) / 2, M = a.g.M;
+        const int64_t base = (int64_t)blockIdx.x * M;
+        dscale = (role && !a.diag && a.diag_scale) ? *a.diag_scale : 0.0;
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            const int k1 = s == 0 ? j : (s == 1 ? j + STRIDE : (s == 2 ? j - 2 * STRIDE : j - STRIDE));
+            const bool ok = role && k0 <= h && k1 <= h && -k1 <= h;
+            const int idx = ok ? (k0 + h) * n + (k1 + h) : 0;
+            const double2 zero = make_double2(0.0, 0.0);
+            bv[s] = ok ? a.b[base + idx] : zero;
+            bm[s] = ok ? a.b[base + (M - 1 - idx)] : zero;
+            dgv[s] = (ok && a.diag) ? a.diag[idx] : 0.0;
+            x0[s] = (ok && !FUSED && !a.zero_x0) ? a.x0[base + idx] : zero;
+            w[s] = (ok && !FUSED) ? a.ws[idx] : zero;
+            wm[s] = (ok && !FUSED) ? a.ws[M - 1 - idx] : zero;
+        }
+    }
+    // jacobi_entry from what was loaded: the same two roundings
+    __device__ __forceinline__ double jacobi(const Args& a, double2 wv, int s) const {
+        if (a.diag) return dgv[s];
+        if (a.diag_scale) return __dadd_rn(__dmul_rn(dscale, __dadd_rn(__dmul_rn(wv.x, wv.x), __dmul_rn(wv.y, wv.y))), a.sigmasq);
+        return 1.0;
+    }
+};
+
 template <int STRIDE>
 struct RowLanes {
     double2 xv[KS], rv[KS], pv[KS];
@@ -149,8 +185,9 @@ struct RowLanes {
 
     // role: the lane may hold modes (a row lane; on the 48-point lines one with j < 6).  FUSED: the fit's cold-start mean solve, ws
     // evaluated here from the built-in kernel's parameters and written out for later users.
-    template <bool FUSED>
-    __device__ __forceinline__ void setup(const Args& a, bool role, int k0_, int j) {
+    // EARLY: x0, ws and the diagonal come from `e` (EarlyLoads::issue with the same role, k0_, j) instead of from memory.
+    template <bool FUSED, bool EARLY = false>
+    __device__ __forceinline__ void setup(const Args& a, bool role, int k0_, int j, const EarlyLoads<STRIDE>* e = nullptr) {
         const int n = a.g.n[0], h = (n - 1) / 2;
         M = a.g.M;
         k0 = k0_;
@@ -171,13 +208,23 @@ struct RowLanes {
                 a.ws_out[idx[s]] = w;
                 a.ws_out[M - 1 - idx[s]] = w;
                 wsr[s] = w.x;
-                dg[s] = jacobi_entry(a, w, idx[s]);
+                if constexpr (EARLY) dg[s] = e->jacobi(a, w, s);
+                else dg[s] = jacobi_entry(a, w, idx[s]);
             } else if (ok[s]) {
-                xv[s] = a.zero_x0 ? make_double2(0.0, 0.0) : a.x0[base + idx[s]];
-                const double2 w = a.ws[idx[s]], wm = a.ws[M - 1 - idx[s]];
+                if constexpr (EARLY) xv[s] = a.zero_x0 ? make_double2(0.0, 0.0) : e->x0[s];
+                else xv[s] = a.zero_x0 ? make_double2(0.0, 0.0) : a.x0[base + idx[s]];
+                double2 w, wm;
+                if constexpr (EARLY) {
+                    w = e->w[s];
+                    wm = e->wm[s];
+                } else {
+                    w = a.ws[idx[s]];
+                    wm = a.ws[M - 1 - idx[s]];
+                }
                 wsr[s] = w.x;
                 ws_im = w.y * w.y + (w.x - wm.x) * (w.x - wm.x) + wm.y * wm.y;
-                dg[s] = jacobi_entry(a, w, idx[s]);
+                if constexpr (EARLY) dg[s] = e->jacobi(a, w, s);
+                else dg[s] = jacobi_entry(a, w, idx[s]);
             } else {
                 xv[s] = make_double2(0.0, 0.0);
                 wsr[s] = 0.0;
@@ -193,18 +240,28 @@ struct RowLanes {
     // (weighted) and of asym.  One uniform branch on the preconditioner around the whole block, here and in step(): with the choice
     // made per slot (precond ? r / diag : r) the compiler turns it into selects -- the quotients are then formed also when there is
     // no diagonal, and 16 v_cndmask sit on the row waves' chain (profiles/cg_herm_refactor_device_code.txt)
-    __device__ __forceinline__ void start(const Args& a, const double2 (&Ax)[KS], double& rz, double& bb, double& asym) {
-        if (precond) start_<true>(a, Ax, rz, bb, asym);
-        else start_<false>(a, Ax, rz, bb, asym);
+    // EARLY: b and its mirror come from `e`.
+    template <bool EARLY = false>
+    __device__ __forceinline__ void start(const Args& a, const double2 (&Ax)[KS], double& rz, double& bb, double& asym,
+                                          const EarlyLoads<STRIDE>* e = nullptr) {
+        if (precond) start_<true, EARLY>(a, Ax, rz, bb, asym, e);
+        else start_<false, EARLY>(a, Ax, rz, bb, asym, e);
     }
-    template <bool PRECOND>
-    __device__ __forceinline__ void start_(const Args& a, const double2 (&Ax)[KS], double& rz, double& bb, double& asym) {
+    template <bool PRECOND, bool EARLY>
+    __device__ __forceinline__ void start_(const Args& a, const double2 (&Ax)[KS], double& rz, double& bb, double& asym,
+                                           const EarlyLoads<STRIDE>* e) {
         rz = bb = asym = 0.0;
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
             if (ok[s]) {
-                double2 bv = a.b[base + idx[s]];
-                double2 bm = a.b[base + (M - 1 - idx[s])];                 // mode -k: must be the conjugate
+                double2 bv, bm;
+                if constexpr (EARLY) {
+                    bv = e->bv[s];
+                    bm = e->bm[s];
+                } else {
+                    bv = a.b[base + idx[s]];
+                    bm = a.b[base + (M - 1 - idx[s])];                     // mode -k: must be the conjugate
+                }
                 if (a.b_times_ws) {
                     bv = make_double2(wsr[s] * bv.x, wsr[s] * bv.y);
                     bm = make_double2(wsr[s] * bm.x, wsr[s] * bm.y);
@@ -242,17 +299,28 @@ struct RowLanes {
     }
 
     // x += alpha p, r -= alpha A p, z = r / diag (Jacobi) or r; the lane's shares of <r,r> and <r,z>
+    // !X_UPDATE: x is left as it is; the caller owes it update_x(alpha, p) with this alpha and this p (nothing reads x before write-out)
+    template <bool X_UPDATE = true>
     __device__ __forceinline__ void step(double alpha, const double2 (&Ap)[KS], double2 (&zv)[KS], double& rr, double& rzn) {
-        if (precond) step_<true>(alpha, Ap, zv, rr, rzn);
-        else step_<false>(alpha, Ap, zv, rr, rzn);
+        if (precond) step_<true, X_UPDATE>(alpha, Ap, zv, rr, rzn);
+        else step_<false, X_UPDATE>(alpha, Ap, zv, rr, rzn);
     }
-    template <bool PRECOND>
+    __device__ __forceinline__ void update_x(double alpha, const double2 (&p)[KS]) {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            xv[s].x += alpha * p[s].x;
+            xv[s].y += alpha * p[s].y;
+        }
+    }
+    template <bool PRECOND, bool X_UPDATE>
     __device__ __forceinline__ void step_(double alpha, const double2 (&Ap)[KS], double2 (&zv)[KS], double& rr, double& rzn) {
         rr = rzn = 0.0;
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
-            xv[s].x += alpha * pv[s].x;
-            xv[s].y += alpha * pv[s].y;
+            if constexpr (X_UPDATE) {
+                xv[s].x += alpha * pv[s].x;
+                xv[s].y += alpha * pv[s].y;
+            }
             rv[s].x -= alpha * Ap[s].x;
             rv[s].y -= alpha * Ap[s].y;
             zv[s] = PRECOND ? make_double2(div_rcp(rv[s].x, dg[s], rdg[s]), div_rcp(rv[s].y, dg[s], rdg[s])) : rv[s];
@@ -1176,6 +1244,13 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
 // Dense role, NOUT output rows per lane (2: waves 2-4, rows kd = 2 g, 2 g + 1; 1: waves 5-7, row kd = g + 4).  The last wave is the
 // one with the least to do: it also takes the norm test and the reciprocal for the next beta (the duties of cg_herm48_kernel's idle
 // wave 3).
+//
+// Round 10 (CHAIN_V1 false, the default; EFGP_CG48_CHAIN_V1=1 keeps the statements of round 9), the row role only: two things leave
+// the dependent chain, neither changes an operation or its order.  The row lanes run x += alpha_k p_k between barriers 1 and 2 of
+// application k + 1, where they wait for the dense waves, from a copy of p_k taken in the same place one application earlier; every
+// way out of the loop pays what is owed.  And what the row lanes read from memory before the first residual is loaded at kernel
+// entry (hrow::EarlyLoads).  The dense role is untouched: reading the stop flag together with G and branching behind the products
+// was measured and dropped (profiles/r10_cg48_chain_ab.txt: no time gained).
 template <int NOUT>
 __device__ __forceinline__ void pairs_dense_role(const Args& a, double2* lds2, double* red, double* s_part, double* s_rcp, int* s_stop) {
     using namespace h48;
@@ -1200,11 +1275,21 @@ __device__ __forceinline__ void pairs_dense_role(const Args& a, double2* lds2, d
     // one operator application, as the dense lanes see it; false: the stopping decision of the last iteration was "stop"
     auto products = [&]() __attribute__((always_inline)) -> bool {
         __syncthreads();                                  // barrier 1: G and the row lanes' shares of <u,u> are written
-        if (*s_stop) return false;
+#ifdef EFGP_CG_STAMPS
+        // slot 8: from barrier 1 until the flag and the first row of G are in the first dense lane's registers
         EFGP_STAMP_RESTART(64 * kRowWavesP);
+        const int flag = *s_stop;
+        if (flag) return false;
+#else
+        if (*s_stop) return false;
+#endif
         double2 gm[NR], acc[NOUT], gk[NOUT];
 #pragma unroll
         for (int m = 0; m < NR; ++m) gm[m] = g0[m * LDR];
+#ifdef EFGP_CG_STAMPS
+        asm volatile("" ::"v"(gm[0].x), "v"(gm[0].y), "v"(flag));
+        EFGP_STAMP_BY(8, 64 * kRowWavesP);
+#endif
 #pragma unroll
         for (int o = 0; o < NOUT; ++o) acc[o] = pair_product(pc[o], gm);
         // G of the lane's own rows once more (kd differs between the lanes of a wave: gm[kd + o] is no register)
@@ -1238,7 +1323,7 @@ __device__ __forceinline__ void pairs_dense_role(const Args& a, double2* lds2, d
 // Register budget: 512 threads are two waves per SIMD, which an allocation of up to 256 VGPR + AGPR still admits on gfx950
 // (__launch_bounds__(512) is that limit).  The two-row dense lanes are the tight role: 184 registers of coefficients, 48 of G, 8 of
 // accumulators; no role may spill (scratch 0 -- profiles/r9_cg48_lag_pairs_ab.txt records the compiler's figures).
-template <int VARIANT, bool FUSED = false>
+template <int VARIANT, bool FUSED = false, bool CHAIN_V1 = false>
 __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a) {
     using namespace h48;
     using h64::dft8_in4;
@@ -1266,6 +1351,10 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
         s_stop = 0;
         s_rcp = 0.0;
     }
+    // the row lanes' loads of b, the diagonal and, without FUSED, x0 and ws go out here and are used behind the prologue
+    constexpr bool EARLY = !CHAIN_V1, DEFER_X = !CHAIN_V1;
+    [[maybe_unused]] hrow::EarlyLoads<6> early;
+    if constexpr (EARLY) early.template issue<FUSED>(a, tid < 8 * NR && j < 6, k0, j);
     // the operator's spectrum, made here (one pass per dimension on 64 line slots) or from memory -- the same numbers -- and one
     // inverse pass along f0: the same statements with and without FUSED
     if (FUSED) {
@@ -1297,7 +1386,8 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
     double2* const xw = Qb + k0s * LX + 9 * j;
     const double2* const xr = Qb + k0s * LX + j;
     hrow::RowLanes<6> L;                 // slots k1 = j, j + 6, j - 12, j - 6 of the lanes j < 6
-    L.setup<FUSED>(a, vec_role, k0, j);
+    if constexpr (EARLY) L.template setup<FUSED, true>(a, vec_role, k0, j, &early);
+    else L.template setup<FUSED>(a, vec_role, k0, j);
     const double (&wsr)[KS] = L.wsr;
     const bool (&ok)[KS] = L.ok;
     const double wgt = L.wgt;
@@ -1310,6 +1400,10 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
     double rcp_rz = 0.0;
     double rz = 0.0;
     double alpha_fd = 0.0;               // rz / (<u, A u> + 1e-16) of the last operator application, formed inside D
+    // DEFER_X: x is one update behind.  owed: x += alpha_fd * p_prev is outstanding, with alpha_fd still that of the last completed
+    // application (D of the next one has not run) and p_prev the vector that application transformed
+    [[maybe_unused]] bool owed = false;
+    [[maybe_unused]] double2 p_prev[KS];
     auto apply_A = [&](const double2 (&u)[KS], double2 (&Au)[KS]) __attribute__((always_inline)) {
         double2 v[8], u6[6];
         EFGP_STAMP(7);
@@ -1329,6 +1423,18 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
         rcp_rz = s_rcp;
         if (stop) return;                                 // uniform: the iteration that just started is abandoned
         EFGP_STAMP(0);
+        if constexpr (DEFER_X) {
+            // the row waves wait here for the dense waves: the x update of the last iteration, and the copy of u for the next one
+            if (owed) L.update_x(alpha_fd, p_prev);
+            owed = false;
+            // (moves written out: a plain assignment is a renaming to the compiler, and the moves it then needs at the loop's back
+            // edge stand behind D, on the chain)
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                asm volatile("v_mov_b64 %0, %1" : "=v"(p_prev[s].x) : "v"(u[s].x));
+                asm volatile("v_mov_b64 %0, %1" : "=v"(p_prev[s].y) : "v"(u[s].y));
+            }
+        }
         __syncthreads();                                  // barrier 2: the dense waves' products (pairs_dense_role stamps them)
         EFGP_STAMP_RESTART(0);
         // D ("8x6"): row k0 >= 0 of the result from Yh[k0]; conjugated inputs, forward transform
@@ -1377,7 +1483,8 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
         apply_A(L.xv, Ap);
     }
     double bb, asym;
-    L.start(a, Ap, rz, bb, asym);
+    if constexpr (EARLY) L.template start<true>(a, Ap, rz, bb, asym, &early);
+    else L.start(a, Ap, rz, bb, asym);
     rz = wave_sum(rz);
     bb = wave_sum(bb);
     asym = wave_sum(asym);
@@ -1403,7 +1510,12 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
         if (stop) break;
         double rr, rzn;
         double2 zv[KS];
-        L.step(alpha_fd, Ap, zv, rr, rzn);                // alpha from D straight into the updates
+        if constexpr (DEFER_X) {
+            L.template step<false>(alpha_fd, Ap, zv, rr, rzn);
+            owed = true;
+        } else {
+            L.step(alpha_fd, Ap, zv, rr, rzn);            // alpha from D straight into the updates
+        }
         EFGP_STAMP(4);
         rr = wave_sum(rr);
         rzn = wave_sum(rzn);
@@ -1416,6 +1528,10 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
         EFGP_STAMP(5);
         ++it;
         L.new_direction(zv, rzn, rz, rcp_rz);
+    }
+    if constexpr (DEFER_X) {
+        // the update of the last completed iteration: the loop ended at max_iter, or on "stop" behind barrier 1, in front of D
+        if (owed) L.update_x(alpha_fd, p_prev);
     }
     L.write_out(a, it);
 }
@@ -1453,16 +1569,23 @@ PickLaunch herm_launch(const PersistentChoice& c, int variant, const Herm48Opera
     // instead of the eight waves with paired lags (round 9).  EFGP_CG48_MODE_DOT=1 is an iteration of the 256-thread kernels only.
     const bool pairs = c.dense48 && freq_dot && std::getenv("EFGP_CG48_LAG_COEFFS") == nullptr;
     constexpr size_t lds48p = (size_t)h48::kLdsElemsPairs * sizeof(double2);
+    // EFGP_CG48_CHAIN_V1=1 (read per call): the eight-wave kernel with the x update inside the iteration's chain and the row lanes'
+    // loads behind the prologue (round 9) instead of off the chain (round 10); equal bits
+    const bool chain_v1 = std::getenv("EFGP_CG48_CHAIN_V1") != nullptr;
     switch (c.pick) {
         case PersistentPick::fused48: {
-            if (pairs) return {cg_herm48_pairs_kernel<0, true>, h48::kThreadsP, lds48p, "fused mean solve (48x48, eight waves)"};
+            if (pairs)
+                return {chain_v1 ? cg_herm48_pairs_kernel<0, true, true> : cg_herm48_pairs_kernel<0, true>, h48::kThreadsP, lds48p,
+                        "fused mean solve (48x48, eight waves)"};
             void (*const dense[2])(Args) = {cg_herm48_kernel<0, true, true, false>, cg_herm48_kernel<0, true, true, true>};
             return {c.dense48 ? dense[freq_dot] : cg_herm48_kernel<0, true, false>, h48::kThreadsH, lds48d, "fused mean solve (48x48)"};
         }
         case PersistentPick::herm48: {
-            if (pairs)
-                return {variant == 0 ? cg_herm48_pairs_kernel<0> : cg_herm48_pairs_kernel<1>, h48::kThreadsP, lds48p,
-                        "persistent CG (48x48, Hermitian, eight waves)"};
+            if (pairs) {
+                void (*const eight[2][2])(Args) = {{cg_herm48_pairs_kernel<0>, cg_herm48_pairs_kernel<1>},
+                                                   {cg_herm48_pairs_kernel<0, false, true>, cg_herm48_pairs_kernel<1, false, true>}};
+                return {eight[chain_v1][variant != 0], h48::kThreadsP, lds48p, "persistent CG (48x48, Hermitian, eight waves)"};
+            }
             void (*const dense[2][2])(Args) = {{cg_herm48_kernel<0, false, true, false>, cg_herm48_kernel<1, false, true, false>},
                                                {cg_herm48_kernel<0, false, true, true>, cg_herm48_kernel<1, false, true, true>}};
             void (*const fft2d[2])(Args) = {cg_herm48_kernel<0, false, false>, cg_herm48_kernel<1, false, false>};

@@ -50,14 +50,20 @@ if len(sys.argv) > 1 and sys.argv[1] == "herm":
     # others by thread 0, whose clock restarts behind barrier 2.  EFGP_CG48_LAG_COEFFS=1: the 256-thread kernel of round 7.
     mode_dot = os.environ.get("EFGP_CG48_MODE_DOT") is not None
     pairs = not mode_dot and os.environ.get("EFGP_CG48_LAG_COEFFS") is None and os.environ.get("EFGP_CG48_FFT2D") is None
+    # Round 10: slot 8, stamped by the first dense lane: from barrier 1 until the stop flag and the first row of G are in its
+    # registers (slot 1 starts there).  EFGP_CG48_CHAIN_V1=1: the x update inside slot 4 instead of between barriers 1 and 2, and
+    # the row lanes' loads behind the prologue (round 9).
+    chain_v1 = pairs and os.environ.get("EFGP_CG48_CHAIN_V1") is not None
     print("arm: " + ("<p,Ap> over the modes behind D (EFGP_CG48_MODE_DOT=1)" if mode_dot else "<p,Ap> in the row-frequency domain")
-          + ("; eight waves, paired lags" if pairs else "; 256 threads, 25 resident lags"))
+          + ("; eight waves, paired lags" if pairs else "; 256 threads, 25 resident lags")
+          + ("; x update on the chain, late loads (EFGP_CG48_CHAIN_V1=1)" if chain_v1 else ""))
     names = {0: "A: ws*p, row transforms (h+1 lines)" + ("" if mode_dot else ", <p,p> partials"),
              1: "per-frequency Toeplitz products (or B/C)",
              2: "D: row transforms, A u" + ("" if mode_dot else "; alpha = rz / pAp"),
              3: "<p,Ap>: wave sums, LDS, barrier", 4: "alpha, x r z updates, partial sums" if mode_dot else "x r z updates, partial sums",
              5: "<r,r>, <r,z>: wave sums, LDS, barrier",
-             6: "<p,Ap>: frequency terms, wave sum, LDS, barrier", 7: "norm test, beta, p update"}
+             6: "<p,Ap>: frequency terms, wave sum, LDS, barrier", 7: "norm test, beta, p update",
+             8: "dense lanes: barrier 1 to the first row of G"}
 herm_names = names if len(sys.argv) > 1 and sys.argv[1] == "herm" else None
 names = herm_names or {0: "load ws*p -> LDS", 1: "fwd pass 0 (last dim)", 2: "fwd pass 1 (+fused mid)", 3: "fwd pass 2",
          4: "inv pass 0 (rest)", 5: "inv pass 1", 6: "inv pass 2", 7: "vector updates + reductions", 8: "crop + A u"}
