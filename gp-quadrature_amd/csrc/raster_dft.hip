@@ -188,6 +188,12 @@ void gemm(hipStream_t stream, const double2* T, int64_t R, int64_t Kpad, const d
 
 }  // namespace
 
+void raster_table_enqueue(hipStream_t stream, const double* x, int64_t n, int64_t m, int64_t Kpad, double h, double xcen, int isign, int modeord,
+                          int by_mode, double* cosp, double* sinp) {
+    hipLaunchKernelGGL(raster_table_kernel, dim3(grid_1d(n * Kpad)), dim3(kThreads), 0, stream, x, n, m, Kpad, h, xcen, isign, modeord, by_mode,
+                       cosp, sinp);
+}
+
 int raster_type2_enqueue(const RasterCall& c, const RasterPlan& plan, void* ws, hipStream_t stream) {
     const int d = c.dim;
     double* base = (double*)ws;
@@ -199,8 +205,7 @@ int raster_type2_enqueue(const RasterCall& c, const RasterPlan& plan, void* ws, 
         cosp[a] = base;
         sinp[a] = base + plane;
         base += 2 * plane;
-        hipLaunchKernelGGL(raster_table_kernel, dim3(grid_1d(plane)), dim3(kThreads), 0, stream, axis, c.n[a], c.m[a], plan.Kpad[a], c.h[a],
-                           c.xcen[a], c.isign, c.modeord, a == d - 1 ? 1 : 0, cosp[a], sinp[a]);
+        raster_table_enqueue(stream, axis, c.n[a], c.m[a], plan.Kpad[a], c.h[a], c.xcen[a], c.isign, c.modeord, a == d - 1 ? 1 : 0, cosp[a], sinp[a]);
         axis += c.n[a];
     }
     const int64_t B = c.nbatch;

@@ -32,4 +32,24 @@ struct RasterPlan {
 // bytes needed).  max_workspace_bytes = 0: kRasterDefaultWorkspace.
 int plan_raster(int dim, const int64_t* n_modes, const int64_t* n_axis, int nbatch, int64_t max_workspace_bytes, RasterPlan* out);
 
+// The adjoint (type 1, raster_adjoint.hip): raster values in, a mode box out.  The last raster axis is contracted first (a GEMM),
+// then the leading axes.  The reduction over the leading raster axis is split into partial sums over kRasterChunk rows each, added
+// in chunk order; a slab is a whole number of chunks, so the sums do not depend on the slab plan.
+constexpr int kRasterChunk = kRasterTile;
+// The GEMM cuts a last raster axis longer than this into segments of this many cells, one workgroup column each, whose sums are
+// added in segment order: a function of the axis length alone.
+constexpr int64_t kRasterSegment = 256;
+inline int64_t raster_segments(int64_t n_last) { return (n_last + kRasterSegment - 1) / kRasterSegment; }
+
+// Workspace layout of one type-1 call, in this order, in the fields of RasterPlan:
+//   per axis a: cos plane, sin plane, each (n_axis[a], Kpad[a]) doubles, all row-major
+//   d = 1:      the GEMM's segments (nbatch, S, m0) complex where S = raster_segments(n_axis[0]) > 1   -- counted in table_bytes
+//   d = 2:      T1 (nbatch, slab_rows, m1) complex, partial sums (nbatch, slab_rows / kRasterChunk, m0, m1) complex,
+//               segments (nbatch, slab_rows, S, m1) complex where S = raster_segments(n_axis[1]) > 1
+//   d = 3:      T1 (nbatch, slab_rows, n_axis[1], m2) complex, T2 (nbatch, slab_rows, m1 * m2) complex,
+//               partial sums (nbatch, slab_rows / kRasterChunk, m0 * m1 * m2) complex,
+//               segments (nbatch, slab_rows, n_axis[1], S, m2) complex where S = raster_segments(n_axis[2]) > 1
+// The same refusals as plan_raster.
+int plan_raster_type1(int dim, const int64_t* n_modes, const int64_t* n_axis, int nbatch, int64_t max_workspace_bytes, RasterPlan* out);
+
 }  // namespace efgp

@@ -98,6 +98,8 @@ _SIGNATURES = {
     "efgp_variance_contract_nd": (_I, [_I, _I, _PI64, C.POINTER(_D), _VP, _I64, _VP, _VP, _VP, _VP]),
     "efgp_raster_type2": (_I, [_I, _I, _PI64, C.POINTER(_D), C.POINTER(_D), _PI64, _VP, _VP, _VP, _I, _I, _I, _VP, _I64, _VP]),
     "efgp_raster_plan": (_I, [_I, _PI64, _PI64, _I, _I64, _PI64, _PI64, _PI64]),
+    "efgp_raster_type1": (_I, [_I, _I, _PI64, C.POINTER(_D), C.POINTER(_D), _PI64, _VP, _VP, _VP, _I, _I, _I, _VP, _I64, _VP]),
+    "efgp_raster_type1_plan": (_I, [_I, _PI64, _PI64, _I, _I64, _PI64, _PI64, _PI64]),
     "efgp_cheb_interp":(_I, [_I, _I, _PI64, _VP, _VP, _VP, _VP, _I64, _I, _VP, _VP]),
     "efgp_hermitian_normal_rows": (_I, [_I, C.c_uint64, _I64, _I, _I64, _D, _VP, _VP, _D, _VP, _VP]),
     "efgp_pg_estep_update": (_I, [_I, _I64, _I, _VP, _VP, C.c_uint64, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP, _VP]),

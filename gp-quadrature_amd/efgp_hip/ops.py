@@ -832,6 +832,179 @@ def raster_type2(axes, h, n_modes, f, *, modeord=0, isign=+1, mode_scale=None, x
     return res if batched else res[0]
 
 
+def raster_type1_plan(n_axis, n_modes, nbatch=1, max_workspace_bytes=0):
+    """Slabs and workspace of a raster_type1 call from a raster of n_axis cells per axis (efgp_raster_type1_plan, host only):
+    dict(slab_rows, slabs, workspace_bytes).  ValueError when the cap cannot hold the phase tables and one 16-row slab."""
+    n_axis = tuple(int(n) for n in (_per_axis(n_axis) or (n_axis,)))
+    shape = tuple(int(m) for m in (_per_axis(n_modes) or (n_modes,)))
+    if len(n_axis) != len(shape) or not 1 <= len(shape) <= 3:
+        raise ValueError(f"raster_type1_plan: n_axis has {len(n_axis)} entries and n_modes {len(shape)}; both must have 1, 2 or 3")
+    rows, slabs, nbytes = C.c_int64(), C.c_int64(), C.c_int64()
+    check(lib().efgp_raster_type1_plan(len(shape), _i64(shape), _i64(n_axis), int(nbatch), int(max_workspace_bytes), C.byref(rows),
+                                       C.byref(slabs), C.byref(nbytes)), "efgp_raster_type1_plan")
+    return dict(slab_rows=rows.value, slabs=slabs.value, workspace_bytes=nbytes.value)
+
+
+def _checked_cell_scale(what, cell_scale, n_axis, dev):
+    """cell_scale as a contiguous float64 tensor of the raster's size on `dev`; ValueError unless finite and >= 0."""
+    if not torch.is_tensor(cell_scale):
+        cell_scale = torch.as_tensor(cell_scale)
+    if cell_scale.numel() != math.prod(n_axis):
+        raise ValueError(f"{what}: cell_scale has {cell_scale.numel()} entries, the raster {n_axis} has {math.prod(n_axis)}")
+    sc = _dc(cell_scale.reshape(-1), dev, _RD)
+    if not bool((torch.isfinite(sc) & (sc >= 0)).all()):
+        raise ValueError(f"{what}: cell_scale must be finite and >= 0")
+    return sc
+
+
+def raster_type1(axes, h, n_modes, values, *, cell_scale=None, modeord=0, isign=-1, xcen=None, batched=None, max_workspace_bytes=0, out=None,
+                 _scale_checked=False):
+    """Exact type-1 transform from the rectilinear raster axes[0] x .. x axes[d-1] ("ij" order) onto a mode box (efgp_raster_type1),
+    the adjoint of `raster_type2`:
+
+        out[b, k] = sum_j values[b, j] cell_scale[j] exp(isign 2 pi i sum_a h[a] k_a (axes[a][j_a] - xcen[a]))
+
+    axes: d one-dimensional tensors (any spacing, any order); h: one spacing or d; values (prod n,) | (*n_axis) | (B, ...) real;
+    cell_scale (*n_axis) real, finite and >= 0, or None: a cell whose scale is 0 is left out whatever its value holds (NaN included).
+    Returns complex128 (*n_modes) or (B, *n_modes) on the GPU.  No window and no tolerance.  Bitwise repeatable, independent of
+    max_workspace_bytes (0: the library's default cap of the pooled workspace).  `out`: a contiguous complex128 tensor of the
+    result's size to write into."""
+    axes, hv, shape = _raster_args("raster_type1", axes, h, n_modes)
+    d, M = len(shape), math.prod(shape)
+    n_axis = tuple(int(a.numel()) for a in axes)
+    ncells = math.prod(n_axis)
+    if not torch.is_tensor(values):
+        values = torch.as_tensor(values)
+    if values.is_complex():
+        raise ValueError("raster_type1: values must be real")
+    if values.numel() == 0 or values.numel() % ncells:
+        raise ValueError(f"raster_type1: values has {values.numel()} entries, the raster {n_axis} has {ncells}")
+    if batched is None:
+        batched = not (values.ndim == 1 or tuple(values.shape) == n_axis)
+    if not batched and values.numel() != ncells:
+        raise ValueError(f"raster_type1: values has {values.numel()} entries, the raster {n_axis} has {ncells}")
+    if xcen is not None:
+        xc = _per_axis(xcen)
+        xc = tuple(float(v) for v in xc) if xc is not None else (float(xcen),) * d
+        if len(xc) != d:
+            raise ValueError(f"raster_type1: xcen has {len(xc)} entries for {d} axes")
+    if isign not in (-1, 1):
+        raise ValueError(f"raster_type1: isign must be +1 or -1 (got {isign})")
+    if modeord not in (0, 1):
+        raise ValueError(f"raster_type1: modeord must be 0 or 1 (got {modeord})")
+    dev = compute_device(values, *axes)
+    sc = None
+    if cell_scale is not None:
+        sc = cell_scale if _scale_checked else _checked_cell_scale("raster_type1", cell_scale, n_axis, dev)
+    vv = _dc(values.reshape(-1, ncells), dev, _RD)
+    B = vv.shape[0]
+    ax = _dc(axes[0], dev, _RD) if d == 1 else torch.cat([a.to(device=dev, dtype=_RD) for a in axes])
+    if out is None:
+        out = torch.empty((B,) + shape, dtype=_CD, device=dev)
+    elif not (out.is_cuda and out.dtype is _CD and out.is_contiguous() and out.numel() == B * M):
+        raise ValueError("raster_type1: out must be a contiguous complex128 GPU tensor of the result's size")
+    with _on(dev):
+        check(lib().efgp_raster_type1(dev.index, d, _i64(shape), _f64(hv), _f64(xc) if xcen is not None else None, _i64(n_axis), _ptr(ax),
+                                      _ptr(vv), _ptr(sc) if sc is not None else None, B, int(isign), int(modeord), _ptr(out),
+                                      int(max_workspace_bytes), _stream(dev)), "efgp_raster_type1")
+    res = out.reshape((B,) + shape)
+    return res if batched else res[0]
+
+
+class RasterPlan:
+    """The transforms of a model whose observations lie on the rectilinear raster axes[0] x .. x axes[d-1]: the part of the
+    `NufftPlan` surface that a model uses on its training points, on `raster_type1` / `raster_type2` -- exact, with no point layout and no
+    coordinate tensor.  "Points" are the raster cells in row-major order (`npts` of them); `cell_scale` (the raster's shape, finite,
+    >= 0; a 0/1 mask of observed cells in the model) multiplies every type-1 input, and a cell of scale 0 is left out whatever
+    the input holds there."""
+
+    def __init__(self, axes, h, cell_scale=None, xcen=None, _scale_checked=False):
+        if torch.is_tensor(axes) or not hasattr(axes, "__len__"):
+            axes = [axes]
+        axes, _, _ = _raster_args("RasterPlan", axes, h, (1,) * len(axes))
+        self.dev = compute_device(*axes)
+        self.axes = [_dc(a, self.dev, _RD) for a in axes]
+        self.dim = len(self.axes)
+        self.n_axis = tuple(int(a.numel()) for a in self.axes)
+        self.npts = math.prod(self.n_axis)
+        hv = _per_axis(h)
+        self.h = tuple(float(v) for v in hv) if hv is not None else float(h)
+        self.xcen = None if xcen is None else tuple(float(v) for v in xcen)
+        # _scale_checked: a model makes a plan per fit over one mask it has checked once (the check reads back from the device)
+        if cell_scale is not None and not _scale_checked:
+            cell_scale = _checked_cell_scale("RasterPlan", cell_scale, self.n_axis, self.dev)
+        self.scale = cell_scale
+        self.probe_block_bytes = 256 << 20          # bound on the generated probe rows held at once
+
+    def close(self):
+        pass
+
+    def _t1(self, values, n_modes, modeord=0, isign=-1, batched=None, scale=True, out=None):
+        return raster_type1(self.axes, self.h, n_modes, values, cell_scale=self.scale if scale else None, modeord=modeord, isign=isign,
+                            xcen=self.xcen, batched=batched, out=out, _scale_checked=True)
+
+    def type1(self, c, n_modes, modeord=0, isign=-1):
+        """c (ncells,) | (*n_axis) | (B, ...) real -> (B?, *n_modes) complex128."""
+        if c.is_complex():
+            raise NotImplementedError("RasterPlan.type1 takes real rows")
+        return self._t1(c, n_modes, modeord, isign)
+
+    def type1_ones(self, n_modes):
+        """F* (cell_scale): with a scale, its raster transform; without one, the outer product of the d one-dimensional sums."""
+        shape = tuple(int(m) for m in n_modes)
+        if self.scale is not None:
+            return self._t1(self.scale, shape, batched=False, scale=False)
+        xc = self.xcen or (0.0,) * self.dim
+        hs = self.h if isinstance(self.h, tuple) else (self.h,) * self.dim
+        sums = [raster_type1([self.axes[a]], hs[a], (shape[a],), torch.ones(self.n_axis[a], dtype=_RD, device=self.dev), xcen=(xc[a],))
+                for a in range(self.dim)]
+        spec = {1: "i->i", 2: "i,j->ij", 3: "i,j,k->ijk"}[self.dim]
+        return torch.einsum(spec, *sums).contiguous()
+
+    def type1_pair(self, y, n_modes_y, n_modes_one):
+        """(F* y on n_modes_y, F* 1 on n_modes_one) as two views of one buffer, like `NufftPlan.type1_pair`."""
+        shape_y, shape_o = tuple(int(m) for m in n_modes_y), tuple(int(m) for m in n_modes_one)
+        My, Mo = math.prod(shape_y), math.prod(shape_o)
+        flat = torch.empty(My + Mo, dtype=_CD, device=self.dev)
+        out_y, out_o = flat[:My].view(shape_y), flat[My:].view(shape_o)
+        self._t1(y, shape_y, batched=False, out=out_y)
+        out_o.copy_(self.type1_ones(shape_o))
+        return out_y, out_o
+
+    def _probe_blocks(self, nbatch):
+        rows = max(2, self.probe_block_bytes // (8 * self.npts) // 2 * 2)         # even: normal rows come in pairs
+        return [(b0, min(int(nbatch), b0 + rows)) for b0 in range(0, int(nbatch), rows)]
+
+    def type1_rademacher(self, seed, nbatch, n_modes, index_offset=0, modeord=0):
+        """F* Z for the rows Z = rademacher_fill(dev, seed, nbatch, ncells, index_offset), indexed by the row-major cell index and
+        materialised a block of rows at a time -> (B, *n_modes).  Cells of scale 0 draw and are dropped."""
+        out = torch.empty((int(nbatch),) + tuple(int(m) for m in n_modes), dtype=_CD, device=self.dev)
+        for b0, b1 in self._probe_blocks(nbatch):
+            z = rademacher_fill(self.dev, seed, b1 - b0, self.npts, _wrap_i64(int(index_offset) + b0 * NORMAL_ROW_STRIDE))
+            self._t1(z, n_modes, modeord, batched=True, out=out[b0:b1])
+        return out
+
+    def type1_normal(self, seed, nbatch, n_modes, index_offset=0, modeord=0):
+        """The same for the rows of normal_fill(dev, seed, nbatch, ncells, index_offset)."""
+        out = torch.empty((int(nbatch),) + tuple(int(m) for m in n_modes), dtype=_CD, device=self.dev)
+        for b0, b1 in self._probe_blocks(nbatch):
+            z = normal_fill(self.dev, seed, b1 - b0, self.npts, normal_row_offset(b0, index_offset))
+            self._t1(z, n_modes, modeord, batched=True, out=out[b0:b1])
+        return out
+
+    def type2(self, f, n_modes, modeord=0, real_only=False, isign=+1, batched=None, mode_scale=None):
+        """f (prod,) | (*n_modes) | (B, ...) complex -> float64 (ncells,) | (B, ncells), cells in row-major order (raster_type2)."""
+        if not real_only:
+            raise NotImplementedError("RasterPlan.type2 returns the real part only (real_only=True): a complex output onto the raster "
+                                      "is not implemented")
+        shape = tuple(int(m) for m in n_modes)
+        if batched is None:
+            batched = not (f.ndim == 1 or tuple(f.shape) == shape)
+        res = raster_type2(self.axes, self.h, shape, f, modeord=modeord, isign=isign, mode_scale=mode_scale, xcen=self.xcen, batched=True)
+        res = res.reshape(res.shape[0], self.npts)
+        return res if batched else res[0]
+
+
 def cheb_interp(nodes_per_axis, weights_per_axis, node_values, x_new, clamp=True):
     """Tensor-product barycentric interpolation (efgp_cheb_interp): `nodes_per_axis` / `weights_per_axis` are d sequences (arrays,
     tensors) of the ascending nodes and their barycentric weights, `node_values` holds prod n_a doubles with the last axis fastest

@@ -32,7 +32,7 @@ from cg import ConjugateGradients
 from kernels.kernel_params import GPParams
 from utils.kernels import get_xis, get_xis_nd
 
-from efgp_hip import NufftPlan, PointSet, ToeplitzOp, lanczos, lag_sums, variance_rhs, variance_contract, cg_solve, cg_solve_lazy, cg_solve_mean_async, cg_solve_mean_fused, vdot_real, compute_device, rademacher_fill, gradient_prepare, gradient_assemble, hermitian_normal_rows, normal_row_offset, spectral_weights_nd, raster_type2
+from efgp_hip import NufftPlan, PointSet, ToeplitzOp, lanczos, lag_sums, variance_rhs, variance_contract, cg_solve, cg_solve_lazy, cg_solve_mean_async, cg_solve_mean_fused, vdot_real, compute_device, rademacher_fill, gradient_prepare, gradient_assemble, hermitian_normal_rows, normal_row_offset, spectral_weights_nd, raster_type2, RasterPlan
 from efgp_hip.dist import PointShards
 from efgp_hip.ops import _per_axis
 
@@ -559,7 +559,7 @@ def efgpnd_gradient_batched(
         probes_Z: Optional[torch.Tensor] = None, probes_V: Optional[torch.Tensor] = None,
         shards: Optional[PointShards] = None, trace_mode: str = "adjoint", probe_seed: Optional[int] = None,
         domain_length: Optional[float] = None, y_norm_sq: Optional[float] = None, points: Optional[PointSet] = None,
-        log_marginal_probe_vectors: Optional[torch.Tensor] = None, pointwise_alpha: bool = False):
+        log_marginal_probe_vectors: Optional[torch.Tensor] = None, pointwise_alpha: bool = False, raster=None):
     """d(negative log marginal likelihood)/d(kernel hypers..., sigma^2) = (term1 - term2)/2 with
     Hutchinson trace estimates (data-space probes Z for non-variance kernel hypers, feature-space
     probes V for the noise) and CG solves.  ``x0, x1`` are ignored as in the reference (:72-73).
@@ -588,6 +588,11 @@ def efgpnd_gradient_batched(
     cancellation: the 6e-8 transform error is amplified by yy / |y - F g|^2 (the reference's pointwise alpha only by the
     square root of that).  For high-SNR data (sigma^2 << signal variance) set it to get alpha = (y - F g)/sigma^2 from ONE
     real type-2 pass and the two N-length reductions of the reference (:163, :170); everything else stays adjoint.
+
+    ``raster`` (set by a gridded model, `EFGPND.from_grid`): ``(axes, mask, n_observed)`` -- the observations lie on the
+    rectilinear raster axes[0] x .. x axes[d-1]; ``x`` is ignored, ``y`` holds the raster's values in row-major order, ``mask``
+    (float64 0/1 of the raster's size, or None) its observed cells.  Every pass over the observations is then an exact
+    `RasterPlan` transform; adjoint estimator only, ``domain_length`` required.
     """
     if trace_mode not in ("adjoint", "reference"):
         raise ValueError(f"trace_mode must be 'adjoint' or 'reference', got {trace_mode!r}")
@@ -658,12 +663,22 @@ def efgpnd_gradient_batched(
         return (g_out, log_marginal) if compute_log_marginal else g_out
 
     # 0) book keeping -------------------------------------------------------------------------
-    dev = compute_device(x, device=device)
+    dev = compute_device(y if raster is not None else x, device=device)
     shards = shards or PointShards(enabled=False)
-    xd = _dev_points(x, dev)
     yd = y.detach().to(device=dev, dtype=torch.float64).contiguous()
-    N_local, d = xd.shape
-    N = int(shards.sum_scalars([N_local], dev)[0]) if shards.active else N_local
+    if raster is not None:
+        if not adjoint or pointwise_alpha:
+            raise NotImplementedError("a gridded model (EFGPND.from_grid) supports the adjoint gradient estimator only: the literal "
+                                      "and pointwise_alpha modes need a complex type-2 transform onto the raster")
+        if shards.active or domain_length is None:
+            raise NotImplementedError("a gridded model (EFGPND.from_grid) runs on one device and passes its domain_length")
+        xd, yd = None, yd.reshape(-1)
+        N_local, d = int(raster[2]), len(raster[0])
+        N = N_local
+    else:
+        xd = _dev_points(x, dev)
+        N_local, d = xd.shape
+        N = int(shards.sum_scalars([N_local], dev)[0]) if shards.active else N_local
     if hasattr(kernel, "ard_kind"):
         L = [float(v) for v in domain_length] if domain_length is not None else _domain_sides(xd, shards)
         L = [v if v > 1e-9 else 1.0 for v in L]
@@ -690,13 +705,13 @@ def efgpnd_gradient_batched(
     # need the caller's nufft_eps (:186-189), i.e. a narrower window: a second plan over the same points (W^d LDS
     # operations per point: 3-D, eps 1e-4 vs 6e-8 is 216 vs 512 per channel).
     tight = min(float(nufft_eps), _CONV_TOL) if nufft_eps else _CONV_TOL
-    if points is not None and (points.x.data_ptr() != xd.data_ptr() or points.npts != N_local):
+    if points is not None and (raster is not None or points.x.data_ptr() != xd.data_ptr() or points.npts != N_local):
         points = None
     # Everything from here to the assembled gradient in ONE library call when the step is the common one (adjoint estimator, built-in
     # kernel, one GPU, generated probes, single-launch solves): the ~15 entry points cost more host time driven from Python than
     # their kernels take on the device (csrc/gradient_step.cpp).  Stage timers then carry the whole call under "4_solve_cg".
     one_call = None
-    if (adjoint and not pointwise_alpha and not shards.active and probes_Z is None and probes_V is None and not do_profiling
+    if (raster is None and adjoint and not pointwise_alpha and not shards.active and probes_Z is None and probes_V is None and not do_profiling
             and not compute_log_marginal and os.environ.get("EFGP_NO_FUSED_GRADIENT") is None and dev.type == "cuda"):
         one_call = _gradient_one_call(kernel, grid, xd, yd, points, sig, N, cg_tol, early_stopping, mean_cg_init,
                                       use_mean_cg_preconditioner, use_trace_cg_preconditioner, tight, nufft_eps, int(trace_samples),
@@ -709,8 +724,11 @@ def efgpnd_gradient_batched(
         for name in ("4_solve_cg", "5_compute_term2", "6_monte_carlo_trace", "7_batch_cg_solve", "7.5_compute_alpha", "8_gradient_calculation"):
             lap(name)
         return finish()
-    plan = NufftPlan(xd, grid.plan_h, tight, points=points)
-    plan_p = plan if (not nufft_eps or float(nufft_eps) <= tight) else NufftPlan(xd, grid.plan_h, float(nufft_eps), points=points)
+    if raster is not None:               # exact transforms: one plan serves the pair and the probes
+        plan = plan_p = RasterPlan(raster[0], grid.plan_h, cell_scale=raster[1], _scale_checked=True)
+    else:
+        plan = NufftPlan(xd, grid.plan_h, tight, points=points)
+        plan_p = plan if (not nufft_eps or float(nufft_eps) <= tight) else NufftPlan(xd, grid.plan_h, float(nufft_eps), points=points)
     lap("2_nufft_setup")
 
     # 3) Toeplitz operator, Jacobi diagonal (F*y rides in the same pass over the points) --------
@@ -1117,6 +1135,28 @@ def _derive_seed(seed: int, stream: int) -> int:
     return z ^ (z >> 31)
 
 
+def _check_axes(axes, d_model, what):
+    """The d_model coordinate vectors of a rectilinear raster as float64 tensors (where the caller has them); ValueError for a
+    wrong count, an axis that is not 1-D or is empty, and non-finite coordinates."""
+    if axes is None:
+        raise ValueError(f"axes must be provided for {what}")
+    if torch.is_tensor(axes) or isinstance(axes, np.ndarray):
+        axes = [axes] if (d_model == 1 and axes.ndim == 1) else list(axes)
+    axes = [torch.as_tensor(a).to(torch.float64) for a in axes]
+    if len(axes) != d_model:
+        raise ValueError(f"{what}: {len(axes)} axes given, the model was built on {d_model} dimensions")
+    for a, ax in enumerate(axes):
+        if ax.ndim != 1:
+            raise ValueError(f"{what}: axes[{a}] must be 1-D (got shape {tuple(ax.shape)})")
+        if ax.numel() == 0:
+            raise ValueError(f"{what}: axes[{a}] is empty")
+    fin = [torch.isfinite(ax).all() for ax in axes]
+    for a, ok in enumerate(torch.stack([f.to(fin[0].device) for f in fin]).tolist()):       # one read-back for all axes
+        if not ok:
+            raise ValueError(f"{what}: axes[{a}] has non-finite coordinates")
+    return axes
+
+
 class EFGPND(nn.Module):
     """Equispaced-Fourier GP regression in d dimensions.
 
@@ -1195,10 +1235,72 @@ class EFGPND(nn.Module):
         self._sample_plan = None
         self._last_sample_stats = {}
         self._nan_scalar = None
+        self._raster = None                      # set by from_grid: the observations lie on a rectilinear raster
         # shard_points: True = torch.distributed default group; an efgp_hip.RcclComm = the library's own RCCL communicator
         sp = self.opts.get("shard_points", False)
         self._shards = PointShards(comm=sp) if (sp is not None and not isinstance(sp, bool)) else PointShards(enabled=bool(sp))
         self._update_param_cache()
+
+    @classmethod
+    def from_grid(cls, axes, Y, kernel, *, mask=None, sigmasq: float = None, eps: float = 1e-2, nufft_eps: float = 1e-4,
+                  opts: Optional[Dict] = None, estimate_params: bool = True):
+        """A model of observations that lie on the rectilinear raster axes[0] x .. x axes[d-1] ("ij" order): `Y` of shape
+        (n_0, .., n_{d-1}), `axes` d one-dimensional coordinate tensors (any spacing, any order; checked as `predict_grid` checks
+        its axes), `mask` a bool tensor of Y's shape, True = observed (None: the finite cells of Y are the observations).
+
+        Such a gridded model never holds the (N, d) coordinate tensor and builds no point layout: every pass over the observations
+        (F* y, the Toeplitz vector, the trace probes, the sampler's noise transform) is an exact separable sum on the raster
+        (`efgp_hip.RasterPlan`: `raster_type1` / `raster_type2`, no spreading window, `nufft_eps` plays no part in them).  `fit`,
+        `predict`, `predict_grid`, `sample_paths`, `sample_paths_grid`, `sample_posterior(method="efgp")`, `compute_gradients`
+        (adjoint estimator), `compute_log_marginal` and `optimize_hyperparameters` work as on a point model;
+        `last_fit_stats["route"]` is "raster".  Refused: opts["shard_points"], the literal and `pointwise_alpha` gradient modes,
+        `sample_posterior(method="dense")`.
+
+        N is the number of observed cells; the domain length (or sides, for an ARD kernel) comes from the axes' extremes; the
+        initial hyper-parameter estimate runs on the coordinates of at most 4096 observed cells taken at a fixed stride."""
+        if opts and opts.get("shard_points", False):
+            raise NotImplementedError("a gridded model (EFGPND.from_grid) does not support opts['shard_points']: the raster is "
+                                      "transformed on one device")
+        Y = torch.as_tensor(Y)
+        if not Y.is_floating_point():
+            Y = Y.to(torch.float64)
+        if Y.ndim < 1 or Y.ndim > 3:
+            raise ValueError(f"from_grid: Y must have 1, 2 or 3 dimensions (got shape {tuple(Y.shape)})")
+        axes = _check_axes(axes, Y.ndim, "from_grid")
+        n_axis = tuple(int(a.numel()) for a in axes)
+        if tuple(Y.shape) != n_axis:
+            raise ValueError(f"from_grid: Y has shape {tuple(Y.shape)}, the axes span {n_axis}")
+        if mask is None:
+            obs = torch.isfinite(Y)
+        else:
+            obs = torch.as_tensor(mask)
+            if obs.dtype != torch.bool or tuple(obs.shape) != n_axis:
+                raise ValueError(f"from_grid: mask must be a bool tensor of Y's shape {n_axis}")
+            obs = obs.to(Y.device)
+            if not bool(torch.isfinite(Y[obs]).all()):
+                raise ValueError("from_grid: Y is not finite in every observed cell")
+        n_obs = int(obs.sum())
+        if n_obs == 0:
+            raise ValueError("from_grid: the raster has no observed cell")
+        # at most 4096 observed cells at a fixed stride through the row-major raster, the stride coprime to the cell count so
+        # that it walks across every axis
+        cells = prod(n_axis)
+        step = -(-cells // 4096)
+        while math.gcd(step, cells) != 1:
+            step += 1
+        idx = torch.arange(0, cells, step, device=Y.device)
+        idx = idx[obs.reshape(-1)[idx]]
+        if idx.numel() == 0:
+            idx = obs.reshape(-1).nonzero().reshape(-1)[:4096]
+        y_sub = Y.reshape(-1)[idx]
+        cols = []
+        for a in reversed(range(len(axes))):
+            cols.append(axes[a].to(device=Y.device, dtype=Y.dtype)[idx % n_axis[a]])
+            idx = idx // n_axis[a]
+        model = cls(torch.stack(cols[::-1], dim=1), y_sub, kernel, sigmasq=sigmasq, eps=eps, nufft_eps=nufft_eps, opts=opts,
+                    estimate_params=estimate_params)
+        model._raster = dict(axes=axes, Y=Y, obs=obs, N=n_obs, n_axis=n_axis)
+        return model
 
     # -- parameter bookkeeping ------------------------------------------------------------------
     def register_optimizer(self, optimizer):
@@ -1273,6 +1375,20 @@ class EFGPND(nn.Module):
 
     # -- device data ------------------------------------------------------------------------------
     def _device_data(self):
+        if self._devdata is None and self._raster is not None:
+            r = self._raster
+            dev = compute_device(r["Y"])
+            ax = [a.to(device=dev, dtype=torch.float64).contiguous() for a in r["axes"]]
+            obs = r["obs"].to(dev)
+            yd = torch.where(obs, r["Y"].detach().to(device=dev, dtype=torch.float64), 0.0).reshape(-1).contiguous()
+            mask = None if r["N"] == obs.numel() else obs.to(torch.float64).reshape(-1).contiguous()
+            sides = torch.stack([a.max() - a.min() for a in ax]).tolist()          # the axes' extremes, one read-back
+            if hasattr(self.kernel, "ard_kind"):
+                L = [v if v > 1e-9 else 1.0 for v in sides]
+            else:
+                L = max(sides) if max(sides) > 1e-9 else 1.0
+            yy = self._shards.sum_scalars([vdot_real(yd, yd)], dev)[0]
+            self._devdata = dict(dev=dev, x=None, y=yd, L=L, N=r["N"], yy=yy, points=None, passes=0, axes=ax, mask=mask)
         if self._devdata is None:
             dev = compute_device(self.x)
             xd = _dev_points(self.x, dev)
@@ -1294,6 +1410,8 @@ class EFGPND(nn.Module):
         (bounding box + key + radix sort + two gathers: 0.5 ms at N = 1e6, 8-13 ms at 1e7), a training loop pays it at its second
         step and streams the sorted copies from then on; True -- from the first pass; False -- never."""
         dd = self._device_data()
+        if self._raster is not None:              # a gridded model has no point layout
+            return None
         want = self.opts.get("point_layout", "auto")
         dd["passes"] += 1
         if want is False or dd["x"].shape[0] == 0 or (want == "auto" and dd["passes"] < 2):
@@ -1320,8 +1438,13 @@ class EFGPND(nn.Module):
         warm = self.opts.get("mean_cg_warm_start", True)
         stats: Dict = {}
         dd = self._device_data()
+        if self._raster is not None:
+            if kwargs.get("trace_mode", "adjoint") != "adjoint" or kwargs.get("pointwise_alpha", False):
+                raise NotImplementedError("a gridded model (EFGPND.from_grid) supports the adjoint gradient estimator only: the "
+                                          "literal and pointwise_alpha modes need a complex type-2 transform onto the raster")
+            kwargs["raster"] = (dd["axes"], dd["mask"], dd["N"])
         res = efgpnd_gradient_batched(
-            dd["x"], dd["y"], sigmasq=self._gp_params.host_pos()[-1], kernel=self.kernel, eps=self.eps,
+            self.x if self._raster is not None else dd["x"], dd["y"], sigmasq=self._gp_params.host_pos()[-1], kernel=self.kernel, eps=self.eps,
             trace_samples=trace_samples, do_profiling=do_profiling, nufft_eps=nufft_eps, cg_tol=cg_tol,
             noise_floor=noise_floor, stats_out=stats,
             mean_cg_init=self._last_gradient_beta if warm else None, mean_cg_init_shape=getattr(self, "_last_gradient_shape", None),
@@ -1357,7 +1480,7 @@ class EFGPND(nn.Module):
             nufft_eps = self.nufft_eps
         dd = self._device_data()
         dev, xd, yd = dd["dev"], dd["x"], dd["y"]
-        d = xd.shape[1]
+        d = xd.shape[1] if self._raster is None else len(dd["axes"])
         sig = self._gp_params.host_pos()[-1]
         rdtype = self.x.dtype
         cdtype = _cmplx(rdtype)
@@ -1371,8 +1494,19 @@ class EFGPND(nn.Module):
                                                         not os.environ.get("EFGP_NO_NATIVE_GRID")) else None
         if bk is None:
             grid.make_weights()
-        plan = NufftPlan(xd, grid.plan_h, min(float(nufft_eps), _CONV_TOL), points=self._layout())
+        if self._raster is not None:            # exact separable sums on the raster: no coordinates, no layout, no window
+            plan = RasterPlan(dd["axes"], grid.plan_h, cell_scale=dd["mask"], _scale_checked=True)
+        else:
+            plan = NufftPlan(xd, grid.plan_h, min(float(nufft_eps), _CONV_TOL), points=self._layout())
         Fy, v = _normal_equations(plan, yd, grid, self._shards)
+        Fy_rhs, rescale = Fy, None
+        if self._raster is not None:
+            # The CG kernels guard <r, z> and <p, A p> with an absolute 1e-16 (as the reference's loop does), which stalls them
+            # near |r| = 1e-8 whatever the tolerance: for data of order one a cg_tolerance below ~1e-9 is never met and the
+            # solve runs to its cap.  beta is linear in y, so the gridded fit solves for 2^k y with |2^k y| near 2^40 and
+            # scales beta back -- both exact -- which makes the tolerance asked for reachable in any units of y.
+            k = max(-900, min(900, 40 - math.frexp(math.sqrt(float(dd["yy"])) or 1.0)[1]))
+            Fy_rhs, rescale = Fy * (2.0 ** k), 2.0 ** -k
         # deferred: on the 48 x 48 Hermitian grids the operator launches nothing; the fused solve makes its spectrum
         toeplitz = ToeplitzND(v, force_pow2=True, defer_spectra=bk is not None)
         use_precond = self.opts.get("mean_cg_preconditioner", True)
@@ -1385,23 +1519,28 @@ class EFGPND(nn.Module):
         if bk is not None:
             (kind, nu, c0), ell, _var = bk
             fused = cg_solve_mean_fused(toeplitz._op, kind, nu, c0, ell, grid.h, grid.mtot, sig,
-                                        _center_value(v) if use_precond else None, Fy, tol, early_stop=True)
+                                        _center_value(v) if use_precond else None, Fy_rhs, tol, early_stop=True)
             if fused is not None:
                 beta_f, grid.ws, iters_f = fused
                 res = (beta_f, iters_f)
         grid.make_weights()                        # no-op when the fused solve made them
         if res is None and not warm:
-            res = cg_solve_mean_async(toeplitz._op, grid.ws, sig, _center_value(v) if use_precond else None, Fy, tol,
+            res = cg_solve_mean_async(toeplitz._op, grid.ws, sig, _center_value(v) if use_precond else None, Fy_rhs, tol,
                                       early_stop=True)
         if res is None:
             # rhs = D F*y (:792) and the Jacobi diagonal (:795-799) in one native launch (four torch launches otherwise, whose first
             # use in a process costs 0.3 s of torch's own lazy kernel loading)
             cidx = _center_flat(v)
-            diag, rhs = gradient_prepare(grid.ws, Fy, v.reshape(-1)[cidx:cidx + 1], sig, want_diag=use_precond)
+            diag, rhs = gradient_prepare(grid.ws, Fy_rhs, v.reshape(-1)[cidx:cidx + 1], sig, want_diag=use_precond)
             b0 = self._beta.detach().to(device=dev, dtype=torch.complex128) if warm else None
+            if warm and rescale is not None:
+                b0 = b0 / rescale
             res = cg_solve_lazy(toeplitz._op, grid.ws, sig, 0, rhs, b0, tol, early_stop=True, diag=diag, batched=False,
                                 hermitian=True)         # 3-D grids: the planes k0 >= 0 only (efgp_cg_solve_hermitian)
         beta, iters = res
+        if rescale is not None:
+            iters.settle()                         # a re-solve writes into the scaled vector: before it is scaled back
+            beta = beta * rescale
         self._beta = beta.to(cdtype) if cdtype != torch.complex128 else beta
         self._xis = (grid, rdtype)                 # the (M, d) node tensor is built when somebody asks for it (property below)
         self._ws = grid.ws.to(cdtype) if cdtype != torch.complex128 else grid.ws
@@ -1413,6 +1552,8 @@ class EFGPND(nn.Module):
             self._last_fit_stats = dict(mean_cg_iters=iters, feature_count=grid.M, hs=grid.hs, shape=grid.shape)
         else:
             self._last_fit_stats = dict(mean_cg_iters=iters, mtot=grid.mtot, feature_count=grid.M, h=grid.h)
+        if self._raster is not None:
+            self._last_fit_stats["route"] = "raster"
         self._fitted = True
         self._update_param_cache()
         # Nothing downstream reads the count before using beta: a solve that may hold a dead system is settled HERE -- last, behind
@@ -1537,7 +1678,10 @@ class EFGPND(nn.Module):
             # replaces _fit_state; what the plan depends on is h)
             tol1 = min(float(self.nufft_eps), _CONV_TOL)
             sp = self._sample_plan
-            if sp is None or sp[0] != (st["plan_h"], tol1) or sp[2] is not points:
+            if self._raster is not None and (sp is None or sp[0] != (st["plan_h"], tol1)):
+                self._sample_plan = sp = ((st["plan_h"], tol1), RasterPlan(self._devdata["axes"], st["plan_h"],
+                                                                          cell_scale=self._devdata["mask"], _scale_checked=True), None)
+            elif sp is None or sp[0] != (st["plan_h"], tol1) or sp[2] is not points:
                 self._sample_plan = sp = ((st["plan_h"], tol1), NufftPlan(self._devdata["x"], st["plan_h"], tol1, points=points), points)
             plan_x = sp[1]
             max_iter = int(self.opts.get("max_cg_iterations", 1000))
@@ -1656,24 +1800,7 @@ class EFGPND(nn.Module):
         count, an axis that is not 1-D or is empty, and non-finite coordinates."""
         if self.opts.get("shard_points", False):
             raise NotImplementedError(f"{what} does not support opts['shard_points']: the raster is evaluated on one device")
-        if axes is None:
-            raise ValueError(f"axes must be provided for {what}")
-        d_model = 1 if self.x.ndim == 1 else self.x.shape[1]
-        if torch.is_tensor(axes) or isinstance(axes, np.ndarray):
-            axes = [axes] if (d_model == 1 and axes.ndim == 1) else list(axes)
-        axes = [torch.as_tensor(a).to(torch.float64) for a in axes]
-        if len(axes) != d_model:
-            raise ValueError(f"{what}: {len(axes)} axes given, the model was built on {d_model} dimensions")
-        for a, ax in enumerate(axes):
-            if ax.ndim != 1:
-                raise ValueError(f"{what}: axes[{a}] must be 1-D (got shape {tuple(ax.shape)})")
-            if ax.numel() == 0:
-                raise ValueError(f"{what}: axes[{a}] is empty")
-        fin = [torch.isfinite(ax).all() for ax in axes]
-        for a, ok in enumerate(torch.stack([f.to(fin[0].device) for f in fin]).tolist()):       # one read-back for all axes
-            if not ok:
-                raise ValueError(f"{what}: axes[{a}] has non-finite coordinates")
-        return axes
+        return _check_axes(axes, 1 if self.x.ndim == 1 else self.x.shape[1], what)
 
     def predict_grid(self, axes, *, return_variance: bool = True, variance_method: str = "stochastic", hutchinson_probes: int = 1_000,
                      variance_probes: Optional[torch.Tensor] = None, force_recompute: bool = False):
@@ -1756,6 +1883,9 @@ class EFGPND(nn.Module):
             return self.sample_paths(x_new, nsamples, seed=seed).T.detach().cpu().numpy()
         if method != "dense":
             raise ValueError(f"unknown sampling method {method!r}: 'dense' or 'efgp'")
+        if self._raster is not None:
+            raise NotImplementedError("a gridded model (EFGPND.from_grid) holds no coordinate tensor for the dense sampler: use "
+                                      "method='efgp'")
         x = _as2d(self.x)
         xn = _as2d(x_new)
         if hasattr(self.kernel, "ard_kind"):            # a function of the coordinate differences, not of the distance

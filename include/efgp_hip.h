@@ -453,6 +453,24 @@ int efgp_raster_type2(int device, int dim, const int64_t* n_modes, const double*
                       double* out /* (nbatch, n_axis...) */, int64_t max_workspace_bytes /* 0: default */, void* stream);
 int efgp_raster_plan(int dim, const int64_t* n_modes, const int64_t* n_axis, int nbatch, int64_t max_workspace_bytes,
                      int64_t* slab_rows_out, int64_t* slabs_out, int64_t* workspace_bytes_out);   /* host only */
+/* The adjoint: type-1 transform from a rectilinear raster (the same axes, mode numbering, modeord and h as efgp_raster_type2) onto
+ * the mode box, exact to rounding:
+ *     out[b, k] = sum_j values[b, j] * cell_scale[j] * exp(isign * 2 pi i * sum_a h[a] * k_a * (axis_a[j_a] - xcen[a]))
+ * values (nbatch, n_axis...) float64; cell_scale (n_axis...) float64, finite and >= 0 (the caller checks), or NULL for 1.  A cell
+ * whose scale is exactly 0 contributes nothing whatever its value holds (NaN and Inf included): a 0/1 mask leaves cells out.  The
+ * last raster axis is contracted first (a real GEMM against the cos and sin tables on the f64 matrix cores), then the leading
+ * axes; the reduction over the leading raster axis is split into partial sums over 16 rows each, added in order.  No atomics: a
+ * call is bitwise repeatable and independent of max_workspace_bytes (0: 256 MiB), under which the leading axis is processed in
+ * slabs of whole 16-row tiles; a cap that cannot hold the tables and one such slab is EFGP_EINVAL (the message names the bytes
+ * needed) before anything is launched.  efgp_raster_type1_plan is the host-side planning alone. */
+int efgp_raster_type1(int device, int dim, const int64_t* n_modes, const double* h /* d, host */,
+                      const double* xcen_host /* d or NULL */, const int64_t* n_axis /* d */,
+                      const double* axes /* device: the d coordinate vectors, concatenated */,
+                      const double* values /* device (nbatch, n_axis...) */, const double* cell_scale /* device (n_axis...) or NULL */,
+                      int nbatch, int isign, int modeord, void* out /* (nbatch, n_modes...) complex128 */,
+                      int64_t max_workspace_bytes /* 0: default */, void* stream);
+int efgp_raster_type1_plan(int dim, const int64_t* n_modes, const int64_t* n_axis, int nbatch, int64_t max_workspace_bytes,
+                           int64_t* slab_rows_out, int64_t* slabs_out, int64_t* workspace_bytes_out);   /* host only */
 /* Rows on the symmetric mode box of nmodes = mtot^d entries (odd; flat index j, the negated frequency at nmodes - 1 - j) for the
  * path sampler, one launch for all rows:
  *     out[s, j] = a * ws[j] * fz[s, j] + b * e[s, j],
