@@ -2,6 +2,7 @@
 // cg_herm48_pairs_kernel (48 x 48, eight waves: the default of a single system).  persistent_cg_launch (cg_persistent.hip) reaches
 // them through herm_launch at the end of this file.
 #include <cstdlib>
+#include <type_traits>
 
 #include "cg_persistent_dev.hpp"
 #include "spectral_weights.hpp"
@@ -39,10 +40,9 @@ constexpr int G_ELEMS = 16 * LDR, T_ELEMS = 32 * LT, Q_ELEMS = kWavesH * 8 * LQ;
 constexpr int kLdsElems = G_ELEMS + T_ELEMS + Q_ELEMS;     // 80.9 KB
 
 // DFT-8 of (a0, a1, 0, 0, 0, 0, a6, a7): the zero-padded first stage (modes 0..15 and -16..-1 of a 64-point line)
-__device__ __forceinline__ void dft8_in4(double2 a0, double2 a1, double2 a6, double2 a7, double2 (&v)[8]) {
-    const double2 ia6 = make_double2(-a6.y, a6.x), ia7 = make_double2(-a7.y, a7.x);
-    const double2 e0 = cadd(a0, a6), e1 = cadd(a0, ia6), e2 = csub(a0, a6), e3 = csub(a0, ia6);
-    const double2 o0 = cadd(a1, a7), o1r = cadd(a1, ia7), o2r = csub(a1, a7), o3r = csub(a1, ia7);
+// its second half: from the first butterflies e = a0 + i^m a6, o = a1 + i^m a7 (m = 0..3) to the outputs
+__device__ __forceinline__ void dft8_in4_tail(double2 e0, double2 e1, double2 e2, double2 e3, double2 o0, double2 o1r, double2 o2r,
+                                              double2 o3r, double2 (&v)[8]) {
     const double hh = 0.70710678118654752440;
     const double2 o1 = make_double2(hh * (o1r.x + o1r.y), hh * (o1r.y - o1r.x));
     const double2 o2 = mul_mi(o2r);
@@ -55,6 +55,10 @@ __device__ __forceinline__ void dft8_in4(double2 a0, double2 a1, double2 a6, dou
     v[6] = csub(e2, o2);
     v[3] = cadd(e3, o3);
     v[7] = csub(e3, o3);
+}
+__device__ __forceinline__ void dft8_in4(double2 a0, double2 a1, double2 a6, double2 a7, double2 (&v)[8]) {
+    const double2 ia6 = make_double2(-a6.y, a6.x), ia7 = make_double2(-a7.y, a7.x);
+    dft8_in4_tail(cadd(a0, a6), cadd(a0, ia6), csub(a0, a6), csub(a0, ia6), cadd(a1, a7), cadd(a1, ia7), csub(a1, a7), csub(a1, ia7), v);
 }
 
 // DFT-8 of which only the outputs 0, 1, 6, 7 are wanted (positions 0..15 and 48..63 of a cropped 64-point line)
@@ -129,6 +133,10 @@ namespace hrow {
 using h64::div_rcp;
 constexpr int KS = 4;                    // vector slots of a row lane
 
+// a Jacobi diagonal is given (as an array, or as the scalar it is made from).  ONE definition for RowLanes::setup and for the host's
+// choice of cg_herm48_pairs_kernel's PRECOND instantiation (herm_launch): the two must not part
+__host__ __device__ __forceinline__ bool has_precond(const Args& a) { return a.diag != nullptr || a.diag_scale != nullptr; }
+
 // the sums over all modes that decide a refusal.  asym: |b[k] - conj b[-k]|^2, against <b,b> (rounding leaves ~1e-32 |b|^2);
 // ws_bad > 0: ws is not real and even
 __device__ __forceinline__ bool refused(double asym, double bb, double ws_bad) { return !(asym <= 1e-16 * bb) || ws_bad != 0.0; }
@@ -192,7 +200,7 @@ struct RowLanes {
         M = a.g.M;
         k0 = k0_;
         base = (int64_t)blockIdx.x * M;
-        precond = a.diag != nullptr || a.diag_scale != nullptr;
+        precond = has_precond(a);
         wgt = k0 == 0 ? 1.0 : 2.0;
         ws_bad = 0.0;
 #pragma unroll
@@ -337,6 +345,15 @@ struct RowLanes {
         const double beta = div_rcp(rzn, rz + 1e-16, rcp_rz);
 #pragma unroll
         for (int s = 0; s < KS; ++s) pv[s] = make_double2(zv[s].x + beta * pv[s].x, zv[s].y + beta * pv[s].y);
+        rz = rzn;
+    }
+    // new_direction with the new p written to p_next while p_cur stays what it was: a caller that alternates two arrays (a loop body
+    // of two iterations) keeps the last direction for a deferred x update without copying it.  The same operations.
+    __device__ __forceinline__ void new_direction_to(const double2 (&zv)[KS], double rzn, double& rz, double rcp_rz,
+                                                     const double2 (&p_cur)[KS], double2 (&p_next)[KS]) const {
+        const double beta = div_rcp(rzn, rz + 1e-16, rcp_rz);
+#pragma unroll
+        for (int s = 0; s < KS; ++s) p_next[s] = make_double2(zv[s].x + beta * p_cur[s].x, zv[s].y + beta * p_cur[s].y);
         rz = rzn;
     }
 
@@ -655,6 +672,65 @@ __device__ __forceinline__ double half_wave_sum(double v) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), 31);
     const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 31);
     return __hiloint2double(hi, lo);
+}
+
+// h64::dft8_in4 of (w[0] u[0], w[1] u[1], 0, 0, 0, 0, w[2] u[2], w[3] u[3]) with the roundings written out.  Each first butterfly
+// adds two products, and which of the two the compiler rounds and which it fuses into the sum is its choice: it fell the other way
+// when u became one of two alternating arrays (cg_herm48_pairs_kernel, round 11).  This is the form the kernels had before: the
+// products of the slots 0 and 1 are rounded and those of the slots 2 and 3 fused in the loop's applications (LOW_ROUNDED), the
+// reverse in the application in front of the loop (A x0 of a warm start).
+template <bool LOW_ROUNDED>
+__device__ __forceinline__ void dft8_in4_ws(const double (&w)[4], const double2 (&u)[4], double2 (&v)[8]) {
+    // r0, r1: the slots whose products are rounded (ra, rb); f0, f1: those whose products are fused (wa ua, wb ub)
+    constexpr int r0 = LOW_ROUNDED ? 0 : 2, r1 = LOW_ROUNDED ? 1 : 3, f0 = LOW_ROUNDED ? 2 : 0, f1 = LOW_ROUNDED ? 3 : 1;
+    double2 e0, e1, e2, e3, o0, o1r, o2r, o3r;
+    const double2 ra = make_double2(__dmul_rn(w[r0], u[r0].x), __dmul_rn(w[r0], u[r0].y));
+    const double2 rb = make_double2(__dmul_rn(w[r1], u[r1].x), __dmul_rn(w[r1], u[r1].y));
+    const double wa = w[f0], wb = w[f1];
+    const double2 ua = u[f0], ub = u[f1];
+    if constexpr (LOW_ROUNDED) {
+        // a0 = ra, a6 = wa ua: a0 + a6, a0 + i a6, a0 - a6, a0 - i a6; the same of a1 = rb, a7 = wb ub
+        e0 = make_double2(fma(wa, ua.x, ra.x), fma(wa, ua.y, ra.y));
+        e1 = make_double2(fma(-wa, ua.y, ra.x), fma(wa, ua.x, ra.y));
+        e2 = make_double2(fma(-wa, ua.x, ra.x), fma(-wa, ua.y, ra.y));
+        e3 = make_double2(fma(wa, ua.y, ra.x), fma(-wa, ua.x, ra.y));
+        o0 = make_double2(fma(wb, ub.x, rb.x), fma(wb, ub.y, rb.y));
+        o1r = make_double2(fma(-wb, ub.y, rb.x), fma(wb, ub.x, rb.y));
+        o2r = make_double2(fma(-wb, ub.x, rb.x), fma(-wb, ub.y, rb.y));
+        o3r = make_double2(fma(wb, ub.y, rb.x), fma(-wb, ub.x, rb.y));
+    } else {
+        // a0 = wa ua, a6 = ra
+        e0 = make_double2(fma(wa, ua.x, ra.x), fma(wa, ua.y, ra.y));
+        e1 = make_double2(fma(wa, ua.x, -ra.y), fma(wa, ua.y, ra.x));
+        e2 = make_double2(fma(wa, ua.x, -ra.x), fma(wa, ua.y, -ra.y));
+        e3 = make_double2(fma(wa, ua.x, ra.y), fma(wa, ua.y, -ra.x));
+        o0 = make_double2(fma(wb, ub.x, rb.x), fma(wb, ub.y, rb.y));
+        o1r = make_double2(fma(wb, ub.x, -rb.y), fma(wb, ub.y, rb.x));
+        o2r = make_double2(fma(wb, ub.x, -rb.x), fma(wb, ub.y, -rb.y));
+        o3r = make_double2(fma(wb, ub.x, rb.y), fma(wb, ub.y, -rb.x));
+    }
+    h64::dft8_in4_tail(e0, e1, e2, e3, o0, o1r, o2r, o3r, v);
+}
+
+// wave_sum of two values at once: the stages of the two chains alternate, so that the moves of one stand where the other waits for
+// its sum.  Each value goes through wave_sum's tree, stage by stage: the same bits.
+__device__ __forceinline__ void wave_sum_pair(double& u, double& v) {
+    EFGP_DPP_ADD(u, 0x111, 0xF);
+    EFGP_DPP_ADD(v, 0x111, 0xF);
+    EFGP_DPP_ADD(u, 0x112, 0xF);
+    EFGP_DPP_ADD(v, 0x112, 0xF);
+    EFGP_DPP_ADD(u, 0x114, 0xF);
+    EFGP_DPP_ADD(v, 0x114, 0xF);
+    EFGP_DPP_ADD(u, 0x118, 0xF);
+    EFGP_DPP_ADD(v, 0x118, 0xF);
+    EFGP_DPP_ADD(u, 0x142, 0xA);
+    EFGP_DPP_ADD(v, 0x142, 0xA);
+    EFGP_DPP_ADD(u, 0x143, 0xC);
+    EFGP_DPP_ADD(v, 0x143, 0xC);
+    const int ulo = __builtin_amdgcn_readlane(__double2loint(u), 63), uhi = __builtin_amdgcn_readlane(__double2hiint(u), 63);
+    const int vlo = __builtin_amdgcn_readlane(__double2loint(v), 63), vhi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
+    u = __hiloint2double(uhi, ulo);
+    v = __hiloint2double(vhi, vlo);
 }
 
 // exchange_6to8 for an iteration that forms <p, A p> ahead of D (cg_herm48_kernel, FREQ_DOT): the sum of `part` over the lanes 0..31
@@ -1323,8 +1399,24 @@ __device__ __forceinline__ void pairs_dense_role(const Args& a, double2* lds2, d
 // Register budget: 512 threads are two waves per SIMD, which an allocation of up to 256 VGPR + AGPR still admits on gfx950
 // (__launch_bounds__(512) is that limit).  The two-row dense lanes are the tight role: 184 registers of coefficients, 48 of G, 8 of
 // accumulators; no role may spill (scratch 0 -- profiles/r9_cg48_lag_pairs_ab.txt records the compiler's figures).
-template <int VARIANT, bool FUSED = false, bool CHAIN_V1 = false>
+//
+// Round 11 (ROW_V1 false, the default; EFGP_CG48_ROW_V1=1 keeps the row role of round 10): the row waves' instruction stream, 607
+// instructions per iteration, loses the 58 that served no operation (profiles/r11_cg48_row_stream.txt).  No floating-point
+// operation and no order changes:
+//   * PRECOND is a template parameter (the host reads it off the arguments as RowLanes::setup does): the uniform branch around
+//     the updates left phi copies of r, z and the partial sums on both of its paths;
+//   * the loop's body is two iterations and p alternates between two arrays: the deferred x update reads the array the iteration
+//     before ran along, so neither the copy of p nor the eight moves at the back edge are needed;
+//   * the sixteen selects that zeroed A u in the slots without a mode are gone: such a slot has ws = 0 and u = 0, and what it
+//     multiplies by that zero is finite once the four scratch entries per line that no stage writes are zeroed (in front of the
+//     loop).  If a solve overflows, a dead slot now carries a NaN into <r,r> where the select carried a zero into a sum that was
+//     not finite either;
+//   * the two wave sums of <r,r> and <r,z> run with their stages interleaved (wave_sum_pair).
+// Where the compiler had a choice between two contractions (the first butterflies of A, ws y + sigma^2 u in D) it chose differently
+// once u was one of two arrays; those roundings are written out in the form round 10 had (dft8_in4_ws, D).
+template <int VARIANT, bool FUSED = false, bool CHAIN_V1 = false, bool ROW_V1 = CHAIN_V1, bool PRECOND = true>
 __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a) {
+    static_assert(ROW_V1 || !CHAIN_V1, "the statements of round 9 come with round 10's loop");
     using namespace h48;
     using h64::dft8_in4;
     using hrow::KS;
@@ -1392,6 +1484,10 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
     const bool (&ok)[KS] = L.ok;
     const double wgt = L.wgt;
     __syncthreads();                                      // the dense lanes have their coefficients: G / Yh / scratch may be written
+    if constexpr (!ROW_V1) {
+        // values 6 and 7 of the writers 6 and 7 of a line's scratch: no stage writes them, and the lanes j >= 6 read them in D
+        if (row_role && j >= 6) xw[6] = xw[7] = make_double2(0.0, 0.0);
+    }
 
 #ifdef EFGP_CG_STAMPS
     long long stamp_prev = (long long)__builtin_readcyclecounter();
@@ -1404,13 +1500,18 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
     // application (D of the next one has not run) and p_prev the vector that application transformed
     [[maybe_unused]] bool owed = false;
     [[maybe_unused]] double2 p_prev[KS];
-    auto apply_A = [&](const double2 (&u)[KS], double2 (&Au)[KS]) __attribute__((always_inline)) {
+    // prev: the vector of the last completed application, for the x update that is owed (DEFER_X)
+    // first: the application in front of the loop
+    auto apply_A = [&](const double2 (&u)[KS], double2 (&Au)[KS], const double2 (&prev)[KS], auto first) __attribute__((always_inline)) {
         double2 v[8], u6[6];
         EFGP_STAMP(7);
         // A ("6x8"): rows k0 >= 0, modes k1 wrapped to positions k1 mod 48 -> G[k0][f1]
         if (row_role) {
-            dft8_in4(make_double2(wsr[0] * u[0].x, wsr[0] * u[0].y), make_double2(wsr[1] * u[1].x, wsr[1] * u[1].y),
-                     make_double2(wsr[2] * u[2].x, wsr[2] * u[2].y), make_double2(wsr[3] * u[3].x, wsr[3] * u[3].y), v);
+            if constexpr (ROW_V1)
+                dft8_in4(make_double2(wsr[0] * u[0].x, wsr[0] * u[0].y), make_double2(wsr[1] * u[1].x, wsr[1] * u[1].y),
+                         make_double2(wsr[2] * u[2].x, wsr[2] * u[2].y), make_double2(wsr[3] * u[3].x, wsr[3] * u[3].y), v);
+            else
+                dft8_in4_ws<!decltype(first)::value>(wsr, u, v);          // the same roundings, written out
             // u6[k2] = G[k0][j + 8 k2], and the lane's share of the sigma^2 <u,u> of <u, A u> (the slots without a mode hold zeros)
             const double uu = exchange_8to6_norm(v, u6, j < 6, xw, xr, twr, u, VARIANT == 0 ? wgt * a.sigmasq : wgt);
             double2* g0 = Gb + k0 * LDR + j;
@@ -1425,14 +1526,16 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
         EFGP_STAMP(0);
         if constexpr (DEFER_X) {
             // the row waves wait here for the dense waves: the x update of the last iteration, and the copy of u for the next one
-            if (owed) L.update_x(alpha_fd, p_prev);
+            if (owed) L.update_x(alpha_fd, prev);
             owed = false;
             // (moves written out: a plain assignment is a renaming to the compiler, and the moves it then needs at the loop's back
             // edge stand behind D, on the chain)
+            if constexpr (ROW_V1) {
 #pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                asm volatile("v_mov_b64 %0, %1" : "=v"(p_prev[s].x) : "v"(u[s].x));
-                asm volatile("v_mov_b64 %0, %1" : "=v"(p_prev[s].y) : "v"(u[s].y));
+                for (int s = 0; s < KS; ++s) {
+                    asm volatile("v_mov_b64 %0, %1" : "=v"(p_prev[s].x) : "v"(u[s].x));
+                    asm volatile("v_mov_b64 %0, %1" : "=v"(p_prev[s].y) : "v"(u[s].y));
+                }
             }
         }
         __syncthreads();                                  // barrier 2: the dense waves' products (pairs_dense_role stamps them)
@@ -1465,7 +1568,12 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
                 if (VARIANT == 0) val = make_double2(gg.x + a.sigmasq * u[s].x, gg.y + a.sigmasq * u[s].y);
                 else val = make_double2(gg.x / a.sigmasq + u[s].x, gg.y / a.sigmasq + u[s].y);
                 // the lanes j >= 6 of a line only lend their radix-6 stages: what they read in the radix-8 stage is stale scratch
-                Au[s] = ok[s] ? val : make_double2(0.0, 0.0);
+                // Without the select the compiler is free to contract the other product of VARIANT 0's sum (ws y rounded and
+                // sigma^2 u fused, or the reverse); the roundings are written out as the select's form has them
+                if constexpr (!ROW_V1 && VARIANT == 0)
+                    Au[s] = make_double2(fma(a.sigmasq, u[s].x, __dmul_rn(wsr[s], y[s].x)), fma(a.sigmasq, u[s].y, __dmul_rn(wsr[s], y[s].y)));
+                else if constexpr (!ROW_V1) Au[s] = val;
+                else Au[s] = ok[s] ? val : make_double2(0.0, 0.0);
             }
         } else {
             alpha_fd = 0.0;                               // these lanes hold no modes: their vectors are zero and stay zero
@@ -1480,7 +1588,7 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
 #pragma unroll
         for (int s = 0; s < KS; ++s) Ap[s] = make_double2(0.0, 0.0);
     } else {
-        apply_A(L.xv, Ap);
+        apply_A(L.xv, Ap, p_prev, std::true_type{});
     }
     double bb, asym;
     if constexpr (EARLY) L.template start<true>(a, Ap, rz, bb, asym, &early);
@@ -1505,8 +1613,47 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
         return;
     }
     int it = 0;
+    if constexpr (!ROW_V1) {
+        double2 p_alt[KS];
+#pragma unroll
+        for (int s = 0; s < KS; ++s) p_alt[s] = make_double2(0.0, 0.0);
+        // one iteration along pc; the next direction goes to pn, which held the direction before pc.  false: "stop"
+        auto half = [&](const double2 (&pc)[KS], double2 (&pn)[KS]) __attribute__((always_inline)) -> bool {
+            apply_A(pc, Ap, pn, std::false_type{});
+            if (stop) return false;
+            double rr, rzn;
+            double2 zv[KS];
+            L.template step_<PRECOND, false>(alpha_fd, Ap, zv, rr, rzn);
+            owed = true;
+            EFGP_STAMP(4);
+            wave_sum_pair(rr, rzn);
+            if (lane == 0) {
+                red[wave] = rr;
+                red[2 + wave] = rzn;
+            }
+            __syncthreads();                              // barrier 3
+            rzn = red[2] + red[3];
+            EFGP_STAMP(5);
+            ++it;
+            L.new_direction_to(zv, rzn, rz, rcp_rz, pc, pn);
+            return true;
+        };
+        bool owed_alt = false;
+        // the loop's body is two iterations, so that the two arrays swap their names instead of their contents.  owed_alt: the last
+        // completed iteration ran along p_alt
+        for (;;) {
+            owed_alt = true;
+            if (it >= a.max_iter || !half(L.pv, p_alt)) break;
+            owed_alt = false;
+            if (it >= a.max_iter || !half(p_alt, L.pv)) break;
+        }
+        // the update of the last completed iteration: the loop ended at max_iter, or on "stop" behind barrier 1, in front of D
+        if (owed) L.update_x(alpha_fd, owed_alt ? p_alt : L.pv);
+        L.write_out(a, it);
+        return;
+    }
     for (; it < a.max_iter;) {
-        apply_A(L.pv, Ap);
+        apply_A(L.pv, Ap, p_prev, std::false_type{});
         if (stop) break;
         double rr, rzn;
         double2 zv[KS];
@@ -1572,19 +1719,34 @@ PickLaunch herm_launch(const PersistentChoice& c, int variant, const Herm48Opera
     // EFGP_CG48_CHAIN_V1=1 (read per call): the eight-wave kernel with the x update inside the iteration's chain and the row lanes'
     // loads behind the prologue (round 9) instead of off the chain (round 10); equal bits
     const bool chain_v1 = std::getenv("EFGP_CG48_CHAIN_V1") != nullptr;
+    // EFGP_CG48_ROW_V1=1 (read per call): the row role's loop of round 10 (one iteration per pass, a copy of p, the preconditioner's
+    // branch and the selects inside it) instead of round 11's; equal bits.  EFGP_CG48_CHAIN_V1=1 implies it.
+    // The default arm has the preconditioner's choice as a template parameter (RowLanes::setup's `precond`).
+    const int arm = chain_v1 ? 3 : (std::getenv("EFGP_CG48_ROW_V1") != nullptr ? 2 : (hrow::has_precond(a) ? 0 : 1));
+    // the launch's label names the arm (efgp_cg_last_launch reports it: the tests of the switches read it)
+    static const char* const fused8[4] = {"fused mean solve (48x48, eight waves)", "fused mean solve (48x48, eight waves, no diagonal)",
+                                          "fused mean solve (48x48, eight waves, row role of round 10)",
+                                          "fused mean solve (48x48, eight waves, round 9)"};
+    static const char* const herm8[4] = {"persistent CG (48x48, Hermitian, eight waves)", "persistent CG (48x48, Hermitian, eight waves, no diagonal)",
+                                         "persistent CG (48x48, Hermitian, eight waves, row role of round 10)",
+                                         "persistent CG (48x48, Hermitian, eight waves, round 9)"};
     switch (c.pick) {
         case PersistentPick::fused48: {
-            if (pairs)
-                return {chain_v1 ? cg_herm48_pairs_kernel<0, true, true> : cg_herm48_pairs_kernel<0, true>, h48::kThreadsP, lds48p,
-                        "fused mean solve (48x48, eight waves)"};
+            if (pairs) {
+                void (*const eight[4])(Args) = {cg_herm48_pairs_kernel<0, true>, cg_herm48_pairs_kernel<0, true, false, false, false>,
+                                                cg_herm48_pairs_kernel<0, true, false, true>, cg_herm48_pairs_kernel<0, true, true>};
+                return {eight[arm], h48::kThreadsP, lds48p, fused8[arm]};
+            }
             void (*const dense[2])(Args) = {cg_herm48_kernel<0, true, true, false>, cg_herm48_kernel<0, true, true, true>};
             return {c.dense48 ? dense[freq_dot] : cg_herm48_kernel<0, true, false>, h48::kThreadsH, lds48d, "fused mean solve (48x48)"};
         }
         case PersistentPick::herm48: {
             if (pairs) {
-                void (*const eight[2][2])(Args) = {{cg_herm48_pairs_kernel<0>, cg_herm48_pairs_kernel<1>},
+                void (*const eight[4][2])(Args) = {{cg_herm48_pairs_kernel<0>, cg_herm48_pairs_kernel<1>},
+                                                   {cg_herm48_pairs_kernel<0, false, false, false, false>, cg_herm48_pairs_kernel<1, false, false, false, false>},
+                                                   {cg_herm48_pairs_kernel<0, false, false, true>, cg_herm48_pairs_kernel<1, false, false, true>},
                                                    {cg_herm48_pairs_kernel<0, false, true>, cg_herm48_pairs_kernel<1, false, true>}};
-                return {eight[chain_v1][variant != 0], h48::kThreadsP, lds48p, "persistent CG (48x48, Hermitian, eight waves)"};
+                return {eight[arm][variant != 0], h48::kThreadsP, lds48p, herm8[arm]};
             }
             void (*const dense[2][2])(Args) = {{cg_herm48_kernel<0, false, true, false>, cg_herm48_kernel<1, false, true, false>},
                                                {cg_herm48_kernel<0, false, true, true>, cg_herm48_kernel<1, false, true, true>}};

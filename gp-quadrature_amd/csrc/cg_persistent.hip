@@ -1199,6 +1199,7 @@ namespace pcg {
 #ifdef EFGP_CG_STAMPS
 static long long* g_last_stamps = nullptr;
 #endif
+static const char* g_last_launch = "";       // label of the last single-launch solve that was enqueued (efgp_cg_last_launch)
 
 static void radices_for(int n, Pass* p) {
     int k = 0;
@@ -1218,6 +1219,8 @@ static void radices_for(int n, Pass* p) {
 }
 
 }  // namespace pcg
+
+extern "C" const char* efgp_cg_last_launch(void) { return pcg::g_last_launch; }
 
 #ifdef EFGP_CG_STAMPS
 extern "C" int efgp_debug_cg_stamps(long long* out16) {
@@ -1447,6 +1450,7 @@ int persistent_cg_launch(const ToepGeom& full, const double2* const* tw_full, co
     if (const int rc = pick_persistent(full, s, h48 != nullptr && h48->vhat != nullptr, lz != nullptr, fuse != nullptr, &c)) return rc;
     const bool herm = c.pick == PersistentPick::fused48 || c.pick == PersistentPick::herm48 || c.pick == PersistentPick::herm64;
     const PickLaunch l = herm ? herm_launch(c, s.variant, h48, fuse, a) : launch_of(c, a.g);
+    g_last_launch = l.what;
     if (const int rc = raise_dynamic_lds((const void*)l.kernel, l.lds, l.what)) return rc;
     {
         KernelTimer timer("cg_solve", stream);

@@ -71,6 +71,7 @@ _SIGNATURES = {
     "efgp_toeplitz_fft_shape": (_I, [_VP, _PI64]),
     "efgp_toeplitz_cg_shape": (_I, [_VP, _I, _PI64]),
     "efgp_toeplitz_single_launch_solves": (_I, [_VP]),
+    "efgp_cg_last_launch": (C.c_char_p, []),
     "efgp_cg_solve": (_I, [_VP, _VP, _D, _I, _VP, _VP, _VP, _I, _D, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _VP]),
     "efgp_fft_c2c": (_I, [_I, _I, C.POINTER(C.c_longlong), C.c_longlong, _VP, _I, _I, _VP]),
     "efgp_cg_solve_hermitian": (_I, [_VP, _VP, _D, _I, _VP, _VP, _VP, _I, _D, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _VP]),

@@ -221,6 +221,10 @@ int efgp_toeplitz_cg_shape(efgp_toeplitz_t* op, int hermitian, int64_t* shape_ou
 /* 1 when every fused solve on this operator is ONE asynchronous launch with no grid barrier (the persistent kernels: circulant
  * grid within one workgroup), 0 otherwise (cooperative / multi-launch iterations, whose callers read row counts back). */
 int efgp_toeplitz_single_launch_solves(efgp_toeplitz_t* op);
+/* Label of the kernel the last single-launch solve enqueued ("" before the first): a static string that names the solve route and,
+ * where an environment switch selects another instantiation of it, the arm.  For tests and tools that must know that a switch
+ * reached the launch. */
+const char* efgp_cg_last_launch(void);
 
 /* ---- preconditioned CG on G = D T D: replaces cg.py ConjugateGradients.solve() for the operators
  * of efgpnd.py:1572-1631 --------------------------------------------------------------------------

@@ -1,0 +1,202 @@
+#!/usr/bin/env python3
+"""Instruction budget of the row role's loop in cg_herm48_pairs_kernel (csrc/cg_herm.hip), from the gfx950 assembly.
+
+    hipcc -O3 -std=c++17 --offload-arch=gfx950 -munsafe-fp-atomics --cuda-device-only -S -x hip csrc/cg_herm.hip -o cg_herm.s
+    python tools/cg48_row_stream.py cg_herm.s '<0, true, false, false, true>' --list
+    python tools/cg48_row_stream.py cg_herm.s '<0, true, false, false, true>' --start LBB0_227 --avoid LBB0_225,bb.233,...
+
+(the block labels belong to one compile: --list prints this build's; profiles/r11_cg48_row_stream.txt records the tables of round 10
+and round 11 with the labels that were used.)  The tool finds the kernel whose demangled template arguments are given, takes the loop that holds the wave sums (DPP row moves)
+and three or six workgroup barriers, and WALKS the path a row wave executes in an iteration of the preconditioned solve: it starts
+at --start, falls through, takes every unconditional branch, takes `execnz` and leaves `execz` branches (the row lanes are active),
+takes a conditional branch when the block behind it is in --avoid and leaves it when its target is in --avoid or outside the loop,
+and stops when it is back at --start.  --avoid names the blocks of the other paths (the "stop" exit, the solve without a
+preconditioner, the first application of a warm start): read them off the listing once per build (--list prints the blocks with
+their branches).  Instructions are counted by class and by the phase they stand in:
+
+    A           from the start of the row transforms to barrier 1 (the loop's first s_and_saveexec opens it)
+    gap         barrier 1 to barrier 2: stop flag, the deferred x update, the copy of p, zeros of the lanes without modes
+    D           barrier 2 to the end of the exec-masked block behind it
+    updates     to the first DPP move behind D
+    sums        the wave sums, to barrier 3
+    beta / p    barrier 3 to the next s_and_saveexec (the next A) or the back edge
+A body of two iterations is reported per iteration (counts halved).  The phases follow the instructions' positions, so work the
+scheduler moved across a marker is counted where it stands.
+"""
+import argparse
+import re
+from collections import Counter, OrderedDict
+
+CLASSES = ["fma f64", "mul f64", "add f64", "other f64", "ds_read", "ds_write", "s_barrier", "v_mov_b64", "v_mov_b32", "dpp move",
+           "v_cndmask", "v_readlane", "other VALU", "s_waitcnt", "s_nop", "branch", "other SALU"]
+PHASES = ["A", "gap", "D", "updates", "sums", "beta / p"]
+
+
+def classify(ins):
+    op = ins.split()[0]
+    if "dpp" in op or "row_shr" in ins or "row_bcast" in ins:
+        return "dpp move"
+    if op.startswith(("v_fma_f64", "v_fmac_f64")):
+        return "fma f64"
+    if op.startswith("v_mul_f64"):
+        return "mul f64"
+    if op.startswith("v_add_f64"):
+        return "add f64"
+    if op.endswith("_f64") or "_f64_" in op:
+        return "other f64"
+    if op.startswith("ds_read"):
+        return "ds_read"
+    if op.startswith("ds_write"):
+        return "ds_write"
+    if op == "s_barrier":
+        return "s_barrier"
+    if op.startswith("v_mov_b64"):
+        return "v_mov_b64"
+    if op.startswith("v_mov_b32"):
+        return "v_mov_b32"
+    if op.startswith("v_cndmask"):
+        return "v_cndmask"
+    if op.startswith("v_readlane") or op.startswith("v_readfirstlane"):
+        return "v_readlane"
+    if op.startswith("v_"):
+        return "other VALU"
+    if op == "s_waitcnt":
+        return "s_waitcnt"
+    if op == "s_nop":
+        return "s_nop"
+    if op.startswith(("s_cbranch", "s_branch")):
+        return "branch"
+    return "other SALU"
+
+
+def kernel_body(lines, targs):
+    want = re.sub(r"\s", "", targs)
+    for i, l in enumerate(lines):
+        m = re.match(r"^(_ZN4efgp3pcg22cg_herm48_pairs_kernelI(\w+?)EEvNS0_4ArgsE):", l)
+        if not m:
+            continue
+        args = re.findall(r"L[ib](\d)", m.group(2))
+        text = "<" + ",".join([args[0]] + ["true" if x == "1" else "false" for x in args[1:]]) + ">"
+        if text == want:
+            end = next(k for k in range(i, len(lines)) if lines[k].startswith("\t.size\t" + m.group(1)))
+            return lines[i:end]
+    raise SystemExit("no cg_herm48_pairs_kernel" + targs + " in the file")
+
+
+def row_loop(body):
+    labels = {m.group(1): i for i, l in enumerate(body) for m in [re.match(r"^\.(LBB\d+_\d+):", l)] if m}
+    spans = []
+    for i, l in enumerate(body):
+        m = re.match(r"^\s+s_c?branch\S*\s+\.(LBB\d+_\d+)", l)
+        if m and labels.get(m.group(1), 1 << 30) < i:
+            seg = body[labels[m.group(1)]:i + 1]
+            nb = sum(1 for x in seg if re.match(r"^\s+s_barrier", x))
+            if nb in (3, 6) and any("row_bcast" in x for x in seg):
+                spans.append((labels[m.group(1)], i))
+    if not spans:
+        raise SystemExit("no loop with wave sums and three or six barriers")
+    return body[min(s[0] for s in spans):max(s[1] for s in spans) + 1]
+
+
+def blocks_of(loop):
+    """ordered name -> instructions; a block starts at a label or at a '; %bb.N:' comment"""
+    blocks = OrderedDict()
+    cur = None
+    for l in loop:
+        m = re.match(r"^\.(LBB\d+_\d+):", l) or re.match(r"^; %(bb\.\d+):", l)
+        if m:
+            cur = m.group(1)
+            blocks[cur] = []
+        elif cur is not None and re.match(r"^\s+[a-z]", l) and not l.strip().startswith(";"):
+            blocks[cur].append(re.sub(r"\s*;.*$", "", l.strip()))
+    return blocks
+
+
+def walk(blocks, start, avoid):
+    names = list(blocks)
+    path, cur, seen_start = [], start, 0
+    for _ in range(10000):
+        if cur == start:
+            seen_start += 1
+            if seen_start == 2:
+                return path
+        nxt = names[names.index(cur) + 1] if names.index(cur) + 1 < len(names) else None
+        jumped = False
+        for ins in blocks[cur]:
+            path.append(ins)
+            m = re.match(r"(s_c?branch\S*)\s+\.(LBB\d+_\d+)", ins)
+            if not m:
+                continue
+            op, tgt = m.groups()
+            if tgt not in blocks or tgt in avoid:
+                take = False
+            elif op == "s_branch" or op.endswith("execnz") or nxt in avoid:
+                take = True
+            else:
+                take = False
+            if take:
+                cur, jumped = tgt, True
+                break
+        if not jumped:
+            if nxt is None or nxt in avoid:
+                raise SystemExit("the walk falls into " + str(nxt) + " behind " + cur)
+            cur = nxt
+    raise SystemExit("the walk does not come back to " + start)
+
+
+def phases(path):
+    out, phase, after_d = [], "A", False
+    nbar = 0
+    for ins in path:
+        op = ins.split()[0]
+        if phase == "beta / p" and op.startswith("s_and_saveexec"):
+            phase = "A"
+        if phase == "D" and op == "s_or_b64" and "exec" in ins.split()[1]:
+            out.append((phase, ins))
+            phase = "updates"
+            continue
+        if phase == "updates" and ("row_shr" in ins or "row_bcast" in ins):
+            phase = "sums"
+        out.append((phase, ins))
+        if op == "s_barrier":
+            nbar += 1
+            phase = {1: "gap", 2: "D", 0: "beta / p"}[nbar % 3]
+    return out, nbar
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("asm")
+    ap.add_argument("targs", help="the kernel's template arguments as the demangler prints them, e.g. '<0, true, false>'")
+    ap.add_argument("--start", help="label of the block that opens A, e.g. LBB1_225")
+    ap.add_argument("--avoid", default="", help="blocks off the steady path, comma separated (LBB1_230, bb.229)")
+    ap.add_argument("--list", action="store_true", help="print the loop's blocks with their sizes and branches")
+    ap.add_argument("--dump", help="write the walked path to this file")
+    a = ap.parse_args()
+    loop = row_loop(kernel_body(open(a.asm).read().split("\n"), a.targs))
+    blocks = blocks_of(loop)
+    if a.list or not a.start:
+        for n, b in blocks.items():
+            print(f"{n:12s} {len(b):4d}  " + "  ".join(i for i in b if i.startswith(("s_cbranch", "s_branch", "s_barrier"))))
+        return
+    path = walk(blocks, a.start, set(x for x in a.avoid.split(",") if x))
+    tagged, nbar = phases(path)
+    per = nbar // 3
+    tab = {p: Counter() for p in PHASES}
+    for p, ins in tagged:
+        tab[p][classify(ins)] += 1
+    print(f"static loop: {sum(len(b) for b in blocks.values())} instructions; walked path: {len(path)} instructions, {nbar} barriers"
+          f" = {per} iteration(s); per iteration:")
+    print(f"{'class':12s}" + "".join(f"{p:>10s}" for p in PHASES) + f"{'total':>10s}")
+    for c in CLASSES:
+        row = [tab[p][c] / per for p in PHASES]
+        if sum(row):
+            print(f"{c:12s}" + "".join(f"{v:10g}" for v in row) + f"{sum(row):10g}")
+    tot = [sum(tab[p].values()) / per for p in PHASES]
+    print(f"{'all':12s}" + "".join(f"{v:10g}" for v in tot) + f"{sum(tot):10g}")
+    if a.dump:
+        open(a.dump, "w").write("\n".join(f"{p:9s} {i}" for p, i in tagged) + "\n")
+
+
+if __name__ == "__main__":
+    main()
