@@ -611,6 +611,10 @@ static_assert(2 * G_ELEMS + NR * LX <= kLdsElemsDense, "the iteration's G, Yh an
 constexpr int kThreadsP = 512, kRowWavesP = 2, kPairWavesP = 3;
 constexpr int NDP = kThreadsP - 64 * kRowWavesP;       // dense lanes: 48 frequencies x 8 groups
 static_assert(NDP == 8 * F && 64 * kPairWavesP == 4 * F, "no wave mixes two-row and one-row groups");
+// the one-row dense wave that sums <u, A u> and forms the step length between barriers 2 and 2b (round 12): the duty wave.  Waves
+// 5, 6 and 7 measure alike (profiles/r12_cg48_alpha_wave.txt); the duty wave reads <r,z> behind barrier 3 anyway
+constexpr int kAlphaWaveP = 7;
+static_assert(kAlphaWaveP >= kRowWavesP + kPairWavesP && kAlphaWaveP < kThreadsP / 64, "a wave of the one-row dense role");
 constexpr int kLdsElemsPairs = F * LDV + (kThreadsP / 8) * LX;      // the prologue's grid + 64 line slots: 111 KB
 
 // "6x8", second half: the lanes j < 6 of a line hand their eight first-stage outputs over (scratch [writer][value], pitch 9);
@@ -626,6 +630,14 @@ __device__ __forceinline__ void exchange_8to6(const double2 (&v)[8], double2 (&u
 #pragma unroll
     for (int t = 1; t < 6; ++t) u[t] = cmulp(u[t], tw[t - 1]);
     dft6(u);
+}
+// a row lane's share of <x, x>: scale * sum |x[s]|^2 over its four slots.  The statements of exchange_8to6_norm below, for a caller
+// that forms the share outside the exchange (cg_herm48_pairs_kernel with ALPHA_WAVE).  A copy, not a call from there: calling it
+// from exchange_8to6_norm reorders the assembly of every kernel that uses the exchange (profiles/r12_cg48_alpha_wave.txt)
+__device__ __forceinline__ double norm_share(const double2 (&x)[4], double scale) {
+    const double x01 = fma(x[0].x, x[0].x, x[0].y * x[0].y) + fma(x[1].x, x[1].x, x[1].y * x[1].y);
+    const double x23 = fma(x[2].x, x[2].x, x[2].y * x[2].y) + fma(x[3].x, x[3].x, x[3].y * x[3].y);
+    return scale * (x01 + x23);
 }
 // exchange_8to6 for an iteration that forms <p, A p> ahead of D (cg_herm48_kernel, FREQ_DOT): the lane's share of <x, x>,
 // scale * sum |x[s]|^2, is issued behind the six reads, while they are under way.
@@ -673,13 +685,35 @@ __device__ __forceinline__ double half_wave_sum(double v) {
     const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 31);
     return __hiloint2double(hi, lo);
 }
+// num / (sum of `part` over the lanes 0..31 + 1e-16): the step length of an iteration that forms <p, A p> ahead of D
+__device__ __forceinline__ double quot_half_wave(double part, double num) { return num / (half_wave_sum(part) + 1e-16); }
 
 // h64::dft8_in4 of (w[0] u[0], w[1] u[1], 0, 0, 0, 0, w[2] u[2], w[3] u[3]) with the roundings written out.  Each first butterfly
 // adds two products, and which of the two the compiler rounds and which it fuses into the sum is its choice: it fell the other way
 // when u became one of two alternating arrays (cg_herm48_pairs_kernel, round 11).  This is the form the kernels had before: the
 // products of the slots 0 and 1 are rounded and those of the slots 2 and 3 fused in the loop's applications (LOW_ROUNDED), the
 // reverse in the application in front of the loop (A x0 of a warm start).
-template <bool LOW_ROUNDED>
+// The odd outputs of the tail, e + hh t and e - hh t, are one fused multiply-add each where the whole tail stands in the writers'
+// block; when the compiler leaves half of it in front of that block (cg_herm48_pairs_kernel with ALPHA_WAVE, round 12) the product
+// hh t is rounded for the outputs behind the branch.  h64::dft8_in4_tail with those eight roundings written out as every kernel
+// had them.
+__device__ __forceinline__ void dft8_in4_tail_fused(double2 e0, double2 e1, double2 e2, double2 e3, double2 o0, double2 o1r, double2 o2r,
+                                                    double2 o3r, double2 (&v)[8]) {
+    const double hh = 0.70710678118654752440;
+    const double s1 = o1r.x + o1r.y, d1 = o1r.y - o1r.x, s3 = o3r.x + o3r.y, d3 = o3r.y - o3r.x;
+    const double2 o2 = mul_mi(o2r);
+    v[0] = cadd(e0, o0);
+    v[4] = csub(e0, o0);
+    v[1] = make_double2(fma(hh, s1, e1.x), fma(hh, d1, e1.y));
+    v[5] = make_double2(fma(-hh, s1, e1.x), fma(-hh, d1, e1.y));
+    v[2] = cadd(e2, o2);
+    v[6] = csub(e2, o2);
+    v[3] = make_double2(fma(hh, d3, e3.x), fma(-hh, s3, e3.y));
+    v[7] = make_double2(fma(-hh, d3, e3.x), fma(hh, s3, e3.y));
+}
+
+// FUSED_TAIL: the tail's roundings written out as well (dft8_in4_tail_fused).
+template <bool LOW_ROUNDED, bool FUSED_TAIL = false>
 __device__ __forceinline__ void dft8_in4_ws(const double (&w)[4], const double2 (&u)[4], double2 (&v)[8]) {
     // r0, r1: the slots whose products are rounded (ra, rb); f0, f1: those whose products are fused (wa ua, wb ub)
     constexpr int r0 = LOW_ROUNDED ? 0 : 2, r1 = LOW_ROUNDED ? 1 : 3, f0 = LOW_ROUNDED ? 2 : 0, f1 = LOW_ROUNDED ? 3 : 1;
@@ -709,7 +743,8 @@ __device__ __forceinline__ void dft8_in4_ws(const double (&w)[4], const double2 
         o2r = make_double2(fma(wb, ub.x, -rb.x), fma(wb, ub.y, -rb.y));
         o3r = make_double2(fma(wb, ub.x, rb.y), fma(wb, ub.y, -rb.x));
     }
-    h64::dft8_in4_tail(e0, e1, e2, e3, o0, o1r, o2r, o3r, v);
+    if constexpr (FUSED_TAIL) dft8_in4_tail_fused(e0, e1, e2, e3, o0, o1r, o2r, o3r, v);
+    else h64::dft8_in4_tail(e0, e1, e2, e3, o0, o1r, o2r, o3r, v);
 }
 
 // wave_sum of two values at once: the stages of the two chains alternate, so that the moves of one stand where the other waits for
@@ -746,10 +781,26 @@ __device__ __forceinline__ double exchange_6to8_quot(double2 (&u)[6], double2 (&
     wave_sync();
     s64::load8_all<9>(rd, v);
     __builtin_amdgcn_sched_barrier(0);
-    const double quot = num / (half_wave_sum(part) + 1e-16);
+    const double quot = quot_half_wave(part, num);
     __builtin_amdgcn_sched_barrier(0);
     h64::dft8_out4(v);
     return quot;
+}
+
+// <u, A u> of the eight-wave kernel from the 480 summands in s_part (cg_herm48_pairs_kernel): fifteen per lane, lane l of a wave
+// takes the entries l mod 32 + 32 t -- twelve Toeplitz terms of the dense lanes and three of the row lanes' shares of sigma^2 <u,u>
+// -- then quot_half_wave over the lanes 0..31.  ONE definition of the reads and of the tree for the row lanes (the ALPHA_WAVE false
+// arms) and for the dense wave that sums beside D (ALPHA_WAVE): the arms are compared bit for bit.
+__device__ __forceinline__ void uAu_summands(const double* s_part, int lane, double (&pt)[15]) {
+    const double* sp = s_part + (lane & 31);
+#pragma unroll
+    for (int t = 0; t < 15; ++t) pt[t] = sp[32 * t];
+}
+template <int VARIANT>
+__device__ __forceinline__ double uAu_of_lane(const double (&pt)[15], double sigmasq) {
+    double tsum = (((pt[0] + pt[1]) + (pt[2] + pt[3])) + ((pt[4] + pt[5]) + (pt[6] + pt[7]))) + ((pt[8] + pt[9]) + (pt[10] + pt[11]));
+    if (VARIANT == 1) tsum /= sigmasq;
+    return tsum + ((pt[12] + pt[13]) + pt[14]);
 }
 
 // Coefficients of the per-frequency Toeplitz products (round 6).  After the row transforms of phase A the remaining convolution
@@ -1315,7 +1366,8 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
 // four multiply-adds per (output row, input row) instead of eight (h48::pair_product).  Each role runs its own loop, selected per
 // wave, so that a wave keeps only its role's state in registers: the row waves the CG vectors, the dense waves 46 doubles of
 // coefficients per output row.  Every role executes the same workgroup barriers in the same order -- one behind the coefficients, two
-// per operator application, one behind the sums in front of the loop, three per iteration -- and reads s_stop behind the same one.
+// per operator application, one behind the sums in front of the loop, three per iteration (with ALPHA_WAVE, round 12 below: three
+// per operator application, four per iteration) -- and reads s_stop behind the same one.
 //
 // Dense role, NOUT output rows per lane (2: waves 2-4, rows kd = 2 g, 2 g + 1; 1: waves 5-7, row kd = g + 4).  The last wave is the
 // one with the least to do: it also takes the norm test and the reciprocal for the next beta (the duties of cg_herm48_kernel's idle
@@ -1327,8 +1379,17 @@ __global__ __launch_bounds__(h48::kThreadsH) void cg_herm48_kernel(Args a) {
 // way out of the loop pays what is owed.  And what the row lanes read from memory before the first residual is loaded at kernel
 // entry (hrow::EarlyLoads).  The dense role is untouched: reading the stop flag together with G and branching behind the products
 // was measured and dropped (profiles/r10_cg48_chain_ab.txt: no time gained).
-template <int NOUT>
-__device__ __forceinline__ void pairs_dense_role(const Args& a, double2* lds2, double* red, double* s_part, double* s_rcp, int* s_stop) {
+//
+// Round 12 (ALPHA_WAVE, the default; EFGP_CG48_ALPHA_ROWS=1 keeps the row lanes' statements of round 11): the sum of <u, A u> and the
+// step length leave the row waves' stream.  Between barriers 2 and 3 the dense waves had nothing to do; now the one-row wave
+// h48::kAlphaWaveP runs, behind barrier 2, the statements the row lanes ran inside D (h48::uAu_summands, uAu_of_lane,
+// quot_half_wave: the same reads, tree and quotient, so the same bits), stores the quotient to *s_alpha, and every wave of the
+// workgroup meets at one more barrier, "2b": the dense waves right behind barrier 2 (the summing wave behind its store), the row
+// waves behind D's transforms, where they read the quotient.  rz: the <r,z> the row lanes hold in this application (0 in front of
+// the loop).
+template <int NOUT, int VARIANT, bool ALPHA_WAVE>
+__device__ __forceinline__ void pairs_dense_role(const Args& a, double2* lds2, double* red, double* s_part, double* s_rcp, int* s_stop,
+                                                 double* s_alpha) {
     using namespace h48;
     const double2* const Gb = lds2;
     double2* const Tb = lds2 + G_ELEMS;
@@ -1336,6 +1397,7 @@ __device__ __forceinline__ void pairs_dense_role(const Args& a, double2* lds2, d
     const int tid = threadIdx.x, lane = tid & 63, d = tid - 64 * kRowWavesP;
     const int f1d = d % F, grp = d / F, kd = NOUT == 2 ? 2 * grp : grp + 4;
     const bool duty = tid >= kThreadsP - 64;
+    [[maybe_unused]] const bool sums = NOUT == 1 && tid >> 6 == kAlphaWaveP;
     PairCoeffs pc[NOUT];
     {
         const double2 wc = a.g.tw[0][((n - 1) * f1d) % F];
@@ -1349,7 +1411,7 @@ __device__ __forceinline__ void pairs_dense_role(const Args& a, double2* lds2, d
     const double2* const g0 = Gb + f1d;
     double2* const t0 = Tb + kd * LDR + f1d;
     // one operator application, as the dense lanes see it; false: the stopping decision of the last iteration was "stop"
-    auto products = [&]() __attribute__((always_inline)) -> bool {
+    auto products = [&]([[maybe_unused]] double rz) __attribute__((always_inline)) -> bool {
         __syncthreads();                                  // barrier 1: G and the row lanes' shares of <u,u> are written
 #ifdef EFGP_CG_STAMPS
         // slot 8: from barrier 1 until the flag and the first row of G are in the first dense lane's registers
@@ -1380,19 +1442,32 @@ __device__ __forceinline__ void pairs_dense_role(const Args& a, double2* lds2, d
         else s_part[d] = t0r;
         __syncthreads();                                  // barrier 2: Yh and the summands of <u, A u> are written
         EFGP_STAMP_BY(6, 64 * kRowWavesP);
+        if constexpr (ALPHA_WAVE) {
+            if (sums) {
+                double pt[15];
+                uAu_summands(s_part, lane, pt);
+                const double alpha = quot_half_wave(uAu_of_lane<VARIANT>(pt, a.sigmasq), rz);
+                if (lane == 0) *s_alpha = alpha;
+            }
+            __syncthreads();                              // barrier 2b: the step length is written
+        }
         return true;
     };
-    if (!a.zero_x0) products();
+    if (!a.zero_x0) products(0.0);
     __syncthreads();                                      // the row waves' sums in front of the loop
-    const double rz = red[0] + red[4], bb = red[1] + red[5], asym = red[2] + red[6], ws_bad = red[3] + red[7];
+    double rz = red[0] + red[4];
+    const double bb = red[1] + red[5], asym = red[2] + red[6], ws_bad = red[3] + red[7];
     if (hrow::refused(asym, bb, ws_bad)) return;          // (the row lanes write the NaNs and the -2)
     const hrow::NormTest norm(bb);
     if (duty && lane == 0) *s_rcp = 1.0 / (rz + 1e-16);
     for (int it = 0; it < a.max_iter;) {
-        if (!products()) break;
+        if (!products(rz)) break;
         __syncthreads();                                  // barrier 3: the row waves' sums of <r,r> and <r,z>
         ++it;
         if (duty) norm.publish(a, red[0] + red[1], red[2] + red[3], it, lane, s_rcp, s_stop);
+        if constexpr (ALPHA_WAVE) {
+            if (sums) rz = red[2] + red[3];               // as the row lanes have it (RowLanes::new_direction_to)
+        }
     }
 }
 
@@ -1414,9 +1489,10 @@ __device__ __forceinline__ void pairs_dense_role(const Args& a, double2* lds2, d
 //   * the two wave sums of <r,r> and <r,z> run with their stages interleaved (wave_sum_pair).
 // Where the compiler had a choice between two contractions (the first butterflies of A, ws y + sigma^2 u in D) it chose differently
 // once u was one of two arrays; those roundings are written out in the form round 10 had (dft8_in4_ws, D).
-template <int VARIANT, bool FUSED = false, bool CHAIN_V1 = false, bool ROW_V1 = CHAIN_V1, bool PRECOND = true>
+template <int VARIANT, bool FUSED = false, bool CHAIN_V1 = false, bool ROW_V1 = CHAIN_V1, bool PRECOND = true, bool ALPHA_WAVE = !ROW_V1>
 __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a) {
     static_assert(ROW_V1 || !CHAIN_V1, "the statements of round 9 come with round 10's loop");
+    static_assert(!ALPHA_WAVE || !ROW_V1, "the step length on a dense wave comes with round 11's row role");
     using namespace h48;
     using h64::dft8_in4;
     using hrow::KS;
@@ -1427,8 +1503,12 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
     __shared__ double s_rcp;             // 1 / (<r,z> + 1e-16) for the next beta, computed by the last wave during A
     __shared__ int s_stop;               // convergence decision of the last completed iteration, taken by the last wave during A
     // the lanes' summands of <u, A u>.  [0, NDP): the Toeplitz terms of the dense lanes, written between barriers 1 and 2;
-    // [NDP, NDP + 96): wgt * sigma^2 sum |u|^2 of every row lane, written in A.  Read behind barrier 2 by the row lanes in D.
+    // [NDP, NDP + 96): wgt * sigma^2 sum |u|^2 of every row lane, written in A (ALPHA_WAVE: between barriers 1 and 2).  Read behind barrier 2: by the row lanes in D, or by the summing
+    // dense wave (ALPHA_WAVE).
     __shared__ double s_part[NDP + 8 * NR];
+    // ALPHA_WAVE: rz / (<u, A u> + 1e-16) of the application under way, written by the dense wave h48::kAlphaWaveP between barriers
+    // 2 and 2b, read by the row lanes behind barrier 2b
+    __shared__ double s_alpha;
     double2* const Gb = lds2;                    // G[k0][f1], k0 = 0..11 (rows beyond h are zero), f1 = 0..47
     double2* const Tb = lds2 + G_ELEMS;          // conj Yh[k0][f1], pitch LDR
     double2* const Qb = Tb + G_ELEMS;            // the row lines' exchange scratch
@@ -1445,6 +1525,13 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
     }
     // the row lanes' loads of b, the diagonal and, without FUSED, x0 and ws go out here and are used behind the prologue
     constexpr bool EARLY = !CHAIN_V1, DEFER_X = !CHAIN_V1;
+    // the row lanes' shares of sigma^2 <u,u> are formed between barriers 1 and 2, where the row waves wait for the dense waves,
+    // instead of in A, where they stood behind the exchange's LDS wait (profiles/r12_cg48_alpha_wave.txt)
+    constexpr bool UU_GAP = ALPHA_WAVE;
+    // the lanes of wave 1 without modes keep the zeros that A u and the step length have there from the start, instead of writing
+    // them in every application: behind barrier 2b those nine moves stand on wave 1's chain (the arms of round 11 have them in the
+    // wait between barriers 1 and 2)
+    constexpr bool ZEROS_ONCE = ALPHA_WAVE;
     [[maybe_unused]] hrow::EarlyLoads<6> early;
     if constexpr (EARLY) early.template issue<FUSED>(a, tid < 8 * NR && j < 6, k0, j);
     // the operator's spectrum, made here (one pass per dimension on 64 line slots) or from memory -- the same numbers -- and one
@@ -1462,11 +1549,11 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
     dense48_inverse_pass<kThreadsP>(lds2, twr);
     __syncthreads();
     if (wave >= kRowWavesP + kPairWavesP) {
-        pairs_dense_role<1>(a, lds2, red, s_part, &s_rcp, &s_stop);
+        pairs_dense_role<1, VARIANT, ALPHA_WAVE>(a, lds2, red, s_part, &s_rcp, &s_stop, &s_alpha);
         return;
     }
     if (wave >= kRowWavesP) {
-        pairs_dense_role<2>(a, lds2, red, s_part, &s_rcp, &s_stop);
+        pairs_dense_role<2, VARIANT, ALPHA_WAVE>(a, lds2, red, s_part, &s_rcp, &s_stop, &s_alpha);
         return;
     }
 
@@ -1511,13 +1598,15 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
                 dft8_in4(make_double2(wsr[0] * u[0].x, wsr[0] * u[0].y), make_double2(wsr[1] * u[1].x, wsr[1] * u[1].y),
                          make_double2(wsr[2] * u[2].x, wsr[2] * u[2].y), make_double2(wsr[3] * u[3].x, wsr[3] * u[3].y), v);
             else
-                dft8_in4_ws<!decltype(first)::value>(wsr, u, v);          // the same roundings, written out
+                dft8_in4_ws<!decltype(first)::value, ALPHA_WAVE>(wsr, u, v);          // the same roundings, written out
             // u6[k2] = G[k0][j + 8 k2], and the lane's share of the sigma^2 <u,u> of <u, A u> (the slots without a mode hold zeros)
-            const double uu = exchange_8to6_norm(v, u6, j < 6, xw, xr, twr, u, VARIANT == 0 ? wgt * a.sigmasq : wgt);
+            double uu = 0.0;
+            if constexpr (UU_GAP) exchange_8to6(v, u6, j < 6, xw, xr, twr);
+            else uu = exchange_8to6_norm(v, u6, j < 6, xw, xr, twr, u, VARIANT == 0 ? wgt * a.sigmasq : wgt);
             double2* g0 = Gb + k0 * LDR + j;
 #pragma unroll
             for (int t = 0; t < 6; ++t) g0[8 * t] = u6[t];
-            s_part[NDP + tid] = uu;
+            if constexpr (!UU_GAP) s_part[NDP + tid] = uu;
         }
         __syncthreads();                                  // barrier 1
         stop = s_stop;
@@ -1538,28 +1627,15 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
                 }
             }
         }
+        if constexpr (UU_GAP) {
+            // the share of sigma^2 <u,u> stood behind the exchange's LDS wait in A; the summing wave reads it behind barrier 2
+            if (row_role) s_part[NDP + tid] = norm_share(u, VARIANT == 0 ? wgt * a.sigmasq : wgt);
+        }
         __syncthreads();                                  // barrier 2: the dense waves' products (pairs_dense_role stamps them)
         EFGP_STAMP_RESTART(0);
         // D ("8x6"): row k0 >= 0 of the result from Yh[k0]; conjugated inputs, forward transform
-        if (row_role) {
-            // <u, A u> and the step length in the block of D.  The 480 summands: fifteen per lane here, then over the 32 lanes (both
-            // row waves have their lanes 0..31 in this block) and the division inside the exchange.  All twenty-one reads go out
-            // together, the summands first.
-            double pt[15];
-            const double* sp = s_part + (lane & 31);
-#pragma unroll
-            for (int t = 0; t < 15; ++t) pt[t] = sp[32 * t];
-            const double2* tp = Tb + k0 * LDR + j;
-#pragma unroll
-            for (int t = 0; t < 6; ++t) u6[t] = tp[8 * t];
-            __builtin_amdgcn_sched_barrier(0);
-            double tsum = (((pt[0] + pt[1]) + (pt[2] + pt[3])) + ((pt[4] + pt[5]) + (pt[6] + pt[7]))) + ((pt[8] + pt[9]) + (pt[10] + pt[11]));
-            if (VARIANT == 1) tsum /= a.sigmasq;
-            const double uAu = tsum + ((pt[12] + pt[13]) + pt[14]);
-            dft6(u6);
-            // lanes j < 6: v[k2] = conj Y[k0][j + 6 k2], k2 in {0, 1, 6, 7}, and rz / (<u, A u> + 1e-16); a warm start's first
-            // application has rz = 0 and drops the value
-            alpha_fd = exchange_6to8_quot(u6, v, xw, xr, twr, uAu, rz);
+        // A u of the lanes j < 6 from v[k2] = conj Y[k0][j + 6 k2], k2 in {0, 1, 6, 7}
+        auto form_Au = [&]() __attribute__((always_inline)) {
             const double2 y[KS] = {s64::conjd(v[0]), s64::conjd(v[1]), s64::conjd(v[6]), s64::conjd(v[7])};
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
@@ -1575,7 +1651,42 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
                 else if constexpr (!ROW_V1) Au[s] = val;
                 else Au[s] = ok[s] ? val : make_double2(0.0, 0.0);
             }
-        } else {
+        };
+        if constexpr (ALPHA_WAVE) {
+            // <u, A u> and the step length are the dense wave h48::kAlphaWaveP's (pairs_dense_role): the row lanes run the transforms
+            // alone and meet it at barrier 2b, outside the row lanes' branch (every wave of the workgroup arrives)
+            if (row_role) {
+                const double2* tp = Tb + k0 * LDR + j;
+#pragma unroll
+                for (int t = 0; t < 6; ++t) u6[t] = tp[8 * t];
+                dft6(u6);
+                exchange_6to8(u6, v, xw, xr, twr);
+            }
+            __syncthreads();                              // barrier 2b: the step length is written
+        }
+        if (row_role) {
+            if constexpr (ALPHA_WAVE) {
+                // rz / (<u, A u> + 1e-16): the read goes out first and A u is formed under it; a warm start's first application
+                // has rz = 0 and drops the value
+                alpha_fd = s_alpha;
+            } else {
+                // <u, A u> and the step length in the block of D.  The 480 summands: fifteen per lane here, then over the 32 lanes
+                // (both row waves have their lanes 0..31 in this block) and the division inside the exchange.  All twenty-one reads
+                // go out together, the summands first.
+                double pt[15];
+                uAu_summands(s_part, lane, pt);
+                const double2* tp = Tb + k0 * LDR + j;
+#pragma unroll
+                for (int t = 0; t < 6; ++t) u6[t] = tp[8 * t];
+                __builtin_amdgcn_sched_barrier(0);
+                const double uAu = uAu_of_lane<VARIANT>(pt, a.sigmasq);
+                dft6(u6);
+                // lanes j < 6: v[k2] = conj Y[k0][j + 6 k2], k2 in {0, 1, 6, 7}, and rz / (<u, A u> + 1e-16); a warm start's
+                // first application has rz = 0 and drops the value
+                alpha_fd = exchange_6to8_quot(u6, v, xw, xr, twr, uAu, rz);
+            }
+            form_Au();
+        } else if constexpr (!ZEROS_ONCE) {
             alpha_fd = 0.0;                               // these lanes hold no modes: their vectors are zero and stay zero
 #pragma unroll
             for (int s = 0; s < KS; ++s) Au[s] = make_double2(0.0, 0.0);
@@ -1584,12 +1695,11 @@ __global__ __launch_bounds__(h48::kThreadsP) void cg_herm48_pairs_kernel(Args a)
     };
 
     double2 Ap[KS];
-    if (a.zero_x0) {
+    if (a.zero_x0 || ZEROS_ONCE) {
 #pragma unroll
         for (int s = 0; s < KS; ++s) Ap[s] = make_double2(0.0, 0.0);
-    } else {
-        apply_A(L.xv, Ap, p_prev, std::true_type{});
     }
+    if (!a.zero_x0) apply_A(L.xv, Ap, p_prev, std::true_type{});
     double bb, asym;
     if constexpr (EARLY) L.template start<true>(a, Ap, rz, bb, asym, &early);
     else L.start(a, Ap, rz, bb, asym);
@@ -1722,19 +1832,34 @@ PickLaunch herm_launch(const PersistentChoice& c, int variant, const Herm48Opera
     // EFGP_CG48_ROW_V1=1 (read per call): the row role's loop of round 10 (one iteration per pass, a copy of p, the preconditioner's
     // branch and the selects inside it) instead of round 11's; equal bits.  EFGP_CG48_CHAIN_V1=1 implies it.
     // The default arm has the preconditioner's choice as a template parameter (RowLanes::setup's `precond`).
-    const int arm = chain_v1 ? 3 : (std::getenv("EFGP_CG48_ROW_V1") != nullptr ? 2 : (hrow::has_precond(a) ? 0 : 1));
+    // EFGP_CG48_ALPHA_ROWS=1 (read per call): the default row role sums <u, A u> and forms the step length itself, inside D (round 11),
+    // instead of reading it from a dense wave behind barrier 2b (round 12); equal bits.  The other two switches' arms never had the
+    // dense wave's sum and do not see this one.
+    const bool alpha_rows = std::getenv("EFGP_CG48_ALPHA_ROWS") != nullptr;
+    const int arm =
+        chain_v1 ? 3 : (std::getenv("EFGP_CG48_ROW_V1") != nullptr ? 2 : (hrow::has_precond(a) ? 0 : 1) + (alpha_rows ? 4 : 0));
     // the launch's label names the arm (efgp_cg_last_launch reports it: the tests of the switches read it)
-    static const char* const fused8[4] = {"fused mean solve (48x48, eight waves)", "fused mean solve (48x48, eight waves, no diagonal)",
+    static const char* const fused8[6] = {"fused mean solve (48x48, eight waves)",
+                                          "fused mean solve (48x48, eight waves, no diagonal)",
                                           "fused mean solve (48x48, eight waves, row role of round 10)",
-                                          "fused mean solve (48x48, eight waves, round 9)"};
-    static const char* const herm8[4] = {"persistent CG (48x48, Hermitian, eight waves)", "persistent CG (48x48, Hermitian, eight waves, no diagonal)",
+                                          "fused mean solve (48x48, eight waves, round 9)",
+                                          "fused mean solve (48x48, eight waves, step length on the row waves)",
+                                          "fused mean solve (48x48, eight waves, no diagonal, step length on the row waves)"};
+    static const char* const herm8[6] = {"persistent CG (48x48, Hermitian, eight waves)",
+                                         "persistent CG (48x48, Hermitian, eight waves, no diagonal)",
                                          "persistent CG (48x48, Hermitian, eight waves, row role of round 10)",
-                                         "persistent CG (48x48, Hermitian, eight waves, round 9)"};
+                                         "persistent CG (48x48, Hermitian, eight waves, round 9)",
+                                         "persistent CG (48x48, Hermitian, eight waves, step length on the row waves)",
+                                         "persistent CG (48x48, Hermitian, eight waves, no diagonal, step length on the row waves)"};
     switch (c.pick) {
         case PersistentPick::fused48: {
             if (pairs) {
-                void (*const eight[4])(Args) = {cg_herm48_pairs_kernel<0, true>, cg_herm48_pairs_kernel<0, true, false, false, false>,
-                                                cg_herm48_pairs_kernel<0, true, false, true>, cg_herm48_pairs_kernel<0, true, true>};
+                void (*const eight[6])(Args) = {cg_herm48_pairs_kernel<0, true>,
+                                                cg_herm48_pairs_kernel<0, true, false, false, false>,
+                                                cg_herm48_pairs_kernel<0, true, false, true>,
+                                                cg_herm48_pairs_kernel<0, true, true>,
+                                                cg_herm48_pairs_kernel<0, true, false, false, true, false>,
+                                                cg_herm48_pairs_kernel<0, true, false, false, false, false>};
                 return {eight[arm], h48::kThreadsP, lds48p, fused8[arm]};
             }
             void (*const dense[2])(Args) = {cg_herm48_kernel<0, true, true, false>, cg_herm48_kernel<0, true, true, true>};
@@ -1742,10 +1867,13 @@ PickLaunch herm_launch(const PersistentChoice& c, int variant, const Herm48Opera
         }
         case PersistentPick::herm48: {
             if (pairs) {
-                void (*const eight[4][2])(Args) = {{cg_herm48_pairs_kernel<0>, cg_herm48_pairs_kernel<1>},
-                                                   {cg_herm48_pairs_kernel<0, false, false, false, false>, cg_herm48_pairs_kernel<1, false, false, false, false>},
-                                                   {cg_herm48_pairs_kernel<0, false, false, true>, cg_herm48_pairs_kernel<1, false, false, true>},
-                                                   {cg_herm48_pairs_kernel<0, false, true>, cg_herm48_pairs_kernel<1, false, true>}};
+                void (*const eight[6][2])(Args) = {
+                    {cg_herm48_pairs_kernel<0>, cg_herm48_pairs_kernel<1>},
+                    {cg_herm48_pairs_kernel<0, false, false, false, false>, cg_herm48_pairs_kernel<1, false, false, false, false>},
+                    {cg_herm48_pairs_kernel<0, false, false, true>, cg_herm48_pairs_kernel<1, false, false, true>},
+                    {cg_herm48_pairs_kernel<0, false, true>, cg_herm48_pairs_kernel<1, false, true>},
+                    {cg_herm48_pairs_kernel<0, false, false, false, true, false>, cg_herm48_pairs_kernel<1, false, false, false, true, false>},
+                    {cg_herm48_pairs_kernel<0, false, false, false, false, false>, cg_herm48_pairs_kernel<1, false, false, false, false, false>}};
                 return {eight[arm][variant != 0], h48::kThreadsP, lds48p, herm8[arm]};
             }
             void (*const dense[2][2])(Args) = {{cg_herm48_kernel<0, false, true, false>, cg_herm48_kernel<1, false, true, false>},

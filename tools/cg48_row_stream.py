@@ -22,6 +22,15 @@ their branches).  Instructions are counted by class and by the phase they stand 
     beta / p    barrier 3 to the next s_and_saveexec (the next A) or the back edge
 A body of two iterations is reported per iteration (counts halved).  The phases follow the instructions' positions, so work the
 scheduler moved across a marker is counted where it stands.
+
+--barriers 4 is the loop of the arm whose step length comes from a dense wave (round 12): barrier "2b" stands inside D, behind the row
+transforms, and D runs on to the end of the exec-masked block behind THAT barrier.
+
+--alpha-slice reports, inside D, the instructions that serve only the sum of <u, A u> and the step length: the backward slice, by
+registers, of D's last v_div_fixup_f64 (the quotient), restricted to D; an s_waitcnt or s_nop counts with it when the next
+instruction that is neither is in the slice.  (The slice ends at D's first instruction: the numerator and the addresses it reads
+are made elsewhere.  Nothing else in D reads a register the slice writes before the slice overwrites it, or the tool says so.)
+For the VARIANT 0 kernels: VARIANT 1 divides by sigma^2 in D as well, and the last v_div_fixup_f64 there is not the quotient's.
 """
 import argparse
 import re
@@ -83,7 +92,7 @@ def kernel_body(lines, targs):
     raise SystemExit("no cg_herm48_pairs_kernel" + targs + " in the file")
 
 
-def row_loop(body):
+def row_loop(body, per_iter=3):
     labels = {m.group(1): i for i, l in enumerate(body) for m in [re.match(r"^\.(LBB\d+_\d+):", l)] if m}
     spans = []
     for i, l in enumerate(body):
@@ -91,10 +100,10 @@ def row_loop(body):
         if m and labels.get(m.group(1), 1 << 30) < i:
             seg = body[labels[m.group(1)]:i + 1]
             nb = sum(1 for x in seg if re.match(r"^\s+s_barrier", x))
-            if nb in (3, 6) and any("row_bcast" in x for x in seg):
+            if nb in (per_iter, 2 * per_iter) and any("row_bcast:31" in x for x in seg):
                 spans.append((labels[m.group(1)], i))
     if not spans:
-        raise SystemExit("no loop with wave sums and three or six barriers")
+        raise SystemExit(f"no loop with wave sums and {per_iter} or {2 * per_iter} barriers")
     return body[min(s[0] for s in spans):max(s[1] for s in spans) + 1]
 
 
@@ -144,14 +153,16 @@ def walk(blocks, start, avoid):
     raise SystemExit("the walk does not come back to " + start)
 
 
-def phases(path):
-    out, phase, after_d = [], "A", False
+def phases(path, per_iter=3):
+    out, phase = [], "A"
     nbar = 0
+    after = {3: {1: "gap", 2: "D", 0: "beta / p"}, 4: {1: "gap", 2: "D", 3: "D", 0: "beta / p"}}[per_iter]
     for ins in path:
         op = ins.split()[0]
         if phase == "beta / p" and op.startswith("s_and_saveexec"):
             phase = "A"
-        if phase == "D" and op == "s_or_b64" and "exec" in ins.split()[1]:
+        d_last_block = per_iter == 3 or nbar % per_iter == 3
+        if phase == "D" and d_last_block and op == "s_or_b64" and "exec" in ins.split()[1]:
             out.append((phase, ins))
             phase = "updates"
             continue
@@ -160,8 +171,64 @@ def phases(path):
         out.append((phase, ins))
         if op == "s_barrier":
             nbar += 1
-            phase = {1: "gap", 2: "D", 0: "beta / p"}[nbar % 3]
+            phase = after[nbar % per_iter]
     return out, nbar
+
+
+def regs(tok):
+    """the 32-bit registers an operand names: v[4:5] -> {v4, v5}, -v[4:5] -> the same, s37, vcc"""
+    tok = tok.strip().lstrip("-|").rstrip("|")
+    m = re.match(r"^([vs])\[(\d+):(\d+)\]$", tok)
+    if m:
+        return {f"{m.group(1)}{k}" for k in range(int(m.group(2)), int(m.group(3)) + 1)}
+    if re.match(r"^[vs]\d+$", tok):
+        return {tok}
+    if tok in ("vcc", "exec"):
+        return {tok}
+    return set()
+
+
+def defs_uses(ins):
+    op, _, rest = ins.partition(" ")
+    toks = [t for t in re.split(r"[,\s]+", rest.strip()) if t]
+    if op.startswith(("ds_write", "s_waitcnt", "s_nop", "s_barrier", "s_cbranch", "s_branch")):
+        return set(), set().union(*[regs(t) for t in toks]) if toks else set()
+    ndef = 2 if op.startswith("v_div_scale") else 1
+    d = set().union(*[regs(t) for t in toks[:ndef]]) if toks else set()
+    u = set().union(*[regs(t) for t in toks[ndef:]]) if len(toks) > ndef else set()
+    if "dpp" in op or op.startswith(("v_fmac", "v_div_fmas")):
+        u |= d if "dpp" in op or op.startswith("v_fmac") else {"vcc"}
+    return d, u
+
+
+def alpha_slice(d_ins):
+    """indices into d_ins (one iteration's D) of the instructions that serve only the quotient"""
+    last = max((i for i, x in enumerate(d_ins) if x.startswith("v_div_fixup_f64")), default=None)
+    if last is None:
+        return set(), []
+    want, inslice = set(defs_uses(d_ins[last])[1]), {last}
+    for i in range(last - 1, -1, -1):
+        d, u = defs_uses(d_ins[i])
+        if d & want:
+            inslice.add(i)
+            want = (want - d) | u
+    quiet = ("s_waitcnt", "s_nop")
+    for i, x in enumerate(d_ins):
+        if x.startswith(quiet):
+            nxt = next((k for k in range(i + 1, len(d_ins)) if not d_ins[k].startswith(quiet)), None)
+            if nxt in inslice:
+                inslice.add(i)
+    # a register the slice wrote, read by an instruction outside it before the slice or anyone else rewrites it
+    shared, live = [], set()
+    for i, x in enumerate(d_ins[:last + 1]):
+        d, u = defs_uses(x)
+        if i in inslice:
+            live |= d
+        else:
+            if u & live:
+                shared.append(x)
+            live -= d
+    return inslice, shared
 
 
 def main():
@@ -172,16 +239,18 @@ def main():
     ap.add_argument("--avoid", default="", help="blocks off the steady path, comma separated (LBB1_230, bb.229)")
     ap.add_argument("--list", action="store_true", help="print the loop's blocks with their sizes and branches")
     ap.add_argument("--dump", help="write the walked path to this file")
+    ap.add_argument("--barriers", type=int, default=3, choices=(3, 4), help="workgroup barriers per iteration (4: with barrier 2b)")
+    ap.add_argument("--alpha-slice", action="store_true", help="inside D, what serves only <u, A u> and the step length")
     a = ap.parse_args()
-    loop = row_loop(kernel_body(open(a.asm).read().split("\n"), a.targs))
+    loop = row_loop(kernel_body(open(a.asm).read().split("\n"), a.targs), a.barriers)
     blocks = blocks_of(loop)
     if a.list or not a.start:
         for n, b in blocks.items():
             print(f"{n:12s} {len(b):4d}  " + "  ".join(i for i in b if i.startswith(("s_cbranch", "s_branch", "s_barrier"))))
         return
     path = walk(blocks, a.start, set(x for x in a.avoid.split(",") if x))
-    tagged, nbar = phases(path)
-    per = nbar // 3
+    tagged, nbar = phases(path, a.barriers)
+    per = nbar // a.barriers
     tab = {p: Counter() for p in PHASES}
     for p, ins in tagged:
         tab[p][classify(ins)] += 1
@@ -194,6 +263,21 @@ def main():
             print(f"{c:12s}" + "".join(f"{v:10g}" for v in row) + f"{sum(row):10g}")
     tot = [sum(tab[p].values()) / per for p in PHASES]
     print(f"{'all':12s}" + "".join(f"{v:10g}" for v in tot) + f"{sum(tot):10g}")
+    if a.alpha_slice:
+        # D of the first iteration on the path
+        first = next(i for i, (p, _) in enumerate(tagged) if p == "D")
+        end = next(i for i in range(first, len(tagged)) if tagged[i][0] != "D")
+        d_ins = [ins for _, ins in tagged[first:end]]
+        inslice, shared = alpha_slice(d_ins)
+        cnt = Counter(classify(d_ins[i]) for i in inslice)
+        print(f"inside D ({len(d_ins)} instructions): {len(inslice)} serve only <u, A u> and the step length")
+        for c in CLASSES:
+            if cnt[c]:
+                print(f"  {c:12s}{cnt[c]:6d}")
+        for x in shared:
+            print("  NOT only the quotient's (its result is read outside the slice): " + x)
+        for i in sorted(inslice):
+            tagged[first + i] = ("D alpha", tagged[first + i][1])
     if a.dump:
         open(a.dump, "w").write("\n".join(f"{p:9s} {i}" for p, i in tagged) + "\n")
 
