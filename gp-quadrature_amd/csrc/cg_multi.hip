@@ -1033,7 +1033,7 @@ static int raise_line_lds(const LineKernel* begin, const LineKernel* end, const 
 
 // The Hermitian 3-D set-up on top of the general one: the real centred spectrum on first use, the check of the data (once per group
 // of rows, through the pinned `host`), the half block in `a`
-static int setup_apply_herm3(efgp_toeplitz_s* op, CgArgs& a, int rows, int* host, hipStream_t stream, OperatorApply* ap) {
+static int setup_apply_herm3(efgp_toeplitz_s* op, CgArgs& a, int rows, int shape_rows, int* host, hipStream_t stream, OperatorApply* ap) {
     DeviceCtx* ctx = op->ctx;
     const ToepGeom& g = op->g;
     if (!op->vc3) {
@@ -1067,8 +1067,8 @@ static int setup_apply_herm3(efgp_toeplitz_s* op, CgArgs& a, int rows, int* host
     l3h.b2 = a.pad_out + (int64_t)rows * nh * g.n[1] * g.F[2];
     const int64_t nlines = nh * g.n[1];
     const int64_t fit = line_lds_fit(ctx, g.F[2]);
-    int lpb = lines_per_block(8, nlines, fit, rows, 64);
-    if (rows >= 3 && lpb < 16 && 32 <= fit) lpb = 16;          // measured at mtot 57: 125 vs 133 us per iteration of 3 systems
+    int lpb = lines_per_block(8, nlines, fit, shape_rows, 64);
+    if (shape_rows >= 3 && lpb < 16 && 32 <= fit) lpb = 16;          // measured at mtot 57: 125 vs 133 us per iteration of 3 systems
     auto knob = [](const char* name, int dflt) {
         const char* e = std::getenv(name);
         int v = e ? std::atoi(e) : dflt;
@@ -1082,7 +1082,7 @@ static int setup_apply_herm3(efgp_toeplitz_s* op, CgArgs& a, int rows, int* host
     }
     l3h.lpb_c = lpb;
     l3h.lpb_s = (int)std::min<int64_t>(knob("EFGP_CG3_LS", 16), g.F[2] / 2);
-    l3h.lpb_m = (int)std::min<int64_t>(knob("EFGP_CG3_LM", rows >= 3 ? 32 : 16), g.F[2] / 2);      // 3 systems: 124.6 vs 132.6 us
+    l3h.lpb_m = (int)std::min<int64_t>(knob("EFGP_CG3_LM", shape_rows >= 3 ? 32 : 16), g.F[2] / 2);      // 3 systems: 124.6 vs 132.6 us
     l3h.nblk_lines = (int)((nlines + lpb - 1) / lpb);
     ap->lds[2] = line_lds_bytes(lpb, g.F[2]);
     ap->lds[1] = line_lds_bytes(l3h.lpb_s, g.F[1]);
@@ -1091,14 +1091,16 @@ static int setup_apply_herm3(efgp_toeplitz_s* op, CgArgs& a, int rows, int* host
                                           {(const void*)cg3h_dim1_kernel<1>, 1}, {(const void*)cg3h_mid0_kernel, 0}};
     if (const int rc = raise_line_lds(std::begin(kLines3H), std::end(kLines3H), ap->lds)) return rc;
     a.nblk = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(std::min(kCgBlocksMax, knob("EFGP_CG_NBLK", 128)), (a.v_len + kVecThreads - 1) / kVecThreads),
-                                                        std::max<int64_t>(1, 1024 / rows)));
+                                                        std::max<int64_t>(1, 1024 / shape_rows)));
     ap->kind = OperatorApply::kLines3H;
     return EFGP_OK;
 }
 
 // Chooses how the iterations of this group of `rows` systems apply the operator and sets it up (the 2-D line kernels need the
-// reference grid's spectrum; the Hermitian 3-D ones change the block `a` describes)
-static int setup_apply(efgp_toeplitz_s* op, const CgSolve& s, CgArgs& a, int rows, int* host, hipStream_t stream, OperatorApply* ap) {
+// reference grid's spectrum; the Hermitian 3-D ones change the block `a` describes).  The launch shapes -- lines per workgroup, and
+// with them the order of the partial sums -- follow `shape_rows`, the size of a full group of the solve (solve_multi_launch)
+static int setup_apply(efgp_toeplitz_s* op, const CgSolve& s, CgArgs& a, int rows, int shape_rows, int* host, hipStream_t stream,
+                       OperatorApply* ap) {
     DeviceCtx* ctx = op->ctx;
     const ToepGeom& g = op->g;
     if (std::getenv("EFGP_NO_CG_LINES") != nullptr) return EFGP_OK;
@@ -1111,7 +1113,7 @@ static int setup_apply(efgp_toeplitz_s* op, const CgSolve& s, CgArgs& a, int row
         la.tw1 = op->tw[1];
         la.b1 = a.pad_out;                                                     // [rows][n0][F1] fits: Ftot >= 2 n0 F1
         la.b2 = a.pad_out + (int64_t)rows * g.n[0] * g.F[1];
-        la.lpb = lines_per_block(4, g.n[0], line_lds_fit(ctx, std::max(g.F[0], g.F[1])), rows, 32);
+        la.lpb = lines_per_block(4, g.n[0], line_lds_fit(ctx, std::max(g.F[0], g.F[1])), shape_rows, 32);
         la.nblk_rows = (int)((g.n[0] + la.lpb - 1) / la.lpb);
         ap->lds[1] = line_lds_bytes(la.lpb, g.F[1]);
         ap->lds[0] = line_lds_bytes(la.lpb, g.F[0]);
@@ -1131,7 +1133,7 @@ static int setup_apply(efgp_toeplitz_s* op, const CgSolve& s, CgArgs& a, int row
     for (int q = 0; q < 3; ++q) l3.tw[q] = op->tw[q];
     l3.b1 = a.pad_out;
     l3.b2 = a.pad_out + (int64_t)rows * nlines * g.F[2];
-    l3.lpb_c = lines_per_block(16, nlines, fit, rows, 64);
+    l3.lpb_c = lines_per_block(16, nlines, fit, shape_rows, 64);
     l3.lpb_s = 16;
     l3.nblk_lines = (int)((nlines + l3.lpb_c - 1) / l3.lpb_c);
     ap->lds[2] = line_lds_bytes(l3.lpb_c, g.F[2]);
@@ -1141,7 +1143,7 @@ static int setup_apply(efgp_toeplitz_s* op, const CgSolve& s, CgArgs& a, int row
     if (const int rc = raise_line_lds(std::begin(kLines3), std::end(kLines3), ap->lds)) return rc;
     ap->kind = OperatorApply::kLines3;
     if (s.hermitian && (g.n[0] & 1) && (g.n[1] & 1) && (g.n[2] & 1) && g.n[0] >= 3 && std::getenv("EFGP_NO_CG_HERM3") == nullptr)
-        return setup_apply_herm3(op, a, rows, host, stream, ap);
+        return setup_apply_herm3(op, a, rows, shape_rows, host, stream, ap);
     return EFGP_OK;
 }
 
@@ -1329,8 +1331,10 @@ static int poll_and_compact(ActiveRows& st, CgArgs& a, int* d_rows, int* host, h
 }
 
 // One group of `rows` systems (from row r0 of the solve) whose padded grids fit the scratch: lay out the scratch, initialise, then
-// bursts of iterations with a poll and a compaction behind each.  st->hsc holds the final scalars.
-static int solve_group(efgp_toeplitz_s* op, const CgSolve& s, int64_t r0, ActiveRows* st, hipStream_t stream) {
+// bursts of iterations with a poll and a compaction behind each.  st->hsc holds the final scalars.  shape_rows: the size of a full
+// group of this solve, which the launch shapes follow -- a short last group sums in the order of the full ones, so a system's
+// bits do not depend on the group it falls into.
+static int solve_group(efgp_toeplitz_s* op, const CgSolve& s, int64_t r0, ActiveRows* st, int shape_rows, hipStream_t stream) {
     DeviceCtx* ctx = op->ctx;
     const ToepGeom g = op->g;
     const int rows = st->rows;
@@ -1372,7 +1376,7 @@ static int solve_group(efgp_toeplitz_s* op, const CgSolve& s, int64_t r0, Active
     a.v_len = g.M;
     a.v_w1 = g.M;
     a.nblk = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(64 /* update kernels: measured optimum */, (g.M + kVecThreads - 1) / kVecThreads),
-                                                        std::max<int64_t>(1, 1024 / rows)));
+                                                        std::max<int64_t>(1, 1024 / shape_rows)));
     EFGP_HIP_CHECK(hipMemsetAsync(a.status, 0, off_partial - off_status, stream));      // status, map, counters
 
     // r0 = b - A x0
@@ -1385,7 +1389,7 @@ static int solve_group(efgp_toeplitz_s* op, const CgSolve& s, int64_t r0, Active
     EFGP_HIP_CHECK(hipGetLastError());
 
     OperatorApply ap;
-    rc = setup_apply(op, s, a, rows, host, stream, &ap);
+    rc = setup_apply(op, s, a, rows, shape_rows, host, stream, &ap);
     if (rc != EFGP_OK) return rc;
     // iteration loop; active rows are compacted on the host whenever the status is polled
     BurstGraph graph(op, stream);
@@ -1429,12 +1433,13 @@ int solve_multi_launch(efgp_toeplitz_s* op, const CgSolve& s, int* iters_out, in
             stream = ctx->aux_stream;
         }
     }
-    // rows are processed in groups whose padded grids fit ~512 MB of scratch
-    const int64_t group_cap = std::max<int64_t>(1, (int64_t)(512ll << 20) / (op->g.Ftot * (int64_t)sizeof(double2)));
+    // rows are processed in groups whose padded grids fit ~512 MB of scratch and whose systems fit gridDim.y
+    const int64_t group_cap = std::max<int64_t>(1, std::min<int64_t>(kMaxGridRows, (int64_t)(512ll << 20) / (op->g.Ftot * (int64_t)sizeof(double2))));
+    const int shape_rows = (int)std::min<int64_t>(group_cap, s.nbatch);
     int global_iters = 0;
     for (int64_t r0 = 0; r0 < s.nbatch; r0 += group_cap) {
         ActiveRows st((int)std::min<int64_t>(group_cap, s.nbatch - r0));
-        const int rc = solve_group(op, s, r0, &st, stream);
+        const int rc = solve_group(op, s, r0, &st, shape_rows, stream);
         if (rc != EFGP_OK) return rc;
         int group_iters;
         if (!s.batched) {

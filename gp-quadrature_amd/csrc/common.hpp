@@ -47,6 +47,10 @@ void set_error(const char* fmt, ...);
         }                                    \
     } while (0)
 
+// Rows (systems, probes, points) ride in gridDim.y, which holds at most 65535: every entry whose caller sets the row count
+// takes them in launches of at most this many, with a row offset ("Rows in gridDim.y")
+constexpr int kMaxGridRows = 65535;
+
 // scratch slots (grow-only device buffers, one set per device)
 enum Slot {
     SLOT_FINE = 0,     // complex fine grids of the NUFFT (nbatch * prod nf)

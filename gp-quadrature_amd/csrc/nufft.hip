@@ -395,8 +395,8 @@ __global__ __launch_bounds__(kSpreadThreads) void spread_pad_kernel(SpreadArgs a
 }
 
 // out[b][n] = the +-1 probe the spread kernels generate for (seed, row b, point n + index_offset)
-__global__ void rademacher_fill_kernel(unsigned long long seed, int64_t npts, int64_t index_offset, double* __restrict__ out) {
-    const int row = blockIdx.y;
+__global__ void rademacher_fill_kernel(unsigned long long seed, int64_t npts, int64_t index_offset, int row0, double* __restrict__ out) {
+    const int row = row0 + blockIdx.y;
     for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < npts; n += (int64_t)gridDim.x * blockDim.x)
         out[(int64_t)row * npts + n] = efgp_rademacher(seed, row, (long long)((unsigned long long)n + (unsigned long long)index_offset));
 }
@@ -3585,8 +3585,10 @@ int efgp_rademacher_fill(int device, uint64_t seed, int64_t index_offset, int nb
     DeviceGuard guard(device, (hipStream_t)stream_);
     hipStream_t stream = (hipStream_t)stream_;
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((npts + 255) / 256, 4096));
-    hipLaunchKernelGGL(rademacher_fill_kernel, dim3(blocks, nbatch), dim3(256), 0, stream, (unsigned long long)seed, npts, index_offset,
-                       out);
+    for (int r0 = 0; r0 < nbatch; r0 += kMaxGridRows) {       // gridDim.y holds at most 65535 rows
+        hipLaunchKernelGGL(rademacher_fill_kernel, dim3(blocks, std::min(kMaxGridRows, nbatch - r0)), dim3(256), 0, stream,
+                           (unsigned long long)seed, npts, index_offset, r0, out);
+    }
     EFGP_HIP_CHECK(hipGetLastError());
     return EFGP_OK;
 }

@@ -521,8 +521,8 @@ int efgp_toeplitz_apply(efgp_toeplitz_t* op, const void* x, int nbatch, void* y,
     EFGP_REQUIRE(nbatch >= 1, "efgp_toeplitz_apply: nbatch must be >= 1");
     hipStream_t stream = (hipStream_t)stream_;
     DeviceGuard guard(op->device, (hipStream_t)stream_);
-    // bound the scratch: process rows in chunks of at most ~256 MB of padded grid
-    const int64_t max_rows = std::max<int64_t>(1, (int64_t)(256ll << 20) / (op->g.Ftot * (int64_t)sizeof(double2)));
+    // bound the scratch: process rows in chunks of at most ~256 MB of padded grid, and of at most the rows gridDim.y holds
+    const int64_t max_rows = std::max<int64_t>(1, std::min<int64_t>(kMaxGridRows, (int64_t)(256ll << 20) / (op->g.Ftot * (int64_t)sizeof(double2))));
     for (int64_t r0 = 0; r0 < nbatch; r0 += max_rows) {
         const int rows = (int)std::min<int64_t>(max_rows, nbatch - r0);
         double2* pad = (double2*)scratch(op->ctx, SLOT_TOEP_PAD, (size_t)rows * (size_t)op->g.Ftot * sizeof(double2));
@@ -552,7 +552,7 @@ int efgp_toeplitz_apply_scaled(efgp_toeplitz_t* op, const void* x, int x_is_real
     if (toeplitz_apply_fused_eligible(q.g))
         return toeplitz_apply_fused_launch(q.g, q.tw[0], q.vhat, (const double2*)pre, (const double2*)post, x, x_is_real, (double2*)y, nbatch,
                                            stream);
-    const int64_t max_rows = std::max<int64_t>(1, (int64_t)(256ll << 20) / (op->g.Ftot * (int64_t)sizeof(double2)));
+    const int64_t max_rows = std::max<int64_t>(1, std::min<int64_t>(kMaxGridRows, (int64_t)(256ll << 20) / (op->g.Ftot * (int64_t)sizeof(double2))));
     for (int64_t r0 = 0; r0 < nbatch; r0 += max_rows) {
         const int rows = (int)std::min<int64_t>(max_rows, nbatch - r0);
         double2* pad = (double2*)scratch(op->ctx, SLOT_TOEP_PAD, (size_t)rows * (size_t)op->g.Ftot * sizeof(double2));

@@ -90,16 +90,17 @@ __global__ __launch_bounds__(256) void lag_scale_kernel(LagGeom g, double factor
     }
 }
 
-// phase 2 pi h k . x for mode index t of the (mtot,)*d box, k = i - (mtot-1)/2 per dimension, last dimension fastest
+// phase 2 pi h k . x for mode index t of the (mtot,)*d box, k = i - (mtot-1)/2 per dimension, last dimension fastest.  Rounded as
+// mode_phase_nd rounds it (k h x_a summed, then 2 pi): a per-axis grid with equal axes gives the bits of the one-spacing entries
 __device__ __forceinline__ double mode_phase(int d, int mtot, double h, const double* __restrict__ x, int64_t t) {
     const int m = (mtot - 1) / 2;
     double ph = 0.0;
     for (int a = d - 1; a >= 0; --a) {
         const int ia = (int)(t % mtot);
         t /= mtot;
-        ph += (double)(ia - m) * x[a];
+        ph += (double)(ia - m) * h * x[a];
     }
-    return 2.0 * M_PI * h * ph;
+    return 2.0 * M_PI * ph;
 }
 
 __global__ __launch_bounds__(256) void variance_rhs_kernel(int d, int mtot, int64_t M, double h, const double* __restrict__ x,
@@ -134,7 +135,7 @@ __global__ __launch_bounds__(256) void variance_contract_kernel(int d, int mtot,
     if (threadIdx.x == 0) {
         double s = 0.0;
         for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += part[i];
-        out[b] = s > 0.0 ? s : 0.0;                                                           // clamp_min(0), efgpnd.py:1820
+        out[b] = s < 0.0 ? 0.0 : s;                                                           // clamp_min(0), efgpnd.py:1820: a NaN stays a NaN
     }
 }
 
@@ -212,7 +213,7 @@ __global__ __launch_bounds__(256) void variance_contract_nd_kernel(AxisGrid g, c
     if (threadIdx.x == 0) {
         double s = 0.0;
         for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += part[i];
-        out[b] = s > 0.0 ? s : 0.0;
+        out[b] = s < 0.0 ? 0.0 : s;                                                           // a NaN stays a NaN
     }
 }
 
@@ -265,8 +266,9 @@ using namespace efgp;
 // The zero-padded correlation on any lag box: pad | forward transforms | multiply and sum over probes | one inverse | crop and scale
 static int lag_sums_general(DeviceCtx* ctx, const LagGeom& g, int dim, const int64_t* sizes, const void* gamma, const double* eta, int nprobes,
                             void* out, hipStream_t stream) {
-    // probes are processed in slabs so that the padded transforms stay within ~256 MB of scratch
-    const int64_t per = std::max<int64_t>(1, std::min<int64_t>(nprobes, ((int64_t)256 << 20) / (int64_t)(2 * g.P * sizeof(double2))));
+    // probes are processed in slabs so that the padded transforms stay within ~256 MB of scratch and a slab fits gridDim.y
+    const int64_t per = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nprobes, kMaxGridRows),
+                                                               ((int64_t)256 << 20) / (int64_t)(2 * g.P * sizeof(double2))));
     double2* pad = (double2*)scratch(ctx, SLOT_TOEP_PAD, (size_t)(2 * per + 1) * g.P * sizeof(double2));
     if (!pad) return EFGP_ENOMEM;
     double2* acc = pad + (int64_t)2 * per * g.P;
