@@ -83,6 +83,8 @@ _SIGNATURES = {
     "efgp_spectral_weights_nd": (_I, [_I, _I, _I, _D, C.POINTER(_D), _D, C.POINTER(_D), _PI64, _VP, _VP, _VP]),
     "efgp_gradient_prepare": (_I, [_I, _I64, _VP, _VP, _VP, _D, _VP, _VP, _VP]),
     "efgp_gradient_assemble": (_I, [_I, _I64, _I, _I, _I, _I, C.POINTER(_I), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _D, _D, _D, _D, _VP, _VP]),
+    "efgp_gradient_assemble_multi": (_I, [_I, _I64, _I, _I, _I, _I, _I, C.POINTER(_I), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _D, _D, _VP, _VP,
+                                          _D, _VP, _VP, _VP]),
     "efgp_gradient_step": (_I, [_VP, _I, _I, _I64, _VP, _VP, _D, _I, _I, _D, _D, _D, _D, _D, _D, _D, _D, _I, _I, C.c_uint64, C.c_uint64,
                            _I, _I, _I, _I, C.POINTER(_I), _VP, _D, _D, _VP, _VP, _VP, _VP, _VP]),
     "efgp_cg_solve_hermitian_async": (_I, [_VP, _VP, _D, _I, _VP, _VP, _VP, _I, _D, _I, _I, _I, _VP, _VP]),

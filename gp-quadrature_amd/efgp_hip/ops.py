@@ -410,6 +410,44 @@ def gradient_assemble(fy, tg, ws, beta, dprime, fz, v, beta_all, *, variance_idx
     return out
 
 
+def gradient_assemble_multi(fy, tg, ws, beta, dprime, fz, v, beta_all, *, variance_idx, trace_idx, sigmasq, n_obs, yy, row_scale, variance):
+    """`gradient_assemble` for the joint objective of R outputs at shared points (efgp_gradient_assemble_multi): fy, tg, beta (R, M),
+    one row per output in units of row_scale[r] (exact powers of two); yy, row_scale (R,) float64 DEVICE tensors, yy[r] the sum of
+    squares of output r in the same units.  Returns (out, rows_out): out the 3 (H + 1) + 1 doubles grad | term1 | term2 | y.alpha of
+    the sum over outputs, rows_out (R, 4) = y.z, |z|^2, y.alpha, |alpha|^2 per output, scaled back.  v = None (then fz, beta_all
+    are not looked at): no probes -- the data terms alone; the estimated entries of term1 (and of grad) are NaN."""
+    dev = ws.device
+    M = ws.numel()
+    H = dprime.shape[1] if dprime is not None and dprime.ndim == 2 else 0
+    T = v.shape[0] if v is not None else 0
+    K = len(trace_idx) if T else 0
+    if T == 0:
+        trace_idx = []
+        v = torch.empty((0, M), dtype=_RD, device=dev)
+        fz = beta_all = torch.empty((0, M), dtype=_CD, device=dev)
+    if fy.ndim != 2 or fy.shape[1] != M or tuple(tg.shape) != tuple(fy.shape) or tuple(beta.shape) != tuple(fy.shape):
+        raise ValueError(f"gradient_assemble_multi: fy, tg and beta must be (rows, {M}) (got {tuple(fy.shape)}, {tuple(tg.shape)}, "
+                         f"{tuple(beta.shape)})")
+    R = fy.shape[0]
+    for t_ in (fy, tg, ws, beta, beta_all) + ((dprime,) if H else ()) + ((fz,) if K else ()):
+        assert t_.is_cuda and t_.dtype == _CD and t_.is_contiguous()
+    assert v.dtype == _RD and v.is_contiguous() and v.shape == (T, M)
+    assert beta_all.numel() == (K + 1) * T * M and (K == 0 or fz.numel() == T * M)
+    for t_ in (yy, row_scale):
+        if not (torch.is_tensor(t_) and t_.is_cuda and t_.dtype == _RD and t_.is_contiguous() and t_.numel() == R):
+            raise ValueError(f"gradient_assemble_multi: yy and row_scale must be contiguous float64 GPU tensors of {R} entries")
+    out = torch.empty(3 * (H + 1) + 1, dtype=_RD, device=dev)
+    rows_out = torch.empty((R, 4), dtype=_RD, device=dev)
+    tix = (C.c_int * max(1, K))(*[int(i) for i in trace_idx])
+    with _on(dev):
+        check(lib().efgp_gradient_assemble_multi(dev.index, M, R, T, H, -1 if variance_idx is None else int(variance_idx), K, tix,
+                                                 _ptr(fy), _ptr(tg), _ptr(ws), _ptr(beta), _ptr(dprime) if H else None,
+                                                 _ptr(fz) if K else None, _ptr(v) if T else None, _ptr(beta_all) if T else None,
+                                                 float(sigmasq), float(n_obs), _ptr(yy), _ptr(row_scale), float(variance), _ptr(out), _ptr(rows_out), _stream(dev)),
+              "efgp_gradient_assemble_multi")
+    return out, rows_out
+
+
 def _start_vector(x0, bb, op, dev):
     """The solver's in/out buffer: a copy of x0, or zeros when x0 is None (one fill instead of a fill and a copy)."""
     if x0 is None:

@@ -306,6 +306,27 @@ int efgp_gradient_assemble(int device, int64_t nmodes, int nprobes, int n_kernel
                            const int* trace_idx, const void* fy, const void* tg, const void* ws, const void* beta, const void* dprime,
                            const void* fz, const double* v, const void* beta_all, double sigmasq, double n_obs, double yy, double variance,
                            double* out, void* stream);
+/* efgp_gradient_assemble for nrows outputs observed at the same points under one kernel and one noise level (EFGPNDMulti): the
+ * gradient of the SUM of their negative log marginals.  Arguments as efgp_gradient_assemble, except:
+ *     fy, tg, beta: (nrows, M) complex, one row per output; ws, dprime, fz, v, beta_all: shared, as above;
+ *     yy: nrows DEVICE doubles, |y_b|^2 of each output; row_scale: nrows DEVICE doubles, exact powers of two.
+ * Row b is given in units of row_scale[b]: it holds the transforms and the solve of y_b / row_scale[b], and yy[b] is
+ * |y_b|^2 / row_scale[b]^2.  The kernel scales every per-row sum back (exactly) before rows are added, so scaled rows give
+ * bitwise what unscaled ones give; row_scale[b] = 1 means plain rows.
+ *     out (3 (n_kernel_hypers + 1) + 1 doubles): grad | term1 | term2 | y.alpha of the joint objective -- term2, y.alpha and the
+ *         data part of the variance entries summed over the rows; term1 (the trace estimates, which do not depend on the data)
+ *         nrows times that of one output; n_obs is the number of observations of ONE output;
+ *     rows_out (nrows, 4): y.z, |z|^2, y.alpha, |alpha|^2 of every output, in the units of y_b.
+ * nprobes = 0 (fz, v, beta_all may be NULL) gives the data terms alone: term2, y.alpha and rows_out are complete; the entries of
+ * term1 that hold an estimate (and those of grad with them) are NaN.
+ * One launch when nrows * nmodes <= 4096, two otherwise (per-workgroup partial sums per row, then one workgroup adds partial sums
+ * and rows in a fixed order and does the scalar algebra): no atomics, bitwise repeatable, nothing read back.  Rows are strided
+ * over at most 65535 of gridDim.y inside the kernel: any nrows is one partial launch. */
+int efgp_gradient_assemble_multi(int device, int64_t nmodes, int nrows, int nprobes, int n_kernel_hypers, int variance_idx, int n_trace,
+                                 const int* trace_idx, const void* fy, const void* tg, const void* ws, const void* beta,
+                                 const void* dprime, const void* fz, const double* v, const void* beta_all, double sigmasq, double n_obs,
+                                 const double* yy, const double* row_scale, double variance, double* out, double* rows_out,
+                                 void* stream);
 
 /* One whole hyper-gradient step of the adjoint estimator in one call: replaces the body of efgpnd_gradient_batched
  * (efgpnd.py:95-262) for the built-in kernels on one GPU -- efgp_spectral_weights | plans | efgp_nufft_type1_pair |
