@@ -20,8 +20,9 @@ import math
 import os
 import time
 import warnings
+from functools import partial
 from math import prod
-from typing import Dict, Optional, Tuple, Union
+from typing import Dict, NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -476,14 +477,81 @@ def _builtin_kernel_constants(kernel):
     return None if kc is None else (kc, float(ell), float(var))
 
 
+def _jacobi_diag(ws, v, sig):
+    """The Jacobi diagonal v[0] |ws|^2 + sigma^2 (:128-133) from the launch every solve of a model takes it from
+    (efgp_gradient_prepare): a diagonal that differs in the last bit sends a CG run that ends at its iteration cap (ill-conditioned
+    D T D) to a visibly different iterate.  Callers that also need rhs = D F*y make their one `gradient_prepare` call themselves."""
+    cidx = _center_flat(v)
+    return gradient_prepare(ws, None, v.reshape(-1)[cidx:cidx + 1], sig, want_diag=True, want_rhs=False)[0]
+
+
+def _variance_hyper(kernel, variance_idx):
+    """Host value of the kernel's `variance` hyper-parameter; 1.0 for a kernel that has none (variance_idx None)."""
+    if variance_idx is None:
+        return 1.0
+    if hasattr(kernel, "get_hypers"):
+        return dict(zip(kernel.hypers, kernel.get_hypers()))["variance"]
+    return float(kernel.get_hyper("variance"))
+
+
+class _StageClock:
+    """Host clock of a gradient step's stages, under the reference's stage names and their roctx ranges: `lap(name, ...)` ends the
+    named stages.  sync (do_profiling): the device is synchronised at every stage boundary, which makes the times device-accurate
+    and is not free."""
+
+    __slots__ = ("dev", "sync", "stages", "_tic", "_ranges")          # a step laps ten times and is bound by host time
+
+    def __init__(self, dev, sync):
+        self.dev, self.sync, self.stages = dev, sync, {}
+        self._tic = time.perf_counter()
+        self._ranges = _StageRanges("efgpnd_gradient_batched", "0_book_keeping")
+
+    def __call__(self, *names):
+        stages, ranges = self.stages, self._ranges
+        for name in names:
+            if self.sync:
+                torch.cuda.synchronize(self.dev)
+            now = time.perf_counter()
+            stages[name] = stages.get(name, 0.0) + (now - self._tic)
+            self._tic = now
+            if ranges.enabled:
+                ranges.lap(name)
+
+    def close(self):
+        if self.sync:
+            print("\n===== stage timings for efgpnd_gradient_batched (seconds) =====")
+            for name, sec in self.stages.items():
+                print(f"  {name:28s} {sec:.6f}")
+        self._ranges.close()
+
+
+class _TailResult(NamedTuple):
+    """What steps 4-8 of a gradient step hand to `_gradient_finish`, whichever tail ran them."""
+    out_vec: Optional[torch.Tensor]     # grad | term1 | term2 | y.alpha in ONE device vector (the next four are views of it), or None
+    grad: torch.Tensor
+    term1: torch.Tensor
+    term2: torch.Tensor
+    y_alpha: object                     # 0-dim device tensor or host float
+    beta: torch.Tensor                  # the mean solve's solution: the next step's warm start
+    mean_iters: object                  # iteration counts: they stay on the device until somebody reads them
+    trace_iters: object
+    n_rhs: int
+    warm: bool
+
+    @classmethod
+    def of_vector(cls, out, nh, *rest):
+        """From the output vector of efgp_gradient_assemble / efgp_gradient_step over nh = H + 1 parameters."""
+        return cls(out, out[:nh], out[nh:2 * nh], out[2 * nh:3 * nh], out[3 * nh], *rest)
+
+
 _NO_ONE_CALL_STEP = set()          # (device, d, mtot) whose solves are not single launches: efgp_gradient_step said so once
 
 
 def _gradient_one_call(kernel, grid, xd, yd, points, sig, N, cg_tol, early_stopping, mean_cg_init, use_mean_pc, use_trace_pc, tight,
                        nufft_eps, T, trace_idx, variance_idx, probe_seed, y_norm_sq, dev):
     """The whole adjoint-estimator step in one library call (efgp_hip.gradient_step) when it applies: built-in kernel, one GPU,
-    generated probes, a circulant grid whose solves are single launches.  Returns what `_gradient_tail_native` returns, or None
-    (nothing enqueued that matters) and the caller drives the entry points itself."""
+    generated probes, a circulant grid whose solves are single launches.  Returns a `_TailResult` as `_gradient_tail_native` does,
+    or None (nothing enqueued that matters) and the caller drives the entry points itself."""
     if grid.ard:                       # the one-call step evaluates the isotropic weights itself
         return None
     key = (dev.index, grid.d, grid.mtot)
@@ -509,7 +577,7 @@ def _gradient_one_call(kernel, grid, xd, yd, points, sig, N, cg_tol, early_stopp
         _NO_ONE_CALL_STEP.add(key)
         return None
     out, beta, mean_iters, trace_iters = res
-    return out, out[:3], out[3:6], out[6:9], out[9], beta, mean_iters, trace_iters, 2 * T, warm
+    return _TailResult.of_vector(out, 3, beta, mean_iters, trace_iters, 2 * T, warm)
 
 
 def _domain_length(xd: torch.Tensor, shards: PointShards) -> float:
@@ -523,6 +591,33 @@ def _domain_sides(xd: torch.Tensor, shards: PointShards):
     lo, hi = torch.aminmax(xd, dim=0)
     lo, hi = shards.minmax(lo, hi)
     return [float(v) for v in (hi - lo).tolist()]
+
+
+def _box_L(sides, ard):
+    """What a `_Grid` takes as L, from the sides of the bounding box: every side for the per-axis grid of an ARD kernel, the longest
+    otherwise; a box without extent counts as 1."""
+    def clamp(v):
+        return v if v > 1e-9 else 1.0
+    return [clamp(float(v)) for v in sides] if ard else clamp(max(sides))
+
+
+def _points_box(xd, shards, ard):
+    """`_box_L` of a model's points.  On a sharded model the longest side is all-reduced first and, for an ARD kernel, the sides
+    after it: every rank goes through the same collectives in this order."""
+    L = _box_L([_domain_length(xd, shards)], False)
+    return _box_L(_domain_sides(xd, shards), True) if ard else L
+
+
+def _kernel_by_name(name, dimension):
+    """The built-in kernel a model's `kernel` string names (case-insensitive)."""
+    from kernels.matern import Matern
+    from kernels.squared_exponential import SquaredExponential
+    key = name.lower()
+    if key in ("squaredexponential", "se"):
+        return SquaredExponential(dimension=dimension)
+    if key in ("matern12", "matern32", "matern52"):
+        return Matern(dimension=dimension, nu={"matern12": 0.5, "matern32": 1.5, "matern52": 2.5}[key])
+    raise ValueError(f"Unknown kernel type: {name}")
 
 
 def _normal_equations(plan: NufftPlan, yd, grid: _Grid, shards: PointShards):
@@ -597,73 +692,13 @@ def efgpnd_gradient_batched(
     if trace_mode not in ("adjoint", "reference"):
         raise ValueError(f"trace_mode must be 'adjoint' or 'reference', got {trace_mode!r}")
     adjoint = trace_mode == "adjoint"
-    num_hypers = kernel.num_hypers
     if cg_tol is None:
         cg_tol = eps
-    out_device = device or x.device
-    rdtype = x.dtype
-    stages: Dict[str, float] = {}
-    tic = [time.perf_counter()]
-    ranges = _StageRanges("efgpnd_gradient_batched", "0_book_keeping")
-
-    def lap(name):
-        if do_profiling:                      # device-accurate stage times only when asked: a sync per stage is not free
-            torch.cuda.synchronize(dev)
-        now = time.perf_counter()
-        stages[name] = stages.get(name, 0.0) + (now - tic[0])
-        tic[0] = now
-        ranges.lap(name)
-
-    def finish():
-        """Diagnostics, the optional log marginal likelihood and the returned gradient (reads the enclosing step's results)."""
-        if stats_out is not None:
-            stats_out.update({
-                # iteration counts of the asynchronous solves stay on the device until somebody reads them (int(...), comparison,
-                # formatting all do): two blocking device-to-host copies per step otherwise
-                "mean_cg_iters": mean_iters,
-                "trace_cg_iters": trace_iters,
-                "trace_num_rhs": int(n_rhs),
-                "feature_count": int(M),
-                **({} if grid.ard else {"mtot": grid.mtot}),
-                "shape": tuple(grid.shape),
-                "hs": tuple(grid.hs),
-                "trace_samples": int(trace_samples),
-                "mean_cg_warm_start_used": bool(warm),
-                "mean_cg_preconditioned": bool(use_mean_cg_preconditioner),
-                "trace_cg_preconditioned": bool(use_trace_cg_preconditioner),
-                "stage_sec": dict(stages),
-            })
-            stats_out["mean_beta"] = beta_raw.to(out_device)
-            if fused:
-                # grad | term1 | term2 | y.alpha live in one device vector: ONE read-back serves the diagnostics and the caller's
-                # host copy of the gradient (EFGPND.compute_gradients)
-                nh_ = int(term1.numel())
-                host_out = out_vec.cpu()
-                stats_out["term1"] = host_out[nh_:2 * nh_].clone()
-                stats_out["term2"] = host_out[2 * nh_:3 * nh_].clone()
-                stats_out["grad_host"] = host_out[:nh_].clone()
-            else:
-                stats_out["term1"] = term1.detach().cpu()
-                stats_out["term2"] = term2.detach().cpu()
-
-        log_marginal = None
-        if compute_log_marginal:
-            det_term = logdet_slq(ws, sig, top, probes=log_marginal_probes, steps=log_marginal_steps,
-                                  dtype=torch.float64, device=dev, n=N, probe_vectors=log_marginal_probe_vectors)
-            log_marginal = torch.tensor(-0.5 * float(y_alpha) - 0.5 * det_term - 0.5 * N * math.log(TWO_PI), dtype=rdtype)
-            lap("9_log_marginal_likelihood")
-
-        if do_profiling:
-            print("\n===== stage timings for efgpnd_gradient_batched (seconds) =====")
-            for k_, v_ in stages.items():
-                print(f"  {k_:28s} {v_:.6f}")
-
-        ranges.close()
-        g_out = grad.to(device=out_device, dtype=rdtype)
-        return (g_out, log_marginal) if compute_log_marginal else g_out
 
     # 0) book keeping -------------------------------------------------------------------------
+    out_device = device or x.device
     dev = compute_device(y if raster is not None else x, device=device)
+    lap = _StageClock(dev, do_profiling)
     shards = shards or PointShards(enabled=False)
     yd = y.detach().to(device=dev, dtype=torch.float64).contiguous()
     if raster is not None:
@@ -680,8 +715,7 @@ def efgpnd_gradient_batched(
         N_local, d = xd.shape
         N = int(shards.sum_scalars([N_local], dev)[0]) if shards.active else N_local
     if hasattr(kernel, "ard_kind"):
-        L = [float(v) for v in domain_length] if domain_length is not None else _domain_sides(xd, shards)
-        L = [v if v > 1e-9 else 1.0 for v in L]
+        L = _box_L(domain_length if domain_length is not None else _domain_sides(xd, shards), True)
     else:
         L = float(domain_length) if domain_length is not None else _domain_length(xd, shards)
     sig = float(sigmasq.detach()) if torch.is_tensor(sigmasq) else float(sigmasq)
@@ -689,13 +723,14 @@ def efgpnd_gradient_batched(
         sig = max(sig, float(noise_floor))
     kernel_hypers = list(getattr(kernel, "hypers", []))
     variance_idx = kernel_hypers.index("variance") if "variance" in kernel_hypers else None
-    kernel_hyper_count = num_hypers - 1
+    kernel_hyper_count = kernel.num_hypers - 1
     trace_idx = [i for i in range(kernel_hyper_count) if i != variance_idx]
+    T = int(trace_samples)
+    echo = (T, bool(use_mean_cg_preconditioner), bool(use_trace_cg_preconditioner))          # what the statistics repeat
     lap("0_book_keeping")
 
     # 1) frequency grid -----------------------------------------------------------------------
     grid = _Grid(kernel, eps, L, d, dev, want_grad=True, defer_weights=True)
-    M = grid.M
     if mean_cg_init_shape is not None and tuple(mean_cg_init_shape) != tuple(grid.shape):
         mean_cg_init = None                   # a start vector of another block with the same mode count is no warm start
     lap("1_frequency_grid_setup")
@@ -710,20 +745,16 @@ def efgpnd_gradient_batched(
     # Everything from here to the assembled gradient in ONE library call when the step is the common one (adjoint estimator, built-in
     # kernel, one GPU, generated probes, single-launch solves): the ~15 entry points cost more host time driven from Python than
     # their kernels take on the device (csrc/gradient_step.cpp).  Stage timers then carry the whole call under "4_solve_cg".
-    one_call = None
+    res = None
     if (raster is None and adjoint and not pointwise_alpha and not shards.active and probes_Z is None and probes_V is None and not do_profiling
             and not compute_log_marginal and os.environ.get("EFGP_NO_FUSED_GRADIENT") is None and dev.type == "cuda"):
-        one_call = _gradient_one_call(kernel, grid, xd, yd, points, sig, N, cg_tol, early_stopping, mean_cg_init,
-                                      use_mean_cg_preconditioner, use_trace_cg_preconditioner, tight, nufft_eps, int(trace_samples),
-                                      trace_idx, variance_idx, probe_seed, y_norm_sq, dev)
-    if one_call is not None:
-        fused = True
-        for name in ("2_nufft_setup", "3_toeplitz_setup"):
-            lap(name)
-        (out_vec, grad, term1, term2, y_alpha, beta_raw, mean_iters, trace_iters, n_rhs, warm) = one_call
-        for name in ("4_solve_cg", "5_compute_term2", "6_monte_carlo_trace", "7_batch_cg_solve", "7.5_compute_alpha", "8_gradient_calculation"):
-            lap(name)
-        return finish()
+        res = _gradient_one_call(kernel, grid, xd, yd, points, sig, N, cg_tol, early_stopping, mean_cg_init,
+                                 use_mean_cg_preconditioner, use_trace_cg_preconditioner, tight, nufft_eps, T, trace_idx, variance_idx,
+                                 probe_seed, y_norm_sq, dev)
+    if res is not None:
+        lap("2_nufft_setup", "3_toeplitz_setup", "4_solve_cg", "5_compute_term2", "6_monte_carlo_trace", "7_batch_cg_solve",
+            "7.5_compute_alpha", "8_gradient_calculation")
+        return _gradient_finish(res, grid, lap, stats_out, echo, out_device, x.dtype)
     if raster is not None:               # exact transforms: one plan serves the pair and the probes
         plan = plan_p = RasterPlan(raster[0], grid.plan_h, cell_scale=raster[1], _scale_checked=True)
     else:
@@ -734,148 +765,196 @@ def efgpnd_gradient_batched(
     # 3) Toeplitz operator, Jacobi diagonal (F*y rides in the same pass over the points) --------
     Fy, v = _normal_equations(plan, yd, grid, shards)
     grid.make_weights()                      # behind the pass over the points: the device is busy while the host sets them up
-    ws, Dp = grid.ws, grid.dprime
+    Dp = grid.dprime
     top = ToeplitzOp(v)
     # The M-scale tail in native launches when the estimator is the adjoint one: prepare | solve | T g | probes, two scaled
     # Toeplitz products | batched solve | assemble -- about 35 launches per step instead of 118 (the step was bound by the host
-    # enqueueing 3 us torch kernels on 529-element vectors).  The literal / pointwise modes keep the torch sequence below.
-    fused = (adjoint and not pointwise_alpha and kernel_hyper_count <= 4 and Dp is not None and Dp.ndim == 2
-             and Dp.shape[1] == kernel_hyper_count and os.environ.get("EFGP_NO_FUSED_GRADIENT") is None)
-    if fused:
-        lap("3_toeplitz_setup")
-        (out_vec, grad, term1, term2, y_alpha, beta_raw, mean_iters, trace_iters, n_rhs, warm) = _gradient_tail_native(
-            kernel, grid, top, Fy, v, sig, N, N_local, cg_tol, early_stopping, mean_cg_init, use_mean_cg_preconditioner,
-            use_trace_cg_preconditioner, plan_p, shards, dev, int(trace_samples), trace_idx, variance_idx, probes_Z, probes_V,
-            probe_seed, y_norm_sq, yd, lap)
+    # enqueueing 3 us torch kernels on 529-element vectors).  The literal / pointwise modes keep the torch sequence.
+    native = (adjoint and not pointwise_alpha and kernel_hyper_count <= 4 and Dp is not None and Dp.ndim == 2
+              and Dp.shape[1] == kernel_hyper_count and os.environ.get("EFGP_NO_FUSED_GRADIENT") is None)
+    tail = _gradient_tail_native if native else partial(_gradient_tail_torch, adjoint=adjoint, pointwise_alpha=pointwise_alpha)
+    res = tail(kernel, grid, top, Fy, v, sig, N, N_local, cg_tol, early_stopping, mean_cg_init, use_mean_cg_preconditioner,
+               use_trace_cg_preconditioner, plan_p, shards, dev, T, trace_idx, variance_idx, probes_Z, probes_V, probe_seed, y_norm_sq,
+               yd, lap)
+    logdet = None
+    if compute_log_marginal:
+        logdet = partial(logdet_slq, grid.ws, sig, top, probes=log_marginal_probes, steps=log_marginal_steps, dtype=torch.float64,
+                         device=dev, n=N, probe_vectors=log_marginal_probe_vectors)
+    return _gradient_finish(res, grid, lap, stats_out, echo, out_device, x.dtype, N, logdet)
+
+
+def _gradient_finish(res, grid, lap, stats_out, echo, out_device, rdtype, N=None, logdet=None):
+    """Diagnostics, the optional log marginal likelihood and the returned gradient of a step whose tail returned `res`.  `echo`: the
+    settings of the step that its statistics repeat (trace samples, mean and trace solves preconditioned); `logdet`: the call that
+    gives log det(K + sigma^2 I) when the log marginal likelihood of the N observations is wanted, else None."""
+    if stats_out is not None:
+        stats_out.update({
+            # iteration counts of the asynchronous solves stay on the device until somebody reads them (int(...), comparison,
+            # formatting all do): two blocking device-to-host copies per step otherwise
+            "mean_cg_iters": res.mean_iters,
+            "trace_cg_iters": res.trace_iters,
+            "trace_num_rhs": int(res.n_rhs),
+            "feature_count": int(grid.M),
+            **({} if grid.ard else {"mtot": grid.mtot}),
+            "shape": tuple(grid.shape),
+            "hs": tuple(grid.hs),
+            "trace_samples": echo[0],
+            "mean_cg_warm_start_used": bool(res.warm),
+            "mean_cg_preconditioned": echo[1],
+            "trace_cg_preconditioned": echo[2],
+            "stage_sec": dict(lap.stages),
+        })
+        stats_out["mean_beta"] = res.beta.to(out_device)
+        if res.out_vec is not None:
+            # grad | term1 | term2 | y.alpha live in one device vector: ONE read-back serves the diagnostics and the caller's
+            # host copy of the gradient (EFGPND.compute_gradients)
+            nh = int(res.term1.numel())
+            host_out = res.out_vec.cpu()
+            stats_out["term1"] = host_out[nh:2 * nh].clone()
+            stats_out["term2"] = host_out[2 * nh:3 * nh].clone()
+            stats_out["grad_host"] = host_out[:nh].clone()
+        else:
+            stats_out["term1"] = res.term1.detach().cpu()
+            stats_out["term2"] = res.term2.detach().cpu()
+    log_marginal = None
+    if logdet is not None:
+        log_marginal = torch.tensor(-0.5 * float(res.y_alpha) - 0.5 * logdet() - 0.5 * N * math.log(TWO_PI), dtype=rdtype)
+        lap("9_log_marginal_likelihood")
+    lap.close()
+    g_out = res.grad.to(device=out_device, dtype=rdtype)
+    return g_out if logdet is None else (g_out, log_marginal)
+
+
+def _gradient_tail_torch(kernel, grid, top, Fy, v, sig, N, N_local, cg_tol, early_stopping, mean_cg_init, use_mean_pc, use_trace_pc,
+                         plan_p, shards, dev, T, trace_idx, variance_idx, probes_Z, probes_V, probe_seed, y_norm_sq, yd, lap, *,
+                         adjoint, pointwise_alpha):
+    """Steps 4-8 of efgpnd_gradient_batched as the reference's own sequence of torch operations: the tests' yardstick, and the only
+    path of trace_mode="reference", of `pointwise_alpha`, and of kernels with more than four hyper-parameters or no `spectral_grad`
+    matrix.  Arguments as `_gradient_tail_native`; the result carries no output vector."""
+    ws, Dp, M = grid.ws, grid.dprime, grid.M
+    num_hypers = kernel.num_hypers
+    kernel_hyper_count = num_hypers - 1
+    diag = _jacobi_diag(ws, v, sig)          # from the launch the native tail takes it from
+    lap("3_toeplitz_setup")
+
+    # 4) mean solve ---------------------------------------------------------------------------
+    rhs = ws * Fy
+    warm = mean_cg_init is not None and tuple(mean_cg_init.shape) == tuple(rhs.shape)
+    b0 = mean_cg_init.detach().to(device=dev, dtype=torch.complex128) if warm else None          # None: the solver starts from zeros it allocates itself (no copy)
+    # rhs = D F*y of the real y (and a warm start from an earlier solve of the same kind): coefficients of real functions
+    beta, mean_iters = cg_solve_lazy(top, ws, sig, 0, rhs, b0, cg_tol, early_stop=early_stopping,
+                                     diag=diag if use_mean_pc else None, batched=False, hermitian=True)
+    mean_iters.settle()
+    beta_raw = beta.clone()
+    beta_s = ws * beta                                        # g = D beta
+    Tg = top.apply(beta_s)
+    if not adjoint:
+        z = plan_p.type2(beta_s, grid.shape)                 # F g, complex (N,)
+        alpha = (yd - z) / sig
+    lap("4_solve_cg")
+
+    # 5) term 2 -------------------------------------------------------------------------------
+    fadj_alpha = (Fy - Tg) / sig                               # = F* alpha without another pass over N
+    term2_kernel = torch.stack([vdot_m(fadj_alpha, Dp[:, i] * fadj_alpha) for i in range(kernel_hyper_count)]) \
+        if kernel_hyper_count else torch.zeros(0, dtype=torch.float64, device=dev)
+    if adjoint:
+        yy = float(y_norm_sq) if y_norm_sq is not None else shards.sum_scalars([vdot_real(yd, yd)], dev)[0]
+        y_z = vdot_m(Fy, beta_s)                               # Re sum_n y_n z_n          (0-dim device tensors:
+        z_z = vdot_m(beta_s, Tg)                               # |F g|^2 = <g, T g>         no host round trip)
+        if pointwise_alpha:
+            zr = plan_p.type2(beta_s, grid.shape, real_only=True)          # Re F g at the N points: one real gather
+            alpha_r = (yd - zr) / sig
+            a_norm, y_alpha = shards.sum_scalars([vdot_real(alpha_r, alpha_r), vdot_real(yd, alpha_r)], dev)
+        else:
+            a_norm = (yy - 2.0 * y_z + z_z) / (sig * sig)
+            y_alpha = (yy - y_z) / sig
     else:
-        # the Jacobi diagonal v[0] |ws|^2 + sigma^2 (:128-133) from the same launch as the native tail: a diagonal that differs in
-        # the last bit sends a CG run that ends at its iteration cap (ill-conditioned D T D) to a visibly different iterate
-        diag = gradient_prepare(ws, None, v.reshape(-1)[_center_flat(v):_center_flat(v) + 1], sig, want_rhs=False)[0]
-        lap("3_toeplitz_setup")
+        a_norm, y_alpha = shards.sum_scalars([vdot_real(alpha, alpha), vdot_real(yd, alpha)], dev)
+    variance = _variance_hyper(kernel, variance_idx)
+    if variance_idx is not None:
+        term2_kernel[variance_idx] = (y_alpha - sig * a_norm) / variance
+    term2 = torch.cat((term2_kernel, torch.as_tensor(a_norm, dtype=torch.float64, device=dev).reshape(1)))
+    lap("5_compute_term2")
 
-        # 4) mean solve ---------------------------------------------------------------------------
-        rhs = ws * Fy
-        warm = mean_cg_init is not None and tuple(mean_cg_init.shape) == tuple(rhs.shape)
-        b0 = mean_cg_init.detach().to(device=dev, dtype=torch.complex128) if warm else None          # None: the solver starts from zeros it allocates itself (no copy)
-        # rhs = D F*y of the real y (and a warm start from an earlier solve of the same kind): coefficients of real functions
-        beta, mean_iters = cg_solve_lazy(top, ws, sig, 0, rhs, b0, cg_tol, early_stop=early_stopping,
-                                         diag=diag if use_mean_cg_preconditioner else None, batched=False, hermitian=True)
-        mean_iters.settle()
-        beta_raw = beta.clone()
-        beta_s = ws * beta                                        # g = D beta
-        Tg = top.apply(beta_s)
+    # 6) Monte-Carlo trace probes ---------------------------------------------------------------
+    K = len(trace_idx)
+    Z = None
+    rhs_k = None
+    if K > 0:
+        if probes_Z is not None:
+            Z = probes_Z.detach().to(device=dev, dtype=torch.float64).contiguous()
+            FZ = plan_p.type1(Z, grid.shape).reshape(T, M)                            # real rows, two per pass
+        elif adjoint:
+            if probe_seed is None:
+                probe_seed = shards.shared_seed(dev)              # one draw on rank 0: all shards use one Z stream
+            offset = shards.exclusive_offset(N_local, dev)
+            FZ = plan_p.type1_rademacher(probe_seed, T, grid.shape, index_offset=offset).reshape(T, M)
+        elif shards.active:
+            # sharded literal mode: Z[t, n] from (seed, t, GLOBAL index n) so the shards hold slices of one global
+            # probe matrix (per-rank torch generators would repeat or decorrelate blocks depending on their seeds)
+            if probe_seed is None:
+                probe_seed = shards.shared_seed(dev)
+            Z = rademacher_fill(dev, probe_seed, T, N_local, index_offset=shards.exclusive_offset(N_local, dev))
+            FZ = plan_p.type1(Z, grid.shape).reshape(T, M)
+        else:
+            Z = torch.empty((T, N_local), device=dev, dtype=torch.float64).bernoulli_(0.5).mul_(2).sub_(1)
+            FZ = plan_p.type1(Z, grid.shape).reshape(T, M)
+        shards.sum_(FZ)
+        DFZ = torch.stack([Dp[:, i] * FZ for i in trace_idx], dim=0).reshape(K * T, M)
         if not adjoint:
-            z = plan_p.type2(beta_s, grid.shape)                 # F g, complex (N,)
-            alpha = (yd - z) / sig
-        lap("4_solve_cg")
+            rhs_k = plan_p.type2(DFZ, grid.shape, batched=True)                       # (K*T, N) complex
+        B_k = ws * top.apply(DFZ)
+    else:
+        DFZ = torch.empty((0, M), dtype=torch.complex128, device=dev)
+        B_k = torch.empty((0, M), dtype=torch.complex128, device=dev)
+    if probes_V is not None:
+        V = probes_V.detach().to(device=dev, dtype=torch.float64).contiguous()
+    else:
+        V = torch.empty((T, M), device=dev, dtype=torch.float64).bernoulli_(0.5).mul_(2).sub_(1)
+        shards.broadcast_(V)                                      # replicated solves need ONE draw (rank 0's)
+    Vc = V.to(torch.complex128)
+    B_n = ws * top.apply(ws * Vc)
+    B_all = torch.cat((B_k, B_n), dim=0)
+    lap("6_monte_carlo_trace")
 
-        # 5) term 2 -------------------------------------------------------------------------------
-        fadj_alpha = (Fy - Tg) / sig                               # = F* alpha without another pass over N
-        term2_kernel = torch.stack([vdot_m(fadj_alpha, Dp[:, i] * fadj_alpha) for i in range(kernel_hyper_count)]) \
-            if kernel_hyper_count else torch.zeros(0, dtype=torch.float64, device=dev)
+    # 7) batched CG -----------------------------------------------------------------------------
+    Beta_all, trace_iters = _solve_batched(shards, top, ws, sig, 0, B_all, cg_tol, early_stop=early_stopping,
+                                           diag=diag if use_trace_pc else None)
+    lap("7_batch_cg_solve")
+
+    # 7.5) term 1 -------------------------------------------------------------------------------
+    term1 = torch.empty(num_hypers, dtype=torch.float64, device=dev)
+    Beta_k, Beta_n = Beta_all[:K * T], Beta_all[K * T:]
+    if K > 0:
         if adjoint:
-            yy = float(y_norm_sq) if y_norm_sq is not None else shards.sum_scalars([vdot_real(yd, yd)], dev)[0]
-            y_z = vdot_m(Fy, beta_s)                               # Re sum_n y_n z_n          (0-dim device tensors:
-            z_z = vdot_m(beta_s, Tg)                               # |F g|^2 = <g, T g>         no host round trip)
-            if pointwise_alpha:
-                zr = plan_p.type2(beta_s, grid.shape, real_only=True)          # Re F g at the N points: one real gather
-                alpha_r = (yd - zr) / sig
-                a_norm, y_alpha = shards.sum_scalars([vdot_real(alpha_r, alpha_r), vdot_real(yd, alpha_r)], dev)
-            else:
-                a_norm = (yy - 2.0 * y_z + z_z) / (sig * sig)
-                y_alpha = (yy - y_z) / sig
+            # sum_n Z (F(D'F*Z) - F(ws beta))/sigma^2 = Re <F*Z, D'F*Z - ws beta> / sigma^2   (F*Z is already global)
+            diff = (DFZ - ws * Beta_k).reshape(K, T, M)
+            sums = [(FZ.conj() * diff[slot]).sum().real / sig for slot in range(K)]
         else:
-            a_norm, y_alpha = shards.sum_scalars([vdot_real(alpha, alpha), vdot_real(yd, alpha)], dev)
-        if variance_idx is not None:
-            variance_scalar = float(kernel.get_hyper("variance"))
-            term2_kernel[variance_idx] = (y_alpha - sig * a_norm) / variance_scalar
-        term2 = torch.cat((term2_kernel, torch.as_tensor(a_norm, dtype=torch.float64, device=dev).reshape(1)))
-        lap("5_compute_term2")
+            fwdB = plan_p.type2(ws * Beta_k, grid.shape, batched=True)
+            Alpha = (rhs_k - fwdB) / sig                                            # (K*T, N)
+            sums = [vdot_real(Z, Alpha[s_ * T:(s_ + 1) * T]) for s_ in range(K)]    # sum_t sum_n Z*Alpha
+            sums = shards.sum_scalars(sums, dev)
+        for slot, ki in enumerate(trace_idx):
+            term1[ki] = sums[slot] / T
+    t1_noise = N / sig - ((Vc.conj() * Beta_n).sum(dim=1).real / sig).mean()
+    if variance_idx is not None:
+        term1[variance_idx] = (N - sig * t1_noise) / variance
+    term1[-1] = t1_noise
+    lap("7.5_compute_alpha")
 
-        # 6) Monte-Carlo trace probes ---------------------------------------------------------------
-        T = int(trace_samples)
-        K = len(trace_idx)
-        Z = None
-        rhs_k = None
-        if K > 0:
-            if probes_Z is not None:
-                Z = probes_Z.detach().to(device=dev, dtype=torch.float64).contiguous()
-                FZ = plan_p.type1(Z, grid.shape).reshape(T, M)                            # real rows, two per pass
-            elif adjoint:
-                if probe_seed is None:
-                    probe_seed = shards.shared_seed(dev)              # one draw on rank 0: all shards use one Z stream
-                offset = shards.exclusive_offset(N_local, dev)
-                FZ = plan_p.type1_rademacher(probe_seed, T, grid.shape, index_offset=offset).reshape(T, M)
-            elif shards.active:
-                # sharded literal mode: Z[t, n] from (seed, t, GLOBAL index n) so the shards hold slices of one global
-                # probe matrix (per-rank torch generators would repeat or decorrelate blocks depending on their seeds)
-                if probe_seed is None:
-                    probe_seed = shards.shared_seed(dev)
-                Z = rademacher_fill(dev, probe_seed, T, N_local, index_offset=shards.exclusive_offset(N_local, dev))
-                FZ = plan_p.type1(Z, grid.shape).reshape(T, M)
-            else:
-                Z = torch.empty((T, N_local), device=dev, dtype=torch.float64).bernoulli_(0.5).mul_(2).sub_(1)
-                FZ = plan_p.type1(Z, grid.shape).reshape(T, M)
-            shards.sum_(FZ)
-            DFZ = torch.stack([Dp[:, i] * FZ for i in trace_idx], dim=0).reshape(K * T, M)
-            if not adjoint:
-                rhs_k = plan_p.type2(DFZ, grid.shape, batched=True)                       # (K*T, N) complex
-            B_k = ws * top.apply(DFZ)
-        else:
-            DFZ = torch.empty((0, M), dtype=torch.complex128, device=dev)
-            B_k = torch.empty((0, M), dtype=torch.complex128, device=dev)
-        if probes_V is not None:
-            V = probes_V.detach().to(device=dev, dtype=torch.float64).contiguous()
-        else:
-            V = torch.empty((T, M), device=dev, dtype=torch.float64).bernoulli_(0.5).mul_(2).sub_(1)
-            shards.broadcast_(V)                                      # replicated solves need ONE draw (rank 0's)
-        Vc = V.to(torch.complex128)
-        B_n = ws * top.apply(ws * Vc)
-        B_all = torch.cat((B_k, B_n), dim=0)
-        lap("6_monte_carlo_trace")
+    grad = 0.5 * (term1 - term2)
+    lap("8_gradient_calculation")
 
-        # 7) batched CG -----------------------------------------------------------------------------
-        Beta_all, trace_iters = _solve_batched(shards, top, ws, sig, 0, B_all, cg_tol, early_stop=early_stopping,
-                                               diag=diag if use_trace_cg_preconditioner else None)
-        lap("7_batch_cg_solve")
-
-        # 7.5) term 1 -------------------------------------------------------------------------------
-        term1 = torch.empty(num_hypers, dtype=torch.float64, device=dev)
-        Beta_k, Beta_n = Beta_all[:K * T], Beta_all[K * T:]
-        if K > 0:
-            if adjoint:
-                # sum_n Z (F(D'F*Z) - F(ws beta))/sigma^2 = Re <F*Z, D'F*Z - ws beta> / sigma^2   (F*Z is already global)
-                diff = (DFZ - ws * Beta_k).reshape(K, T, M)
-                sums = [(FZ.conj() * diff[slot]).sum().real / sig for slot in range(K)]
-            else:
-                fwdB = plan_p.type2(ws * Beta_k, grid.shape, batched=True)
-                Alpha = (rhs_k - fwdB) / sig                                            # (K*T, N)
-                sums = [vdot_real(Z, Alpha[s_ * T:(s_ + 1) * T]) for s_ in range(K)]    # sum_t sum_n Z*Alpha
-                sums = shards.sum_scalars(sums, dev)
-            for slot, ki in enumerate(trace_idx):
-                term1[ki] = sums[slot] / T
-        t1_noise = N / sig - ((Vc.conj() * Beta_n).sum(dim=1).real / sig).mean()
-        if variance_idx is not None:
-            term1[variance_idx] = (N - sig * t1_noise) / float(kernel.get_hyper("variance"))
-        term1[-1] = t1_noise
-        lap("7.5_compute_alpha")
-
-        grad = 0.5 * (term1 - term2)
-        lap("8_gradient_calculation")
-
-        n_rhs = int(B_all.shape[0])
-
-    return finish()
+    return _TailResult(None, grad, term1, term2, y_alpha, beta_raw, mean_iters, trace_iters, int(B_all.shape[0]), warm)
 
 
 def _gradient_tail_native(kernel, grid, top, Fy, v, sig, N, N_local, cg_tol, early_stopping, mean_cg_init, use_mean_pc, use_trace_pc,
                           plan_p, shards, dev, T, trace_idx, variance_idx, probes_Z, probes_V, probe_seed, y_norm_sq, yd, lap):
     """Steps 4-8 of efgpnd_gradient_batched (adjoint estimator) in native launches; same quantities, same stage names.
-    Returns (out_vec, grad, term1, term2, y_alpha, beta, mean_iters, trace_iters, n_rhs, warm): out_vec is the device vector
-    grad | term1 | term2 | y.alpha of efgp_gradient_assemble, the next four are views of it."""
+    Returns a `_TailResult` whose output vector is grad | term1 | term2 | y.alpha of efgp_gradient_assemble."""
     ws, Dp, M = grid.ws, grid.dprime, grid.M
-    K = len(trace_idx)
-    H = Dp.shape[1]
+    lap("3_toeplitz_setup")
     # 4) mean solve (reference :128-153): Jacobi diagonal and rhs = D F*y in one launch, solve, T g
     cidx = _center_flat(v)
     diag, rhs = gradient_prepare(ws, Fy, v.reshape(-1)[cidx:cidx + 1], sig, want_diag=use_mean_pc or use_trace_pc)
@@ -887,6 +966,30 @@ def _gradient_tail_native(kernel, grid, top, Fy, v, sig, N, N_local, cg_tol, ear
     lap("4_solve_cg")
     lap("5_compute_term2")                                      # term 2 is part of the assemble launch below
 
+    # 6, 7) probes, the right-hand sides of the trace systems and their batched solve
+    FZ, V, Beta_all, trace_iters = _trace_systems(grid, top, plan_p, sig, cg_tol, early_stopping, diag if use_trace_pc else None, T,
+                                                  trace_idx, shards, N_local, dev, probes_Z, probes_V, probe_seed, lap)
+    # the mean solve is settled only here, where the batched solve has made the host wait already; a re-solved beta needs T g again
+    if mean_iters.settle():
+        Tg = top.apply_scaled(beta, pre=ws)
+    lap("7_batch_cg_solve")
+
+    # 7.5 / 8) every inner product of terms 1 and 2 and the final algebra: two launches, nothing read back
+    yy = float(y_norm_sq) if y_norm_sq is not None else float(shards.sum_scalars([vdot_real(yd, yd)], dev)[0])
+    out = gradient_assemble(Fy, Tg, ws, beta, Dp, FZ, V, Beta_all.reshape(-1, M), variance_idx=variance_idx, trace_idx=trace_idx,
+                            sigmasq=sig, n_obs=N, yy=yy, variance=_variance_hyper(kernel, variance_idx))
+    lap("7.5_compute_alpha", "8_gradient_calculation")
+    return _TailResult.of_vector(out, Dp.shape[1] + 1, beta, mean_iters, trace_iters, Beta_all.shape[0], warm)
+
+
+def _trace_systems(grid, top, plan_p, sig, cg_tol, early_stopping, diag, T, trace_idx, shards, N_local, dev, probes_Z=None,
+                   probes_V=None, probe_seed=None, lap=None):
+    """The trace block of the adjoint estimator, which depends on the points and the hyper-parameters only: T data-space probes Z
+    through F* (for the traced hypers `trace_idx`), T feature-space probes V (for the noise), the (len(trace_idx) + 1) T
+    right-hand sides and their batched solve from zero -> (F*Z (T, M) or None, V (T, M), solutions ((K + 1) T, M), iteration
+    counts).  Draws from torch's generator, in this order: the seed of Z, only when none was given and a hyper is traced; then
+    the seed of V (its T x M entries on a sharded model).  `lap` ends stage 6 between the right-hand sides and the solve."""
+    ws, Dp, M, K = grid.ws, grid.dprime, grid.M, len(trace_idx)
     # 6) probes and the right-hand sides of the trace systems (reference :179-203)
     B_all = torch.empty(((K + 1) * T, M), dtype=torch.complex128, device=dev)
     FZ = None
@@ -896,7 +999,7 @@ def _gradient_tail_native(kernel, grid, top, Fy, v, sig, N, N_local, cg_tol, ear
             FZ = plan_p.type1(Z, grid.shape).reshape(T, M)
         else:
             if probe_seed is None:
-                probe_seed = shards.shared_seed(dev)
+                probe_seed = shards.shared_seed(dev)            # one draw on rank 0: all shards use one Z stream
             FZ = plan_p.type1_rademacher(probe_seed, T, grid.shape, index_offset=shards.exclusive_offset(N_local, dev)).reshape(T, M)
         shards.sum_(FZ)
         for slot, ki in enumerate(trace_idx):                   # D ws-scaled T (D'_i F*Z): D'_i rides in the pad, ws in the crop
@@ -909,28 +1012,11 @@ def _gradient_tail_native(kernel, grid, top, Fy, v, sig, N, N_local, cg_tol, ear
     else:
         V = rademacher_fill(dev, int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()), T, M)
     top.apply_scaled(V, pre=ws, post=ws, out=B_all[K * T:])
-    lap("6_monte_carlo_trace")
-
+    if lap is not None:
+        lap("6_monte_carlo_trace")
     # 7) batched CG from zero (reference :205-236)
-    Beta_all, trace_iters = _solve_batched(shards, top, ws, sig, 0, B_all, cg_tol, early_stop=early_stopping,
-                                           diag=diag if use_trace_pc else None)
-    # the mean solve is settled only here, where the batched solve has made the host wait already; a re-solved beta needs T g again
-    if mean_iters.settle():
-        Tg = top.apply_scaled(beta, pre=ws)
-    lap("7_batch_cg_solve")
-
-    # 7.5 / 8) every inner product of terms 1 and 2 and the final algebra: two launches, nothing read back
-    yy = float(y_norm_sq) if y_norm_sq is not None else float(shards.sum_scalars([vdot_real(yd, yd)], dev)[0])
-    variance = 1.0
-    if variance_idx is not None:
-        variance = dict(zip(kernel.hypers, kernel.get_hypers()))["variance"] if hasattr(kernel, "get_hypers") \
-            else float(kernel.get_hyper("variance"))
-    out = gradient_assemble(Fy, Tg, ws, beta, Dp, FZ, V, Beta_all.reshape(-1, M), variance_idx=variance_idx, trace_idx=trace_idx,
-                            sigmasq=sig, n_obs=N, yy=yy, variance=variance)
-    nh = H + 1
-    lap("7.5_compute_alpha")
-    lap("8_gradient_calculation")
-    return out, out[:nh], out[nh:2 * nh], out[2 * nh:3 * nh], out[3 * nh], beta, mean_iters, trace_iters, (K + 1) * T, warm
+    Beta_all, trace_iters = _solve_batched(shards, top, ws, sig, 0, B_all, cg_tol, early_stop=early_stopping, diag=diag)
+    return FZ, V, Beta_all, trace_iters
 
 
 def _rows_over_ranks(shards, top, R):
@@ -1182,15 +1268,7 @@ class EFGPND(nn.Module):
         dimension = 1 if x.ndim == 1 else x.shape[1]
 
         if isinstance(kernel, str):
-            from kernels.squared_exponential import SquaredExponential
-            from kernels.matern import Matern
-            name = kernel.lower()
-            if name in ("squaredexponential", "se"):
-                kernel = SquaredExponential(dimension=dimension)
-            elif name in ("matern12", "matern32", "matern52"):
-                kernel = Matern(dimension=dimension, nu={"matern12": 0.5, "matern32": 1.5, "matern52": 2.5}[name])
-            else:
-                raise ValueError(f"Unknown kernel type: {kernel}")
+            kernel = _kernel_by_name(kernel, dimension)
         self.kernel = kernel
 
         if estimate_params:
@@ -1383,24 +1461,17 @@ class EFGPND(nn.Module):
             yd = torch.where(obs, r["Y"].detach().to(device=dev, dtype=torch.float64), 0.0).reshape(-1).contiguous()
             mask = None if r["N"] == obs.numel() else obs.to(torch.float64).reshape(-1).contiguous()
             sides = torch.stack([a.max() - a.min() for a in ax]).tolist()          # the axes' extremes, one read-back
-            if hasattr(self.kernel, "ard_kind"):
-                L = [v if v > 1e-9 else 1.0 for v in sides]
-            else:
-                L = max(sides) if max(sides) > 1e-9 else 1.0
+            L = _box_L(sides, hasattr(self.kernel, "ard_kind"))
             yy = self._shards.sum_scalars([vdot_real(yd, yd)], dev)[0]
             self._devdata = dict(dev=dev, x=None, y=yd, L=L, N=r["N"], yy=yy, points=None, passes=0, axes=ax, mask=mask)
         if self._devdata is None:
             dev = compute_device(self.x)
             xd = _dev_points(self.x, dev)
             yd = self.y.detach().to(device=dev, dtype=torch.float64).contiguous()
-            L = _domain_length(xd, self._shards)
-            if L <= 1e-9:
-                L = 1.0
-            if hasattr(self.kernel, "ard_kind"):        # a grid axis per box side (same all-reduced min / max)
-                L = [v if v > 1e-9 else 1.0 for v in _domain_sides(xd, self._shards)]
+            L = _points_box(xd, self._shards, hasattr(self.kernel, "ard_kind"))
             n_glob = int(self._shards.sum_scalars([xd.shape[0]], dev)[0]) if self._shards.active else xd.shape[0]
             yy = self._shards.sum_scalars([vdot_real(yd, yd)], dev)[0]          # global sum of y^2 (gradient, once)
-            self._devdata = dict(dev=dev, x=xd, y=yd, L=L, N=n_glob, yy=yy, points=None, passes=0)
+            self._devdata = dict(dev=dev, x=xd, y=yd, L=L, N=n_glob, yy=yy, points=None, passes=0, layout_values=yd)
         return self._devdata
 
     def _layout(self):
@@ -1417,7 +1488,7 @@ class EFGPND(nn.Module):
         if want is False or dd["x"].shape[0] == 0 or (want == "auto" and dd["passes"] < 2):
             return None
         if dd["points"] is None:
-            dd["points"] = PointSet(dd["x"], values=dd["y"])
+            dd["points"] = PointSet(dd["x"], values=dd["layout_values"])
         return dd["points"]
 
     # -- gradient -----------------------------------------------------------------------------------
@@ -1585,6 +1656,55 @@ class EFGPND(nn.Module):
         return self
 
     # -- predict ---------------------------------------------------------------------------------------
+    def _plan_at(self, xn, nufft_eps):
+        """The plan over the new points `xn`, kept while the same tensor (same storage, same version) comes back with the same
+        grid: predicting at the training points after every refit is the reference's own usage (efgpnd_ex.ipynb cell 23)."""
+        st = self._fit_state
+        pkey = (xn.data_ptr(), tuple(xn.shape), xn._version, st["plan_h"], float(nufft_eps))
+        if self._predict_plan is None or self._predict_plan[0] != pkey:
+            self._predict_plan = (pkey, NufftPlan(xn, st["plan_h"], float(nufft_eps)))
+        return self._predict_plan[1]
+
+    def _nan_like(self, shape):
+        """NaN of `shape`, where no variance was asked for.  The reference fills a (B,) tensor with NaN (efgpnd.py:947): same values
+        as a stride-0 view of ONE NaN, made once per model, without writing 8 B bytes per call (16 us and 80 MB of traffic per
+        predict at N = 1e7)."""
+        rdtype = self.x.dtype
+        if self._nan_scalar is None or self._nan_scalar.device != self.device or self._nan_scalar.dtype != rdtype:
+            self._nan_scalar = torch.full((1,), float("nan"), device=self.device, dtype=rdtype)
+        return self._nan_scalar.expand(shape)
+
+    # What a subclass with other coefficients supplies (EFGPNDMulti): the two means and the log marginal that `predict` appends
+    def _mean_at(self, plan):
+        st = self._fit_state          # the shape is carried explicitly (the reference re-derives it, :908)
+        return plan.type2(st["beta"], st["shape"], real_only=True, mode_scale=st["ws"])     # F (ws * beta), efgpnd.py:919-922
+
+    def _mean_on_raster(self, ax):
+        st = self._fit_state
+        return raster_type2(ax, st["plan_h"], st["shape"], st["beta"], mode_scale=st["ws"])        # F (ws * beta) on the raster
+
+    def _predict_log_marginal(self):
+        st = self._fit_state
+        return self._compute_log_marginal(beta=st["beta"], ws=st["ws"], sigmasq=st["sig"], toeplitz=self._toeplitz,
+                                          device=self._devdata["dev"], rdtype=self.x.dtype, n=self._devdata["N"])
+
+    def _variance_at(self, xn, variance_method, hutchinson_probes, nufft_eps, variance_probes):
+        """The latent variance at the points `xn` (on the compute device); it depends on the points and the hyper-parameters only."""
+        st = self._fit_state
+        rdtype = self.x.dtype
+        if variance_probes is None and self._shards.active and variance_method.lower() == "stochastic":
+            # replicas must estimate the SAME lag sums: rank 0's draw (reference draw: efgpnd.py:1644)
+            variance_probes = (torch.randint(0, 2, (hutchinson_probes, st["ws"].numel()), device=xn.device) * 2 - 1).to(torch.float64)
+            self._shards.broadcast_(variance_probes)
+        A_var = create_A_var(st["ws"], self._toeplitz, st["sig"], torch.complex128)
+        return compute_prediction_variance(
+            x_new=xn, xis=self._xis.to(torch.float64), ws=st["ws"], A_var=A_var,
+            cg_tol=self.opts.get("cg_tolerance", 1e-4), max_cg_iter=self.opts.get("max_cg_iterations", 1000),
+            variance_method=variance_method, h=st["plan_h"], xcen=torch.zeros(xn.shape[1], dtype=torch.float64),
+            hutchinson_probes=hutchinson_probes, nufft_eps=nufft_eps, device=self.device, rdtype=rdtype,
+            cdtype=_cmplx(rdtype), probes=variance_probes, shards=self._shards if self._shards.active else None,
+            shape=st["shape"] if st["ard"] else None)
+
     def predict(self, x_new: torch.Tensor, *, return_variance: bool = True, variance_method: str = "stochastic",
                 hutchinson_probes: int = 1_000, compute_log_marginal: bool = False, force_recompute: bool = False,
                 do_profiling: bool = False, nufft_eps: Optional[float] = None, variance_probes: Optional[torch.Tensor] = None):
@@ -1593,8 +1713,6 @@ class EFGPND(nn.Module):
             raise ValueError("x_new must be provided for prediction")
         self._compute_common_parameters(force_recompute=force_recompute, nufft_eps=nufft_eps)
         st = self._fit_state
-        rdtype = self.x.dtype
-        cdtype = _cmplx(rdtype)
         if nufft_eps is None:
             nufft_eps = self.nufft_eps
         dev = self._devdata["dev"]
@@ -1603,49 +1721,20 @@ class EFGPND(nn.Module):
         if d != st["d"]:
             raise ValueError(f"x_new has {d} columns, the model was built on {st['d']}")
         t0 = time.perf_counter()
-        ranges = _StageRanges("EFGPND.predict", "predict_mean")
-        shape = st["shape"]                             # carried explicitly (the reference re-derives it, :908)
-        # the plan over x_new is kept while the same tensor (same storage, same version) comes back with the same grid:
-        # predicting at the training points after every refit is the reference's own usage (efgpnd_ex.ipynb cell 23)
-        pkey = (xn.data_ptr(), tuple(xn.shape), xn._version, st["plan_h"], float(nufft_eps))
-        if self._predict_plan is not None and self._predict_plan[0] == pkey:
-            plan = self._predict_plan[1]
-        else:
-            plan = NufftPlan(xn, st["plan_h"], float(nufft_eps))
-            self._predict_plan = (pkey, plan)
-        mean = plan.type2(st["beta"], shape, real_only=True, mode_scale=st["ws"])     # F (ws * beta), efgpnd.py:919-922
-        out_mean = mean.to(device=self.device, dtype=rdtype)
+        ranges = _StageRanges(f"{type(self).__name__}.predict", "predict_mean")
+        out_mean = self._mean_at(self._plan_at(xn, nufft_eps)).to(device=self.device, dtype=self.x.dtype)
         t1 = time.perf_counter()
         if return_variance:
             ranges.stage("compute_variance")
-            if variance_probes is None and self._shards.active and variance_method.lower() == "stochastic":
-                # replicas must estimate the SAME lag sums: rank 0's draw (reference draw: efgpnd.py:1644)
-                variance_probes = (torch.randint(0, 2, (hutchinson_probes, st["ws"].numel()), device=dev) * 2 - 1).to(torch.float64)
-                self._shards.broadcast_(variance_probes)
-            A_var = create_A_var(st["ws"], self._toeplitz, st["sig"], torch.complex128)
-            var = compute_prediction_variance(
-                x_new=xn, xis=self._xis.to(torch.float64), ws=st["ws"], A_var=A_var,
-                cg_tol=self.opts.get("cg_tolerance", 1e-4), max_cg_iter=self.opts.get("max_cg_iterations", 1000),
-                variance_method=variance_method, h=st["plan_h"], xcen=torch.zeros(d, dtype=torch.float64),
-                hutchinson_probes=hutchinson_probes, nufft_eps=nufft_eps, device=self.device, rdtype=rdtype,
-                cdtype=cdtype, probes=variance_probes, shards=self._shards if self._shards.active else None,
-                shape=st["shape"] if st["ard"] else None)
+            var = self._variance_at(xn, variance_method, hutchinson_probes, nufft_eps, variance_probes)
         else:
-            # the reference fills a (B,) tensor with NaN (efgpnd.py:947): same values as a stride-0 view of ONE NaN, without
-            # writing 8 B bytes per call (16 us and 80 MB of traffic per predict at N = 1e7)
-            if self._nan_scalar is None or self._nan_scalar.device != self.device or self._nan_scalar.dtype != rdtype:
-                self._nan_scalar = torch.full((1,), float("nan"), device=self.device, dtype=rdtype)     # once per model
-            var = self._nan_scalar.expand(B)
+            var = self._nan_like((B,))
         t2 = time.perf_counter()
         ranges.close()
         if do_profiling:
             torch.cuda.synchronize(dev)
             print(f"predict_mean {t1 - t0:.6f}s  compute_variance {t2 - t1:.6f}s")
-        if compute_log_marginal:
-            lm = self._compute_log_marginal(beta=st["beta"], ws=st["ws"], sigmasq=st["sig"], toeplitz=self._toeplitz,
-                                            device=dev, rdtype=rdtype, n=self._devdata["N"])
-            return out_mean, var, lm
-        return out_mean, var
+        return (out_mean, var, self._predict_log_marginal()) if compute_log_marginal else (out_mean, var)
 
     # -- function draws ----------------------------------------------------------------------------------
     @property
@@ -1685,10 +1774,7 @@ class EFGPND(nn.Module):
                 self._sample_plan = sp = ((st["plan_h"], tol1), NufftPlan(self._devdata["x"], st["plan_h"], tol1, points=points), points)
             plan_x = sp[1]
             max_iter = int(self.opts.get("max_cg_iterations", 1000))
-            diag = None
-            if self.opts.get("mean_cg_preconditioner", True):
-                cidx = _center_flat(st["v"])
-                diag, _ = gradient_prepare(st["ws"], None, st["v"].reshape(-1)[cidx:cidx + 1], sig, want_diag=True, want_rhs=False)
+            diag = _jacobi_diag(st["ws"], st["v"], sig) if self.opts.get("mean_cg_preconditioner", True) else None
             sroot = math.sqrt(sig)
         outs = []
         for r0 in range(0, nsamples, block):
@@ -1768,13 +1854,8 @@ class EFGPND(nn.Module):
         dev = self._devdata["dev"]
         xn = _dev_points(x_new, dev)
         shape = st["shape"]
-        pkey = (xn.data_ptr(), tuple(xn.shape), xn._version, st["plan_h"], float(self.nufft_eps))
-        if self._predict_plan is not None and self._predict_plan[0] == pkey:
-            plan_new = self._predict_plan[1]
-        else:
-            plan_new = NufftPlan(xn, st["plan_h"], float(self.nufft_eps))
-            self._predict_plan = (pkey, plan_new)
-        keep = dict(weights=[], delta=[], rhs=[]) if return_state else None
+        plan_new = self._plan_at(xn, self.nufft_eps)
+        keep =dict(weights=[], delta=[], rhs=[]) if return_state else None
         outs, max_iter, tol = self._draw_weight_blocks(
             nsamples, prior, seed, cg_tolerance, keep,
             lambda w: plan_new.type2(w, shape, real_only=True, batched=True, mode_scale=st["ws"]))
@@ -1816,17 +1897,17 @@ class EFGPND(nn.Module):
         return_variance=False returns NaN of the raster's shape as a stride-0 view."""
         axes = self._grid_axes(axes, "predict_grid")
         self._compute_common_parameters(force_recompute=force_recompute)
-        st = self._fit_state
-        rdtype = self.x.dtype
-        dev = self._devdata["dev"]
-        ax = [a.to(dev) for a in axes]
+        ax = [a.to(self._devdata["dev"]) for a in axes]
         n_axis = tuple(int(a.numel()) for a in ax)
-        mean = raster_type2(ax, st["plan_h"], st["shape"], st["beta"], mode_scale=st["ws"])        # F (ws * beta) on the raster
-        out_mean = mean.to(device=self.device, dtype=rdtype)
+        out_mean = self._mean_on_raster(ax).to(device=self.device, dtype=self.x.dtype)
         if not return_variance:
-            if self._nan_scalar is None or self._nan_scalar.device != self.device or self._nan_scalar.dtype != rdtype:
-                self._nan_scalar = torch.full((1,), float("nan"), device=self.device, dtype=rdtype)
-            return out_mean, self._nan_scalar.expand(n_axis)
+            return out_mean, self._nan_like(n_axis)
+        return out_mean, self._variance_on_raster(ax, n_axis, variance_method, hutchinson_probes, variance_probes)
+
+    def _variance_on_raster(self, ax, n_axis, variance_method, hutchinson_probes, variance_probes):
+        """The latent variance map of `predict_grid` on the raster of the device axes `ax` (n_axis cells per axis)."""
+        st = self._fit_state
+        dev = self._devdata["dev"]
         A_var = create_A_var(st["ws"], self._toeplitz, st["sig"], torch.complex128)
         cg_tol, max_it = self.opts.get("cg_tolerance", 1e-4), self.opts.get("max_cg_iterations", 1000)
         shape = st["shape"] if st["ard"] else None
@@ -1851,7 +1932,7 @@ class EFGPND(nn.Module):
             var = torch.cat(parts).reshape(n_axis)
         else:
             raise ValueError(f"Variance method '{variance_method}' not implemented. Choose 'regular' or 'stochastic'.")
-        return out_mean, var.to(device=self.device, dtype=rdtype)
+        return var.to(device=self.device, dtype=self.x.dtype)
 
     def sample_paths_grid(self, axes, nsamples: int, *, prior: bool = False, seed: Optional[int] = None,
                           cg_tolerance: Optional[float] = None):

@@ -18,15 +18,13 @@ Out of scope: per-output missing data or noise levels, gridded and sharded multi
 from __future__ import annotations
 
 import math
-from math import prod
 from typing import Dict, Optional
 
 import torch
 
-from efgp_hip import NufftPlan, PointSet, cg_solve_lazy, compute_device, gradient_assemble_multi, gradient_prepare, rademacher_fill, raster_type2
-from efgp_hip.dist import PointShards
-from efgpnd import (EFGPND, ToeplitzND, _CONV_TOL, _Grid, _SAMPLE_BLOCK, _StageRanges, _center_flat, _cmplx, _dev_points, _domain_length,
-                    _domain_sides, _solve_batched, compute_prediction_variance, create_A_var, diag_sums_nd, logdet_slq)
+from efgp_hip import NufftPlan, cg_solve_lazy, compute_device, gradient_assemble_multi, raster_type2
+from efgpnd import (EFGPND, ToeplitzND, _CONV_TOL, _Grid, _SAMPLE_BLOCK, _dev_points, _jacobi_diag, _kernel_by_name, _points_box,
+                    _trace_systems, _variance_hyper, logdet_slq)
 
 TWO_PI = 2.0 * math.pi
 _ESTIMATE_COLUMNS = 8          # columns the initial hyper-parameter estimate looks at
@@ -81,15 +79,7 @@ class EFGPNDMulti(EFGPND):
                              "would break the operator the outputs share)")
         dimension = 1 if x.ndim == 1 else x.shape[1]
         if isinstance(kernel, str):
-            from kernels.matern import Matern
-            from kernels.squared_exponential import SquaredExponential
-            name = kernel.lower()
-            if name in ("squaredexponential", "se"):
-                kernel = SquaredExponential(dimension=dimension)
-            elif name in ("matern12", "matern32", "matern52"):
-                kernel = Matern(dimension=dimension, nu={"matern12": 0.5, "matern32": 1.5, "matern52": 2.5}[name])
-            else:
-                raise ValueError(f"Unknown kernel type: {kernel}")
+            kernel = _kernel_by_name(kernel, dimension)
         if estimate_params:
             try:
                 ls, var, noise = self._estimate(kernel, x, Y)
@@ -142,7 +132,8 @@ class EFGPNDMulti(EFGPND):
 
     # -- device data ----------------------------------------------------------------------------------------------------------------
     def _device_data(self):
-        """Points, the (B, N) rows in units of 2^e_b each, the scales and |row|^2, the box: made once per model."""
+        """Points, the (B, N) rows in units of 2^e_b each, the scales and |row|^2, the box: made once per model.  The point layout
+        (`EFGPND._layout`) carries no target values: the rows go through `type1`, which takes them in point order."""
         if self._devdata is None:
             dev = compute_device(self.x)
             xd = _dev_points(self.x, dev)
@@ -151,29 +142,28 @@ class EFGPNDMulti(EFGPND):
             expo = torch.frexp(amax.cpu())[1].clamp(-1021, 1023)          # B numbers, once per model: on the host
             scale = torch.ldexp(torch.ones(expo.shape, dtype=torch.float64), expo).to(dev)      # 2^e_b > max|y_b| (1 for a zero column)
             rows = (Yd / scale[None, :]).T.contiguous()                   # division by a power of two: exact
-            shards = PointShards(enabled=False)
-            L = _domain_length(xd, shards)
-            if L <= 1e-9:
-                L = 1.0
-            if hasattr(self.kernel, "ard_kind"):
-                L = [v if v > 1e-9 else 1.0 for v in _domain_sides(xd, shards)]
+            L = _points_box(xd, self._shards, hasattr(self.kernel, "ard_kind"))
             zero = (amax == 0)
             self._devdata = dict(dev=dev, x=xd, y=rows, scale=scale.contiguous(), yy=(rows * rows).sum(dim=1).contiguous(), L=L,
-                                 N=xd.shape[0], points=None, passes=0, zero=zero, zero_host=[bool(z) for z in zero.tolist()])
+                                 N=xd.shape[0], points=None, passes=0, layout_values=None, zero=zero,
+                                 zero_host=[bool(z) for z in zero.tolist()])
         return self._devdata
 
-    def _layout(self):
-        """As EFGPND._layout, without target values attached (the rows go through `type1`, which takes them in point order)."""
-        dd = self._device_data()
-        want = self.opts.get("point_layout", "auto")
-        dd["passes"] += 1
-        if want is False or dd["x"].shape[0] == 0 or (want == "auto" and dd["passes"] < 2):
-            return None
-        if dd["points"] is None:
-            dd["points"] = PointSet(dd["x"])
-        return dd["points"]
-
     # -- the batched pieces -----------------------------------------------------------------------------------------------------------
+    def _shared_operator(self, grid, sig, nufft_eps, want_diag, probe_plan=False):
+        """What depends on x only, once for all outputs: the plan at the Toeplitz vector's tolerance (and, with probe_plan, the one
+        at nufft_eps for the trace probes when that is looser), the Toeplitz vector from a ones-only pass, the operator and the
+        Jacobi diagonal.  Counts as a pass over the points (`_layout`).  -> (plan, plan_p, v, toeplitz, diag)"""
+        xd = self._device_data()["x"]
+        tight = min(float(nufft_eps), _CONV_TOL) if nufft_eps else _CONV_TOL
+        points = self._layout()
+        plan = plan_p = NufftPlan(xd, grid.plan_h, tight, points=points)
+        if probe_plan and nufft_eps and float(nufft_eps) > tight:
+            plan_p = NufftPlan(xd, grid.plan_h, float(nufft_eps), points=points)
+        v = plan.type1_ones(tuple(2 * n - 1 for n in grid.shape))
+        toeplitz = ToeplitzND(v, force_pow2=True)
+        return plan, plan_p, v, toeplitz, _jacobi_diag(grid.ws, v, sig) if want_diag else None
+
     def _solve_rows(self, plan, grid, top, diag, sig, tol, warm_rows):
         """F* of every row and the B mean systems, `_SAMPLE_BLOCK` rows at a time (a pass holds a complex fine grid per two rows and
         the CG vectors of every row).  -> (FY (B, M), beta (B, M), list of the blocks' LazyIterations); rows in their own units."""
@@ -211,19 +201,11 @@ class EFGPNDMulti(EFGPND):
         if nufft_eps is None:
             nufft_eps = self.nufft_eps
         dd = self._device_data()
-        dev, xd = dd["dev"], dd["x"]
-        d = xd.shape[1]
+        d = dd["x"].shape[1]
         sig = self._gp_params.host_pos()[-1]
-        grid = _Grid(self.kernel, self.eps, dd["L"], d, dev)
-        plan = NufftPlan(xd, grid.plan_h, min(float(nufft_eps), _CONV_TOL), points=self._layout())
-        v = plan.type1_ones(tuple(2 * n - 1 for n in grid.shape))          # depends on x only: once for all outputs
-        toeplitz = ToeplitzND(v, force_pow2=True)
-        use_precond = self.opts.get("mean_cg_preconditioner", True)
+        grid = _Grid(self.kernel, self.eps, dd["L"], d, dd["dev"])
+        plan, _, v, toeplitz, diag = self._shared_operator(grid, sig, nufft_eps, self.opts.get("mean_cg_preconditioner", True))
         tol = self.opts.get("cg_tolerance", 1e-4)
-        diag = None
-        if use_precond:
-            cidx = _center_flat(v)
-            diag, _ = gradient_prepare(grid.ws, None, v.reshape(-1)[cidx:cidx + 1], sig, want_diag=True, want_rhs=False)
         prev = self._fit_state
         warm = (self.opts.get("mean_cg_warm_start", True) and prev is not None and tuple(prev["shape"]) == tuple(grid.shape)
                 and tuple(prev["beta_rows"].shape) == (self.n_outputs, grid.M))
@@ -254,108 +236,30 @@ class EFGPNDMulti(EFGPND):
         return st
 
     # -- predict --------------------------------------------------------------------------------------------------------------------
-    def _nan_like(self, shape):
-        rdtype = self.x.dtype
-        if self._nan_scalar is None or self._nan_scalar.device != self.device or self._nan_scalar.dtype != rdtype:
-            self._nan_scalar = torch.full((1,), float("nan"), device=self.device, dtype=rdtype)
-        return self._nan_scalar.expand(shape)
-
+    # `predict` -> (means (N*, B), latent variance (N*,)) and `predict_grid` -> (means (B, n_0, .., n_{d-1}), variance map) are
+    # EFGPND's: the variance does not depend on Y and is computed once.  What differs is how the means are formed, and that
+    # predict(compute_log_marginal=True) appends `log_marginal()` (B,) with opts["log_marginal_probes"] / ["log_marginal_steps"].
     def _row_blocks(self):
         block = _SAMPLE_BLOCK[self._fit_state["d"]]
         return [(r0, min(self.n_outputs, r0 + block)) for r0 in range(0, self.n_outputs, block)]
 
-    def predict(self, x_new: torch.Tensor, *, return_variance: bool = True, variance_method: str = "stochastic",
-                hutchinson_probes: int = 1_000, compute_log_marginal: bool = False, force_recompute: bool = False,
-                do_profiling: bool = False, nufft_eps: Optional[float] = None, variance_probes: Optional[torch.Tensor] = None):
-        """Posterior means (N*, B) and the latent variance (N*,) at x_new; the variance does not depend on Y and is computed once.
-        Keywords as `EFGPND.predict`; compute_log_marginal=True appends `log_marginal()` (B,) with opts["log_marginal_probes"] /
-        ["log_marginal_steps"]."""
-        if x_new is None:
-            raise ValueError("x_new must be provided for prediction")
-        self._compute_common_parameters(force_recompute=force_recompute, nufft_eps=nufft_eps)
-        st = self._fit_state
-        rdtype = self.x.dtype
-        if nufft_eps is None:
-            nufft_eps = self.nufft_eps
-        dd = self._devdata
-        dev = dd["dev"]
-        xn = _dev_points(x_new, dev)
-        n_new, d = xn.shape
-        if d != st["d"]:
-            raise ValueError(f"x_new has {d} columns, the model was built on {st['d']}")
-        ranges = _StageRanges("EFGPNDMulti.predict", "predict_mean")
-        pkey = (xn.data_ptr(), tuple(xn.shape), xn._version, st["plan_h"], float(nufft_eps))
-        if self._predict_plan is not None and self._predict_plan[0] == pkey:
-            plan = self._predict_plan[1]
-        else:
-            plan = NufftPlan(xn, st["plan_h"], float(nufft_eps))
-            self._predict_plan = (pkey, plan)
-        mean = torch.empty((self.n_outputs, n_new), dtype=torch.float64, device=dev)
+    def _mean_at(self, plan):
+        st, dd = self._fit_state, self._devdata
+        mean = torch.empty((self.n_outputs, plan.npts), dtype=torch.float64, device=dd["dev"])
         for r0, r1 in self._row_blocks():                    # F (ws * beta_b), a block of rows per gather
             mean[r0:r1] = plan.type2(st["beta_rows"][r0:r1], st["shape"], real_only=True, batched=True, mode_scale=st["ws"])
-        out_mean = (mean * dd["scale"][:, None]).T.to(device=self.device, dtype=rdtype)
-        if not return_variance:
-            ranges.close()
-            return self._with_log_marginal(compute_log_marginal, out_mean, self._nan_like((n_new,)))
-        ranges.stage("compute_variance")
-        A_var = create_A_var(st["ws"], self._toeplitz, st["sig"], torch.complex128)
-        var = compute_prediction_variance(
-            x_new=xn, xis=self._xis.to(torch.float64), ws=st["ws"], A_var=A_var, cg_tol=self.opts.get("cg_tolerance", 1e-4),
-            max_cg_iter=self.opts.get("max_cg_iterations", 1000), variance_method=variance_method, h=st["plan_h"],
-            xcen=torch.zeros(d, dtype=torch.float64), hutchinson_probes=hutchinson_probes, nufft_eps=nufft_eps, device=self.device,
-            rdtype=rdtype, cdtype=_cmplx(rdtype), probes=variance_probes, shards=None, shape=st["shape"] if st["ard"] else None)
-        ranges.close()
-        if do_profiling:
-            torch.cuda.synchronize(dev)
-        return self._with_log_marginal(compute_log_marginal, out_mean, var)
+        return (mean * dd["scale"][:, None]).T
 
-    def _with_log_marginal(self, wanted, mean, var):
-        if not wanted:
-            return mean, var
-        return mean, var, self.log_marginal(self.opts.get("log_marginal_probes", 100), self.opts.get("log_marginal_steps", 25))
-
-    def predict_grid(self, axes, *, return_variance: bool = True, variance_method: str = "stochastic", hutchinson_probes: int = 1_000,
-                     variance_probes: Optional[torch.Tensor] = None, force_recompute: bool = False):
-        """Posterior means (B, n_0, .., n_{d-1}) on the rectilinear raster axes[0] x .. x axes[d-1] by the batched exact raster
-        transform, and the shared variance map (n_0, .., n_{d-1}).  Arguments as `EFGPND.predict_grid`."""
-        axes = self._grid_axes(axes, "predict_grid")
-        self._compute_common_parameters(force_recompute=force_recompute)
-        st = self._fit_state
-        rdtype = self.x.dtype
-        dd = self._devdata
-        dev = dd["dev"]
-        ax = [a.to(dev) for a in axes]
+    def _mean_on_raster(self, ax):
+        st, dd = self._fit_state, self._devdata
         n_axis = tuple(int(a.numel()) for a in ax)
-        mean = torch.empty((self.n_outputs,) + n_axis, dtype=torch.float64, device=dev)
-        for r0, r1 in self._row_blocks():
+        mean = torch.empty((self.n_outputs,) + n_axis, dtype=torch.float64, device=dd["dev"])
+        for r0, r1 in self._row_blocks():                    # the batched exact raster transform
             raster_type2(ax, st["plan_h"], st["shape"], st["beta_rows"][r0:r1], batched=True, mode_scale=st["ws"], out=mean[r0:r1])
-        out_mean = (mean * dd["scale"].reshape((-1,) + (1,) * len(n_axis))).to(device=self.device, dtype=rdtype)
-        if not return_variance:
-            return out_mean, self._nan_like(n_axis)
-        A_var = create_A_var(st["ws"], self._toeplitz, st["sig"], torch.complex128)
-        cg_tol, max_it = self.opts.get("cg_tolerance", 1e-4), self.opts.get("max_cg_iterations", 1000)
-        shape = st["shape"] if st["ard"] else None
-        method = variance_method.lower()
-        if method == "stochastic":
-            est = diag_sums_nd(A_var, hutchinson_probes, self._xis.to(torch.float64), max_it, cg_tol, st["ws"], probes=variance_probes,
-                               shape=shape)
-            var = raster_type2(ax, st["plan_h"], tuple(est.shape), est.detach(), modeord=1)
-        elif method == "regular":
-            cells, parts = prod(n_axis), []
-            for lo in range(0, cells, 8192):
-                idx = torch.arange(lo, min(cells, lo + 8192), device=dev)
-                cols = []
-                for a in reversed(range(len(ax))):
-                    cols.append(ax[a][idx % n_axis[a]])
-                    idx = idx // n_axis[a]
-                parts.append(compute_prediction_variance(
-                    x_new=torch.stack(cols[::-1], dim=1), xis=None, ws=st["ws"], A_var=A_var, cg_tol=cg_tol, max_cg_iter=max_it,
-                    variance_method="regular", h=st["plan_h"], xcen=None, hutchinson_probes=hutchinson_probes,
-                    nufft_eps=self.nufft_eps, device=dev, rdtype=torch.float64, cdtype=torch.complex128, shape=shape))
-            var = torch.cat(parts).reshape(n_axis)
-        else:
-            raise ValueError(f"Variance method '{variance_method}' not implemented. Choose 'regular' or 'stochastic'.")
-        return out_mean, var.to(device=self.device, dtype=rdtype)
+        return mean * dd["scale"].reshape((-1,) + (1,) * len(n_axis))
+
+    def _predict_log_marginal(self):
+        return self.log_marginal(self.opts.get("log_marginal_probes", 100), self.opts.get("log_marginal_steps", 25))
 
     # -- objective --------------------------------------------------------------------------------------------------------------------
     def log_marginal(self, probes: int = 100, steps: int = 25) -> torch.Tensor:
@@ -397,8 +301,7 @@ class EFGPNDMulti(EFGPND):
         if cg_tol is None:
             cg_tol = 0.1 * self.eps
         dd = self._device_data()
-        dev, xd, N = dd["dev"], dd["x"], dd["N"]
-        d = xd.shape[1]
+        dev, N = dd["dev"], dd["N"]
         kernel = self.kernel
         sig = self._gp_params.host_pos()[-1]
         if noise_floor is not None:
@@ -408,45 +311,26 @@ class EFGPNDMulti(EFGPND):
         H = kernel.num_hypers - 1
         trace_idx = [i for i in range(H) if i != variance_idx]
         K, T = len(trace_idx), int(trace_samples)
-        grid = _Grid(kernel, self.eps, dd["L"], d, dev, want_grad=True)
+        grid = _Grid(kernel, self.eps, dd["L"], dd["x"].shape[1], dev, want_grad=True)
         ws, Dp, M = grid.ws, grid.dprime, grid.M
         if H > 4 or Dp is None or Dp.ndim != 2 or Dp.shape[1] != H:
             raise NotImplementedError("EFGPNDMulti.compute_gradients needs a kernel with at most 4 hyper-parameters and a spectral_grad")
-        tight = min(float(nufft_eps), _CONV_TOL) if nufft_eps else _CONV_TOL
-        points = self._layout()
-        plan = NufftPlan(xd, grid.plan_h, tight, points=points)
-        plan_p = plan if (not nufft_eps or float(nufft_eps) <= tight) else NufftPlan(xd, grid.plan_h, float(nufft_eps), points=points)
-        v = plan.type1_ones(tuple(2 * n - 1 for n in grid.shape))
-        toeplitz = ToeplitzND(v, force_pow2=True)
-        top = toeplitz._op
         use_mean_pc = self.opts.get("mean_cg_preconditioner", True)
         use_trace_pc = self.opts.get("trace_cg_preconditioner", True)
-        diag = None
-        if use_mean_pc or use_trace_pc:
-            cidx = _center_flat(v)
-            diag, _ = gradient_prepare(ws, None, v.reshape(-1)[cidx:cidx + 1], sig, want_diag=True, want_rhs=False)
+        plan, plan_p, _, toeplitz, diag = self._shared_operator(grid, sig, nufft_eps, use_mean_pc or use_trace_pc, probe_plan=True)
+        top = toeplitz._op
         prev = self._last_gradient_beta
         warm = (self.opts.get("mean_cg_warm_start", True) and prev is not None and tuple(prev.shape) == (self.n_outputs, M)
                 and getattr(self, "_last_gradient_shape", None) == tuple(grid.shape))
         FY, beta, mean_its = self._solve_rows(plan, grid, top, diag if use_mean_pc else None, sig, cg_tol, prev if warm else None)
         Tg = top.apply_scaled(beta, pre=ws)                                # T (D beta_b), every row in one call
 
-        # probes and the right-hand sides of the trace systems: once for all outputs
-        B_all = torch.empty(((K + 1) * T, M), dtype=torch.complex128, device=dev)
-        FZ = None
-        if K > 0:
-            probe_seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-            FZ = plan_p.type1_rademacher(probe_seed, T, grid.shape).reshape(T, M)
-            for slot, ki in enumerate(trace_idx):
-                top.apply_scaled(FZ, pre=Dp[:, ki].contiguous(), post=ws, out=B_all[slot * T:(slot + 1) * T])
-        V = rademacher_fill(dev, int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()), T, M)
-        top.apply_scaled(V, pre=ws, post=ws, out=B_all[K * T:])
-        Beta_all, trace_iters = _solve_batched(None, top, ws, sig, 0, B_all, cg_tol, early_stop=True, diag=diag if use_trace_pc else None)
-
-        variance = dict(zip(kernel.hypers, kernel.get_hypers()))["variance"] if variance_idx is not None else 1.0
+        # probes, the right-hand sides of the trace systems and their solve: once for all outputs, on generated probes
+        FZ, V, Beta_all, trace_iters = _trace_systems(grid, top, plan_p, sig, cg_tol, True, diag if use_trace_pc else None, T, trace_idx,
+                                                      self._shards, N, dev)
         out, rows_out = gradient_assemble_multi(FY, Tg, ws, beta, Dp, FZ, V, Beta_all.reshape(-1, M), variance_idx=variance_idx,
                                                 trace_idx=trace_idx, sigmasq=sig, n_obs=N, yy=dd["yy"], row_scale=dd["scale"],
-                                                variance=variance)
+                                                variance=_variance_hyper(kernel, variance_idx))
         nh = H + 1
         host = out.cpu()                                                   # ONE read-back: gradient and diagnostics
         self._last_gradient_beta = beta
