@@ -10,7 +10,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "csrc")
-SOURCES = ["es_kernel.cpp", "grid_host.cpp", "common.cpp", "cg_plan_host.cpp", "nufft_plan_host.cpp", "raster_plan_host.cpp", "raster_dft.hip", "raster_adjoint.hip", "nufft.hip", "spread_mfma.hip", "points_layout.hip", "small_dft.hip", "variance_ops.hip", "cheb_interp.hip", "pg_ops.hip", "gradient_ops.hip", "multi_output.hip", "gradient_step.cpp", "comm.cpp", "toeplitz_cg.hip", "cg_multi.hip", "cg_coop2d.hip", "cg_persistent.hip", "cg_herm.hip", "line_fft.hip"]
+SOURCES = ["es_kernel.cpp", "grid_host.cpp", "common.cpp", "cg_plan_host.cpp", "nufft_plan_host.cpp", "raster_plan_host.cpp", "raster_dft.hip", "raster_adjoint.hip", "nufft.hip", "spread_mfma.hip", "points_layout.hip", "small_dft.hip", "variance_ops.hip", "cheb_interp.hip", "pg_ops.hip", "gradient_ops.hip", "multi_output.hip", "mode_jet.hip", "gradient_step.cpp", "comm.cpp", "toeplitz_cg.hip", "cg_multi.hip", "cg_coop2d.hip", "cg_persistent.hip", "cg_herm.hip", "line_fft.hip"]
 HEADERS = ["es_kernel.hpp", "common.hpp", "toeplitz_cg.hpp", "toeplitz_op.hpp", "toeplitz_line_dev.hpp", "cg_plan_host.hpp", "cg_persistent_dev.hpp", "nufft_plan_host.hpp", "nufft_dev.hpp", "spectral_weights.hpp", "points_layout.hpp", "spread_mfma.hpp", "small_dft.hpp", "line_fft.hpp", "raster_plan_host.hpp", "raster_dft.hpp", os.path.join("..", "..", "include", "efgp_hip.h")]
 TARGET = os.path.join(HERE, "libefgp_hip.so")
 

@@ -105,6 +105,7 @@ _SIGNATURES = {
     "efgp_raster_type1_plan": (_I, [_I, _PI64, _PI64, _I, _I64, _PI64, _PI64, _PI64]),
     "efgp_cheb_interp":(_I, [_I, _I, _PI64, _VP, _VP, _VP, _VP, _I64, _I, _VP, _VP]),
     "efgp_hermitian_normal_rows": (_I, [_I, C.c_uint64, _I64, _I, _I64, _D, _VP, _VP, _D, _VP, _VP]),
+    "efgp_mode_jet_rows": (_I, [_I, _I, _PI64, C.POINTER(_D), _VP, _VP, _I64, _I, _VP, _VP]),
     "efgp_pg_estep_update": (_I, [_I, _I64, _I, _VP, _VP, C.c_uint64, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
     "efgp_pg_nb_estep_update": (_I, [_I, _I64, _I, _VP, _VP, C.c_uint64, _VP, _D, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
     "efgp_pg_nb_total_count_grad": (_I, [_I, _I64, _VP, _VP, _VP, _D, _I, _VP, _VP, _VP, _VP]),

@@ -298,6 +298,28 @@ class NufftPlan:
                       "efgp_nufft_type2_scaled")
         return out if batched else out[0]
 
+    def type2_jet(self, f, n_modes, *, mode_scale=None):
+        """Value and gradient of Re F (mode_scale * f) at the plan's points: f (M,) | (nrows, M) complex -> (nrows, 1 + d, N)
+        float64, entry [b, 0] the value and [b, 1 + a] the partial along axis a.  `mode_jet_rows` makes the 1 + d coefficient rows of
+        every row of f; they go through the batched real-only `type2`, which pairs them two per complex fine grid, in blocks of at
+        most `_SAMPLE_BLOCK[d]` rows (the fine-grid memory of one call)."""
+        shape = tuple(int(m) for m in n_modes)
+        jets = mode_jet_rows(f, shape, self.h, mode_scale=mode_scale)
+        R, J, M = jets.shape
+        rows = jets.view(R * J, M)
+        block = _SAMPLE_BLOCK[self.dim]
+        if R * J <= block:
+            return self.type2(rows, shape, real_only=True, batched=True).view(R, J, self.npts)
+        out = torch.empty((R * J, self.npts), dtype=_RD, device=self.dev)
+        for lo in range(0, R * J, block):
+            out[lo:lo + block] = self.type2(rows[lo:lo + block], shape, real_only=True, batched=True)
+        return out.view(R, J, self.npts)
+
+
+# Rows per batched type-2 call of the function draws, the multi-output means and the jets: a call holds one complex fine grid per
+# TWO real-only rows (efgpnd.py states the memory reasoning where it uses the blocks)
+_SAMPLE_BLOCK = {1: 64, 2: 64, 3: 8}
+
 
 class ToeplitzOp:
     """d-dimensional Toeplitz mat-vec (C ABI: efgp_toeplitz_*)."""
@@ -868,6 +890,56 @@ def raster_type2(axes, h, n_modes, f, *, modeord=0, isign=+1, mode_scale=None, x
                                       int(max_workspace_bytes), _stream(dev)), "efgp_raster_type2")
     res = out.reshape((B,) + n_axis)
     return res if batched else res[0]
+
+
+def mode_jet_rows(f, n_modes, h, *, mode_scale=None, modeord=0):
+    """The coefficient rows of a trigonometric sum and of its d first partial derivatives (efgp_mode_jet_rows):
+
+        out[b, 0, k] = mode_scale[k] f[b, k],      out[b, 1 + a, k] = (2 pi h[a] k_a) i out[b, 0, k]
+
+    with k_a the mode number of slot k on axis a (-(n // 2) .. (n - 1) // 2; FFT order for modeord = 1).  f (M,) | (nrows, M)
+    complex, M = prod n_modes; h: one spacing or d; mode_scale (M,) complex or None.  Returns (nrows, 1 + d, M) complex128 on the
+    GPU.  Wrong sizes are a ValueError before anything touches the device."""
+    pa = _per_axis(n_modes)
+    shape = tuple(int(m) for m in (pa if pa is not None else (n_modes,)))
+    d = len(shape)
+    if not 1 <= d <= 3:
+        raise ValueError(f"mode_jet_rows: n_modes must hold 1, 2 or 3 mode counts (got {d})")
+    if any(m < 1 for m in shape):
+        raise ValueError(f"mode_jet_rows: n_modes must be positive (got {shape})")
+    M = math.prod(shape)
+    hv = _per_axis(h)
+    hv = tuple(float(v) for v in hv) if hv is not None else (float(h),) * d
+    if len(hv) != d:
+        raise ValueError(f"mode_jet_rows: h has {len(hv)} spacings for {d} axes")
+    if modeord not in (0, 1):
+        raise ValueError(f"mode_jet_rows: modeord must be 0 or 1 (got {modeord})")
+    if not torch.is_tensor(f):
+        f = torch.as_tensor(f)
+    if f.ndim not in (1, 2) or f.shape[-1] != M:
+        raise ValueError(f"mode_jet_rows: f has shape {tuple(f.shape)}, the mode box {shape} has {M} entries per row")
+    if mode_scale is not None and mode_scale.numel() != M:
+        raise ValueError(f"mode_jet_rows: mode_scale has {mode_scale.numel()} entries, the mode box {shape} has {M}")
+    dev = compute_device(f, mode_scale)
+    ff = _dc(f.reshape(-1, M), dev, _CD)
+    sc = _dc(mode_scale.reshape(-1), dev, _CD) if mode_scale is not None else None
+    R = ff.shape[0]
+    out = torch.empty((R, 1 + d, M), dtype=_CD, device=dev)
+    with _on(dev):
+        check(lib().efgp_mode_jet_rows(dev.index, d, _i64(shape), _f64(hv), _ptr(ff), _ptr(sc) if sc is not None else None, R,
+                                       int(modeord), _ptr(out), _stream(dev)), "efgp_mode_jet_rows")
+    return out
+
+
+def raster_type2_jet(axes, h, n_modes, f, *, mode_scale=None, xcen=None):
+    """Value and gradient of Re F (mode_scale * f) on the rectilinear raster axes[0] x .. x axes[d-1]: f (M,) | (nrows, M) complex ->
+    (nrows, 1 + d, n_0, .., n_{d-1}) float64, entry [b, 0] the value and [b, 1 + a] the partial along axis a: the rows of
+    `mode_jet_rows` through the exact `raster_type2` (its slab planning, its arguments)."""
+    axes, hv, shape = _raster_args("raster_type2_jet", axes, h, n_modes)
+    jets = mode_jet_rows(f, shape, hv, mode_scale=mode_scale)
+    R, J, M = jets.shape
+    res = raster_type2(axes, hv, shape, jets.view(R * J, M), batched=True, xcen=xcen)
+    return res.view((R, J) + tuple(res.shape[1:]))
 
 
 def raster_type1_plan(n_axis, n_modes, nbatch=1, max_workspace_bytes=0):

@@ -33,9 +33,9 @@ from cg import ConjugateGradients
 from kernels.kernel_params import GPParams
 from utils.kernels import get_xis, get_xis_nd
 
-from efgp_hip import NufftPlan, PointSet, ToeplitzOp, lanczos, lag_sums, variance_rhs, variance_contract, cg_solve, cg_solve_lazy, cg_solve_mean_async, cg_solve_mean_fused, vdot_real, compute_device, rademacher_fill, gradient_prepare, gradient_assemble, hermitian_normal_rows, normal_row_offset, spectral_weights_nd, raster_type2, RasterPlan
+from efgp_hip import NufftPlan, PointSet, ToeplitzOp, lanczos, lag_sums, variance_rhs, variance_contract, cg_solve, cg_solve_lazy, cg_solve_mean_async, cg_solve_mean_fused, vdot_real, compute_device, rademacher_fill, gradient_prepare, gradient_assemble, hermitian_normal_rows, normal_row_offset, spectral_weights_nd, raster_type2, raster_type2_jet, RasterPlan
 from efgp_hip.dist import PointShards
-from efgp_hip.ops import _per_axis
+from efgp_hip.ops import _per_axis, _SAMPLE_BLOCK
 
 TWO_PI = 2.0 * math.pi
 _CONV_TOL = 6e-8       # tolerance the reference hard-codes for the Toeplitz vector (efgpnd.py:1418)
@@ -1072,12 +1072,9 @@ def _unwrap_operator(A_apply):
     raise TypeError("expected an operator made by create_A_mean / create_A_var")
 
 
-def diag_sums_nd(A_apply, J, xis_flat, max_cg_iter, cg_tol, ws, probes: Optional[torch.Tensor] = None, shards=None, shape=None):
-    """Hutchinson estimate of the lag sums c[r] = sum_{k-l=r} (A^-1)_{kl}-weighted products used by the
-    stochastic variance (reference: efgpnd.py:1634-1664).  ``probes`` (J,M) of +-1 may be injected;
-    otherwise they are drawn with torch.randint as in the reference (:1644).  ``shards`` (a PointShards of a multi-GPU
-    model; the probes must then be identical on all ranks): the J systems are split by rows over the ranks.  ``shape``: the mode
-    count per axis of a per-axis grid (then ``xis_flat`` is not looked at); the lag box is (2 n_a - 1) per axis."""
+def _hutchinson_solves(A_apply, J, xis_flat, max_cg_iter, cg_tol, ws, probes, shards, shape):
+    """The probes of the stochastic variance and their solves u_j = A^-1 (ws eta_j), which depend on the hyper-parameters only: what
+    `diag_sums_nd` and `diag_sums_gradient_nd` share.  -> (ws on the device, us (J, M), etas (J, M), mode count(s), d)."""
     if shape is not None:
         m_loc, d_loc, Mtot = tuple(int(n) for n in shape), len(shape), prod(shape)
     else:
@@ -1094,8 +1091,28 @@ def diag_sums_nd(A_apply, J, xis_flat, max_cg_iter, cg_tol, ws, probes: Optional
     rhs = wsd[None, :] * etas
     us, _ = _solve_batched(shards, op.toeplitz._op, wsd, op.sigmasq, op.variant, rhs, cg_tol, early_stop=True, diag=None,
                            max_iter=max_cg_iter)
+    return wsd, us, etas, m_loc, d_loc
+
+
+def diag_sums_nd(A_apply, J, xis_flat, max_cg_iter, cg_tol, ws, probes: Optional[torch.Tensor] = None, shards=None, shape=None):
+    """Hutchinson estimate of the lag sums c[r] = sum_{k-l=r} (A^-1)_{kl}-weighted products used by the
+    stochastic variance (reference: efgpnd.py:1634-1664).  ``probes`` (J,M) of +-1 may be injected;
+    otherwise they are drawn with torch.randint as in the reference (:1644).  ``shards`` (a PointShards of a multi-GPU
+    model; the probes must then be identical on all ranks): the J systems are split by rows over the ranks.  ``shape``: the mode
+    count per axis of a per-axis grid (then ``xis_flat`` is not looked at); the lag box is (2 n_a - 1) per axis."""
+    wsd, us, etas, m_loc, d_loc = _hutchinson_solves(A_apply, J, xis_flat, max_cg_iter, cg_tol, ws, probes, shards, shape)
     # zero-padded correlation of every probe pair and the mean over probes (:1660-1664): hipFFT + three small kernels
     return lag_sums(wsd[None, :] * us, etas, m_loc, d_loc)
+
+
+def diag_sums_gradient_nd(A_apply, J, xis_flat, max_cg_iter, cg_tol, ws, xi_axes, probes: Optional[torch.Tensor] = None, shards=None,
+                          shape=None):
+    """The lag sums of the variance of every partial derivative, from the solves of `diag_sums_nd` (same probe handling): with
+    C = D A^-1 D, Var[d_a f(x)] = sum_kl (2 pi)^2 xi_ka xi_la f_k(x) C_kl conj f_l(x), so axis a takes the frequency-weighted sums
+    2 pi lag_sums((2 pi xi_a) ws u, xi_a eta).  xi_axes: d device vectors (M,), xi_a of every mode.  -> list of d lag boxes."""
+    wsd, us, etas, m_loc, d_loc = _hutchinson_solves(A_apply, J, xis_flat, max_cg_iter, cg_tol, ws, probes, shards, shape)
+    g = wsd[None, :] * us
+    return [TWO_PI * lag_sums((TWO_PI * xi)[None, :] * g, xi[None, :] * etas, m_loc, d_loc) for xi in xi_axes]
 
 
 def nufft_var_est_nd(est_sums, h_val, x_center, pts, eps_val):
@@ -1204,13 +1221,57 @@ def compute_prediction_variance(x_new, xis, ws, A_var, cg_tol, max_cg_iter, vari
     raise ValueError(f"Variance method '{variance_method}' not implemented. Choose 'regular' or 'stochastic'.")
 
 
+def gradient_variance_regular(x_new, xi_axes, ws, A_var, cg_tol, max_cg_iter, h, shape=None):
+    """'regular' variance of the d partial derivatives of the latent function at x_new -> (B, d) float64 on the compute device.
+    The feature row of the partial along axis a is 2 pi i xi_a f(x*): per block of 8192 points the right-hand sides of the value
+    (`variance_rhs`: ws conj f) are multiplied by -2 pi i xi_a -- they stay conjugate-even -- and solved by the Hermitian batched
+    CG; Var = max(0, Re sum_k conj(rhs_k) gamma_k), the contraction of `variance_contract` with the derivative row.
+    xi_axes: d device vectors (M,); ``shape`` with ``h`` a sequence: a per-axis grid, as in `compute_prediction_variance`."""
+    op = _unwrap_operator(A_var)
+    dev = op.toeplitz._dev
+    wsd = ws.to(device=dev, dtype=torch.complex128)
+    xn = x_new.to(device=dev, dtype=torch.float64)
+    M_loc = wsd.numel()
+    if shape is not None:
+        mtot_loc, hval = tuple(int(n) for n in shape), tuple(float(v) for v in h)
+        assert prod(mtot_loc) == M_loc, "ws must lie on the per-axis grid"
+    else:
+        mtot_loc = round(M_loc ** (1.0 / xn.shape[1]))
+        assert mtot_loc ** xn.shape[1] == M_loc, "ws must lie on the tensor grid"
+        hval = float(h)
+    factors = [torch.complex(torch.zeros_like(xi), -TWO_PI * xi) for xi in xi_axes]
+    out = []
+    for xb in torch.split(xn, 8192, dim=0):
+        rhs = variance_rhs(xb, hval, mtot_loc, wsd)
+        cols = []
+        for fac in factors:
+            ra = rhs * fac[None, :]
+            gamma, _, _ = cg_solve(op.toeplitz._op, wsd, op.sigmasq, op.variant, ra, None, cg_tol, max_iter=max_cg_iter,
+                                   early_stop=True, diag=None, batched=True, hermitian=True)
+            cols.append((ra.conj() * gamma.reshape(ra.shape)).sum(dim=1).real.clamp_min(0.0))
+        out.append(torch.stack(cols, dim=1))
+    return torch.cat(out, dim=0)
+
+
+def _raster_cell_blocks(ax, n_axis, dev, block=8192):
+    """The coordinates of the raster's cells in row-major order, `block` cells at a time: no (prod n, d) tensor."""
+    cells = prod(n_axis)
+    for lo in range(0, cells, block):
+        idx = torch.arange(lo, min(cells, lo + block), device=dev)
+        cols = []
+        for a in reversed(range(len(ax))):
+            cols.append(ax[a][idx % n_axis[a]])
+            idx = idx // n_axis[a]
+        yield torch.stack(cols[::-1], dim=1)
+
+
 # ======================================================================================
 # the model (reference: efgpnd.py:336-1226)
 # ======================================================================================
 # Rows per batched pass of EFGPND.sample_paths (even: normals come in pairs).  A pass holds one complex fine grid and one int64
 # accumulator pair per TWO rows plus the CG vectors of every row: 64 rows keep that below ~100 MB on the 2-D grids (up to
 # 512 x 512 fine cells) and fill the batched CG; the 3-D fine grids (128^3 and beyond) are 100x larger per row.
-_SAMPLE_BLOCK = {1: 64, 2: 64, 3: 8}
+# The table is efgp_hip.ops._SAMPLE_BLOCK = {1: 64, 2: 64, 3: 8} (imported above): NufftPlan.type2_jet feeds its rows by it too.
 
 
 def _derive_seed(seed: int, stream: int) -> int:
@@ -1736,6 +1797,122 @@ class EFGPND(nn.Module):
             print(f"predict_mean {t1 - t0:.6f}s  compute_variance {t2 - t1:.6f}s")
         return (out_mean, var, self._predict_log_marginal()) if compute_log_marginal else (out_mean, var)
 
+    # -- posterior gradients ---------------------------------------------------------------------------
+    # The fitted model is a finite trigonometric sum, so its partial derivatives are exact in the same feature space: mode k of the
+    # partial along axis a is 2 pi i xi_ka times mode k of the mean (efgp_hip.mode_jet_rows), through the transforms of the mean.
+    def _xi_axes(self):
+        """xi_a of every mode, a = 0 .. d - 1: d device vectors (M,) in the row-major order of the mode box, kept with the fit."""
+        st = self._fit_state
+        if "xi_axes" not in st:
+            dev = st["ws"].device
+            shape = tuple(int(n) for n in st["shape"])
+            cols = []
+            for a, (n, h) in enumerate(zip(shape, st["hs"])):
+                k = torch.arange(-(n // 2), (n - 1) // 2 + 1, dtype=torch.float64, device=dev) * float(h)
+                view = [1] * len(shape)
+                view[a] = n
+                cols.append(k.view(view).expand(shape).reshape(-1))
+            st["xi_axes"] = cols
+        return st["xi_axes"]
+
+    # What a subclass with other coefficients supplies (EFGPNDMulti): value and gradient of the mean from ONE pass
+    def _jet_at(self, plan):
+        """-> (mean (N*,), grad (N*, d)) on the compute device."""
+        st = self._fit_state
+        jet = plan.type2_jet(st["beta"], st["shape"], mode_scale=st["ws"])[0]
+        return jet[0], jet[1:].T
+
+    def _jet_on_raster(self, ax):
+        """-> (mean (n_0, ..), grad (d, n_0, ..)) on the compute device."""
+        st = self._fit_state
+        jet = raster_type2_jet(ax, st["plan_h"], st["shape"], st["beta"], mode_scale=st["ws"])[0]
+        return jet[0], jet[1:]
+
+    def _gradient_lag_sums(self, hutchinson_probes, variance_probes):
+        """The d lag boxes of the stochastic variance of the partials, stacked (d, 2 n_0 - 1, ..)."""
+        st = self._fit_state
+        A_var = create_A_var(st["ws"], self._toeplitz, st["sig"], torch.complex128)
+        ests = diag_sums_gradient_nd(A_var, hutchinson_probes, self._xis.to(torch.float64), self.opts.get("max_cg_iterations", 1000),
+                                     self.opts.get("cg_tolerance", 1e-4), st["ws"], self._xi_axes(), probes=variance_probes,
+                                     shape=st["shape"] if st["ard"] else None)
+        return torch.stack(ests)
+
+    def _gradient_variance_regular(self, xb):
+        st = self._fit_state
+        A_var = create_A_var(st["ws"], self._toeplitz, st["sig"], torch.complex128)
+        return gradient_variance_regular(xb, self._xi_axes(), st["ws"], A_var, self.opts.get("cg_tolerance", 1e-4),
+                                         self.opts.get("max_cg_iterations", 1000), st["plan_h"], shape=st["shape"] if st["ard"] else None)
+
+    def _gradient_refusals(self, what, return_variance, variance_method):
+        if self.opts.get("shard_points", False):
+            raise NotImplementedError(f"{what} does not support opts['shard_points']: the jets are transformed on one device")
+        if return_variance and variance_method.lower() not in ("regular", "stochastic"):
+            raise ValueError(f"Variance method '{variance_method}' not implemented. Choose 'regular' or 'stochastic'.")
+
+    def predict_gradient(self, x_new: torch.Tensor, *, return_variance: bool = True, variance_method: str = "stochastic",
+                         hutchinson_probes: int = 1_000, variance_probes: Optional[torch.Tensor] = None,
+                         nufft_eps: Optional[float] = None, return_mean: bool = False, force_recompute: bool = False):
+        """Gradient of the posterior mean at x_new and the latent variance of every partial -> (grad (N*, d), grad_var (N*, d));
+        return_mean=True: (mean (N*,), grad, grad_var), the mean out of the same pass over the points.
+
+        Nothing is approximated beyond what `predict` approximates: the partial along axis a multiplies mode k by 2 pi i xi_ka
+        (`efgp_hip.mode_jet_rows`), and the 1 + d real-only rows ride two per complex fine grid through the type 2 of `predict`.
+        "stochastic": the Hutchinson solves of `predict` (same probe handling: `variance_probes` (J, M) of +-1 may be injected)
+        with frequency-weighted lag sums per axis; "regular": the per-point solves of `predict` with the derivative rows, 8192
+        points at a time.  return_variance=False returns NaN of the gradient's shape as a stride-0 view."""
+        self._gradient_refusals("predict_gradient", return_variance, variance_method)
+        if x_new is None:
+            raise ValueError("x_new must be provided for prediction")
+        self._compute_common_parameters(force_recompute=force_recompute, nufft_eps=nufft_eps)
+        st = self._fit_state
+        if nufft_eps is None:
+            nufft_eps = self.nufft_eps
+        dev = self._devdata["dev"]
+        xn = _dev_points(x_new, dev)
+        B, d = xn.shape
+        if d != st["d"]:
+            raise ValueError(f"x_new has {d} columns, the model was built on {st['d']}")
+        plan = self._plan_at(xn, nufft_eps)
+        mean, grad = self._jet_at(plan)
+        if not return_variance:
+            var = self._nan_like((B, d))
+        else:
+            if variance_method.lower() == "stochastic":
+                ests = self._gradient_lag_sums(hutchinson_probes, variance_probes)
+                var = plan.type2(ests, tuple(ests.shape[1:]), modeord=1, real_only=True, batched=True).T
+            else:
+                var = self._gradient_variance_regular(xn)
+            var = var.to(device=self.device, dtype=self.x.dtype)
+        grad = grad.to(device=self.device, dtype=self.x.dtype)
+        return (mean.to(device=self.device, dtype=self.x.dtype), grad, var) if return_mean else (grad, var)
+
+    def predict_gradient_grid(self, axes, *, return_variance: bool = True, variance_method: str = "stochastic",
+                              hutchinson_probes: int = 1_000, variance_probes: Optional[torch.Tensor] = None, return_mean: bool = False,
+                              force_recompute: bool = False):
+        """`predict_gradient` on the rectilinear raster axes[0] x .. x axes[d-1] -> (grad (d, n_0, .., n_{d-1}), grad_var of the same
+        shape), return_mean=True prepends the mean map: the jets through the exact raster transform of `predict_grid` (arguments
+        as there); the "regular" variance is fed 8192 raster cells at a time in row-major order."""
+        self._gradient_refusals("predict_gradient_grid", return_variance, variance_method)
+        axes = self._grid_axes(axes, "predict_gradient_grid")
+        self._compute_common_parameters(force_recompute=force_recompute)
+        st = self._fit_state
+        dev = self._devdata["dev"]
+        ax = [a.to(dev) for a in axes]
+        n_axis = tuple(int(a.numel()) for a in ax)
+        d = len(ax)
+        mean, grad = self._jet_on_raster(ax)
+        if not return_variance:
+            var = self._nan_like((d,) + n_axis)
+        else:
+            if variance_method.lower() == "stochastic":
+                ests = self._gradient_lag_sums(hutchinson_probes, variance_probes)
+                var = raster_type2(ax, st["plan_h"], tuple(ests.shape[1:]), ests, modeord=1, batched=True)
+            else:
+                var = torch.cat([self._gradient_variance_regular(xb) for xb in _raster_cell_blocks(ax, n_axis, dev)]).T.reshape((d,) + n_axis)
+            var = var.to(device=self.device, dtype=self.x.dtype)
+        grad = grad.to(device=self.device, dtype=self.x.dtype)
+        return (mean.to(device=self.device, dtype=self.x.dtype), grad, var) if return_mean else (grad, var)
+
     # -- function draws ----------------------------------------------------------------------------------
     @property
     def last_sample_stats(self) -> Dict:
@@ -1810,7 +1987,7 @@ class EFGPND(nn.Module):
         return outs, max_iter, tol
 
     def sample_paths(self, x_new: torch.Tensor, nsamples: int, *, prior: bool = False, seed: Optional[int] = None,
-                     cg_tolerance: Optional[float] = None, return_state: bool = False):
+                     cg_tolerance: Optional[float] = None, return_state: bool = False, gradient: bool = False):
         """Draws of the latent function at x_new -> (nsamples, B), from the posterior (default) or the prior, in the weight space
         of the equispaced features: with D = diag(ws), A = D F*F D + sigma^2 I and the weights' prior N(0, I),
 
@@ -1832,7 +2009,10 @@ class EFGPND(nn.Module):
         opts["max_cg_iterations"] (default 1000) caps them.  Rows that reach the cap are returned as they stand; their indices
         are in `last_sample_stats["cg_capped"]` (read on request: no synchronisation in the call) and in the state, and a
         return_state=True call, which reads the counts anyway, warns about them.  The pass over the training points counts as
-        one for opts["point_layout"] = "auto": a first sample_paths call after a single fit builds the sorted layout."""
+        one for opts["point_layout"] = "auto": a first sample_paths call after a single fit builds the sorted layout.
+
+        gradient=True returns (draws (nsamples, B), grads (nsamples, B, d)[, state]): the same weight draws under the same seed
+        through `NufftPlan.type2_jet` -- every draw with its exact spatial gradient out of one pass over x_new."""
         nsamples = int(nsamples)
         if nsamples < 1:
             raise ValueError(f"nsamples must be at least 1 (got {nsamples})")
@@ -1856,11 +2036,16 @@ class EFGPND(nn.Module):
         shape = st["shape"]
         plan_new = self._plan_at(xn, self.nufft_eps)
         keep =dict(weights=[], delta=[], rhs=[]) if return_state else None
-        outs, max_iter, tol = self._draw_weight_blocks(
-            nsamples, prior, seed, cg_tolerance, keep,
-            lambda w: plan_new.type2(w, shape, real_only=True, batched=True, mode_scale=st["ws"]))
+        if gradient:
+            transform = lambda w: plan_new.type2_jet(w, shape, mode_scale=st["ws"])        # (nb, 1 + d, B)
+        else:
+            transform = lambda w: plan_new.type2(w, shape, real_only=True, batched=True, mode_scale=st["ws"])
+        outs, max_iter, tol = self._draw_weight_blocks(nsamples, prior, seed, cg_tolerance, keep, transform)
         out = outs[0] if len(outs) == 1 else torch.cat(outs)       # one block: the transform's own output, no copy
-        res = out.to(device=self.device, dtype=rdtype)
+        if gradient:
+            res = (out[:, 0].to(device=self.device, dtype=rdtype), out[:, 1:].permute(0, 2, 1).to(device=self.device, dtype=rdtype))
+        else:
+            res = out.to(device=self.device, dtype=rdtype)
         if not return_state:
             return res
         state = dict(seed=seed, weights=torch.cat(keep["weights"]),
@@ -1873,7 +2058,7 @@ class EFGPND(nn.Module):
             if stats["cg_capped"]:
                 warnings.warn(f"sample_paths: {len(stats['cg_capped'])} of {nsamples} solves reached max_cg_iterations = {max_iter} "
                               f"without meeting the tolerance {tol:g}; raise opts['max_cg_iterations']", RuntimeWarning, stacklevel=2)
-        return res, state
+        return res + (state,) if gradient else (res, state)
 
     # -- maps on rectilinear grids ---------------------------------------------------------------------
     def _grid_axes(self, axes, what):
@@ -1917,14 +2102,8 @@ class EFGPND(nn.Module):
                                shape=shape)
             var = raster_type2(ax, st["plan_h"], tuple(est.shape), est.detach(), modeord=1)
         elif method == "regular":
-            cells, parts = prod(n_axis), []
-            for lo in range(0, cells, 8192):                     # the coordinates of 8192 cells at a time: no (prod n, d) tensor
-                idx = torch.arange(lo, min(cells, lo + 8192), device=dev)
-                cols = []
-                for a in reversed(range(len(ax))):
-                    cols.append(ax[a][idx % n_axis[a]])
-                    idx = idx // n_axis[a]
-                xb = torch.stack(cols[::-1], dim=1)
+            parts = []
+            for xb in _raster_cell_blocks(ax, n_axis, dev):      # the coordinates of 8192 cells at a time
                 parts.append(compute_prediction_variance(
                     x_new=xb, xis=None, ws=st["ws"], A_var=A_var, cg_tol=cg_tol, max_cg_iter=max_it, variance_method="regular",
                     h=st["plan_h"], xcen=None, hutchinson_probes=hutchinson_probes, nufft_eps=self.nufft_eps, device=dev,
@@ -1935,10 +2114,11 @@ class EFGPND(nn.Module):
         return var.to(device=self.device, dtype=self.x.dtype)
 
     def sample_paths_grid(self, axes, nsamples: int, *, prior: bool = False, seed: Optional[int] = None,
-                          cg_tolerance: Optional[float] = None):
+                          cg_tolerance: Optional[float] = None, gradient: bool = False):
         """Draws of the latent function on the rectilinear raster axes[0] x .. x axes[d-1] -> (nsamples, n_0, .., n_{d-1}): the
         weight draws of `sample_paths` (same seed, same weights), evaluated by the exact raster transform of `predict_grid`
-        instead of a type-2 NUFFT over materialised points.  Arguments as in `sample_paths`; `last_sample_stats` is set alike."""
+        instead of a type-2 NUFFT over materialised points.  Arguments as in `sample_paths`; `last_sample_stats` is set alike.
+        gradient=True returns (draws, grads (nsamples, d, n_0, .., n_{d-1})) through `raster_type2_jet`."""
         nsamples = int(nsamples)
         if nsamples < 1:
             raise ValueError(f"nsamples must be at least 1 (got {nsamples})")
@@ -1950,10 +2130,14 @@ class EFGPND(nn.Module):
         st = self._fit_state
         dev = self._devdata["dev"]
         ax = [a.to(dev) for a in axes]
-        outs, _, _ = self._draw_weight_blocks(
-            nsamples, prior, seed, cg_tolerance, None,
-            lambda w: raster_type2(ax, st["plan_h"], st["shape"], w, batched=True, mode_scale=st["ws"]))
+        if gradient:
+            transform = lambda w: raster_type2_jet(ax, st["plan_h"], st["shape"], w, mode_scale=st["ws"])      # (nb, 1 + d, n_0, ..)
+        else:
+            transform = lambda w: raster_type2(ax, st["plan_h"], st["shape"], w, batched=True, mode_scale=st["ws"])
+        outs, _, _ = self._draw_weight_blocks(nsamples, prior, seed, cg_tolerance, None, transform)
         out = outs[0] if len(outs) == 1 else torch.cat(outs)
+        if gradient:
+            return out[:, 0].to(device=self.device, dtype=self.x.dtype), out[:, 1:].to(device=self.device, dtype=self.x.dtype)
         return out.to(device=self.device, dtype=self.x.dtype)
 
     def sample_posterior(self, x_new: torch.Tensor, nsamples: int, method: str = "dense", seed: Optional[int] = None):

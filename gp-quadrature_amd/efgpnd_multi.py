@@ -22,7 +22,7 @@ from typing import Dict, Optional
 
 import torch
 
-from efgp_hip import NufftPlan, cg_solve_lazy, compute_device, gradient_assemble_multi, raster_type2
+from efgp_hip import NufftPlan, cg_solve_lazy, compute_device, gradient_assemble_multi, raster_type2, raster_type2_jet
 from efgpnd import (EFGPND, ToeplitzND, _CONV_TOL, _Grid, _SAMPLE_BLOCK, _dev_points, _jacobi_diag, _kernel_by_name, _points_box,
                     _trace_systems, _variance_hyper, logdet_slq)
 
@@ -257,6 +257,24 @@ class EFGPNDMulti(EFGPND):
         for r0, r1 in self._row_blocks():                    # the batched exact raster transform
             raster_type2(ax, st["plan_h"], st["shape"], st["beta_rows"][r0:r1], batched=True, mode_scale=st["ws"], out=mean[r0:r1])
         return mean * dd["scale"].reshape((-1,) + (1,) * len(n_axis))
+
+    # `predict_gradient` -> (grad (N*, B, d), variance of the partials (N*, d)) and `predict_gradient_grid` -> (grad (B, d, n_0, ..),
+    # variance (d, n_0, ..)) are EFGPND's as well; return_mean=True prepends the means (N*, B) / (B, n_0, ..) of the same pass.
+    def _jet_at(self, plan):
+        st, dd = self._fit_state, self._devdata
+        d = st["d"]
+        jet = torch.empty((self.n_outputs, 1 + d, plan.npts), dtype=torch.float64, device=dd["dev"])
+        for r0, r1 in self._row_blocks():                    # value and partials of F (ws * beta_b), a block of outputs per call
+            jet[r0:r1] = plan.type2_jet(st["beta_rows"][r0:r1], st["shape"], mode_scale=st["ws"])
+        jet = jet * dd["scale"][:, None, None]
+        return jet[:, 0].T, jet[:, 1:].permute(2, 0, 1)
+
+    def _jet_on_raster(self, ax):
+        st, dd = self._fit_state, self._devdata
+        jet = torch.cat([raster_type2_jet(ax, st["plan_h"], st["shape"], st["beta_rows"][r0:r1], mode_scale=st["ws"])
+                         for r0, r1 in self._row_blocks()])
+        jet = jet * dd["scale"].reshape((-1,) + (1,) * (jet.ndim - 1))
+        return jet[:, 0], jet[:, 1:]
 
     def _predict_log_marginal(self):
         return self.log_marginal(self.opts.get("log_marginal_probes", 100), self.opts.get("log_marginal_steps", 25))

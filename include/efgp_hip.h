@@ -510,6 +510,20 @@ int efgp_raster_type1_plan(int dim, const int64_t* n_modes, const int64_t* n_axi
 int efgp_hermitian_normal_rows(int device, uint64_t seed, int64_t index_offset, int nrows, int64_t nmodes, double a, const void* ws,
                                const void* fz, double b, void* out, void* stream);
 
+/* The value and the first partial derivatives of a finite trigonometric sum as coefficient rows (EFGPND.predict_gradient): for
+ * f(x) = Re sum_k s_k f_k exp(2 pi i sum_a h_a k_a x_a) the partial along axis a multiplies mode k by 2 pi i h_a k_a, so
+ *     out[b, 0, k]     = s_k f[b, k],
+ *     out[b, 1 + a, k] = (2 pi h_a k_a) i (s_k f[b, k]),     a = 0 .. dim - 1,
+ * are 1 + dim rows for any type-2 transform (efgp_nufft_type2 pairs real-only rows two per complex fine grid; efgp_raster_type2).
+ * n_modes, h: dim HOST values; f: (nrows, M) complex, M = prod n_modes, last axis fastest; mode_scale: (M) complex or NULL (s = 1);
+ * out: (nrows, 1 + dim, M) complex.  k_a is the mode number of slot k on axis a, -(n / 2) .. (n - 1) / 2, in that order for
+ * modeord = 0 and in FFT order (0 .. (n - 1) / 2, then -(n / 2) .. -1) for modeord = 1; an even axis applies the formula to
+ * k = -n / 2 as it stands.  s_k f is formed once per entry; a slot with k_a = 0 holds +0.0 + 0.0i.  dim 1..3, nrows >= 0 (0: nothing
+ * is launched); f, mode_scale and out 16-byte aligned.  One launch for any nrows (rows and mode blocks are strided inside the kernel
+ * over a bounded grid); no atomics: two calls agree bit for bit. */
+int efgp_mode_jet_rows(int device, int dim, const int64_t* n_modes, const double* h, const void* f, const void* mode_scale, int64_t nrows,
+                       int modeord, void* out, void* stream);
+
 /* Tensor-product barycentric interpolation from a node box to npts points (the Chebyshev predictive variance of the PG
  * estimators, pg_classifier.py:894-942, 1000-1003).  Per point x and axis a, with nodes x_k and weights c_k of that axis:
  *     |x_a - x_k| <= 1e-14 for some k: w_a is one-hot at the first such k (ascending node order);
