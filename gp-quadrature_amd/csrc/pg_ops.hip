@@ -28,8 +28,14 @@ __device__ __forceinline__ T pg_wave_sum(T v) {
     return v;
 }
 
+// A NaN stays a NaN, as in torch's clamp_min / clamp(min=) / max(), which the reference uses (fmax would return the other
+// operand): a non-finite solve shows in delta, in the residual and in the metric instead of passing for a converged one.
+__device__ __forceinline__ double pg_clamp_min(double x, double lo) { return x < lo ? lo : x; }
+
+__device__ __forceinline__ double pg_max_nan(double a, double b) { return (b > a || b != b) ? b : a; }
+
 __device__ __forceinline__ double pg_wave_max(double v) {
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
+    for (int off = 32; off > 0; off >>= 1) v = pg_max_nan(v, __shfl_down(v, off, 64));
     return v;
 }
 
@@ -42,7 +48,7 @@ struct PgBernoulli {
     __device__ double shape(int64_t n, double) const { return pg_b ? pg_b[n] : 1.0; }
     // hit of the logistic-Gaussian approximation (:129-138, :173-191)
     __device__ Acc metric(double m, double sd, double y) const {
-        const double den = sqrt(__dadd_rn(1.0, __dmul_rn(M_PI / 8.0, fmax(sd, 0.0))));
+        const double den = sqrt(__dadd_rn(1.0, __dmul_rn(M_PI / 8.0, pg_clamp_min(sd, 0.0))));
         const double p = 1.0 / (1.0 + exp(-__ddiv_rn(m, den)));
         return ((p > 0.5) == (y != 0.0)) ? 1ull : 0ull;
     }
@@ -55,7 +61,7 @@ struct PgNegativeBinomial {
     __device__ double shape(int64_t, double y) const { return __dadd_rn(y, r); }
     // |r exp(mean + max(sigma_diag, 0) / 2) - y|: the absolute error of the predicted mean count (:166-168, :194-201)
     __device__ Acc metric(double m, double sd, double y) const {
-        return fabs(__dsub_rn(__dmul_rn(r, exp(__dadd_rn(m, __dmul_rn(0.5, fmax(sd, 0.0))))), y));
+        return fabs(__dsub_rn(__dmul_rn(r, exp(__dadd_rn(m, __dmul_rn(0.5, pg_clamp_min(sd, 0.0))))), y));
     }
 };
 
@@ -87,16 +93,16 @@ __global__ __launch_bounds__(kPgThreads) void pg_estep_update_kernel(int64_t N, 
         const double yn = y[n];
         const double b = lik.shape(n, yn);
         // c2 = clamp_min(sigma_diag + mean^2, 1e-12); Lambda = E[omega] of PG(b, c)  (:557-559, :252-257)
-        const double c2 = fmax(__dadd_rn(sd, __dmul_rn(m, m)), 1e-12);
+        const double c2 = pg_clamp_min(__dadd_rn(sd, __dmul_rn(m, m)), 1e-12);
         const double c = sqrt(c2);
-        const double sc = fmax(c, 1e-12);
+        const double sc = pg_clamp_min(c, 1e-12);
         const double lam = c > 1e-8 ? __ddiv_rn(__dmul_rn(__dmul_rn(0.5, b), tanh(__dmul_rn(0.5, sc))), sc) : __dmul_rn(0.25, b);
         // damped update and clamp (:561-563)
-        const double dn = fmax(__dadd_rn(__dmul_rn(delta[n], one_m_rho), __dmul_rn(rho, lam)), 0.0);
+        const double dn = pg_clamp_min(__dadd_rn(__dmul_rn(delta[n], one_m_rho), __dmul_rn(rho, lam)), 0.0);
         delta[n] = dn;
         mean_out[n] = m;
         sdiag_out[n] = sd;
-        lmax = fmax(lmax, fabs(__dsub_rn(dn, lam)));
+        lmax = pg_max_nan(lmax, fabs(__dsub_rn(dn, lam)));
         lmet += lik.metric(m, sd, yn);
     }
     lmax = pg_wave_max(lmax);
@@ -110,7 +116,7 @@ __global__ __launch_bounds__(kPgThreads) void pg_estep_update_kernel(int64_t N, 
         double bm = smax[0];
         Acc bc = smet[0];
         for (int w = 1; w < kPgThreads / 64; ++w) {
-            bm = fmax(bm, smax[w]);
+            bm = pg_max_nan(bm, smax[w]);
             bc += smet[w];
         }
         part_max[blockIdx.x] = bm;
@@ -128,7 +134,7 @@ __global__ __launch_bounds__(kPgThreads) void pg_estep_finish_kernel(int nparts,
     double m = 0.0;
     Acc c = 0;
     for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
-        m = fmax(m, part_max[i]);
+        m = pg_max_nan(m, part_max[i]);
         c += part_metric[i];
     }
     m = pg_wave_max(m);
@@ -142,7 +148,7 @@ __global__ __launch_bounds__(kPgThreads) void pg_estep_finish_kernel(int nparts,
         double bm = smax[0];
         Acc bc = smet[0];
         for (int w = 1; w < kPgThreads / 64; ++w) {
-            bm = fmax(bm, smax[w]);
+            bm = pg_max_nan(bm, smax[w]);
             bc += smet[w];
         }
         if (resid_out) resid_out[0] = bm;
@@ -150,9 +156,11 @@ __global__ __launch_bounds__(kPgThreads) void pg_estep_finish_kernel(int nparts,
     }
 }
 
-// digamma(x) for x > 0: the recurrence psi(x) = psi(x + 1) - 1/x up to x >= 10, then the asymptotic series
+// digamma(x) for x > 0, NaN for every other argument (zero, negative, NaN: the estimators refuse such targets, and the
+// recurrence below would not end for x <= -2^53): the recurrence psi(x) = psi(x + 1) - 1/x up to x >= 10, then the asymptotic series
 // psi(x) = ln x - 1/(2x) - sum_{k=1..7} B_2k / (2k x^2k); the first omitted term is 0.443 / x^16 <= 4.5e-17.
 __device__ double pg_digamma(double x) {
+    if (!(x > 0.0)) return __builtin_nan("");
     double acc = 0.0;
     while (x < 10.0) {
         acc -= 1.0 / x;
@@ -184,7 +192,7 @@ __global__ __launch_bounds__(kPgThreads) void pg_nb_total_count_grad_kernel(int6
     double lsum = 0.0;
     for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += (int64_t)gridDim.x * blockDim.x) {
         const double m = mean[n];
-        const double s = sqrt(fmax(sdiag[n], 0.0));
+        const double s = sqrt(pg_clamp_min(sdiag[n], 0.0));
         double e = 0.0;
         for (int q = 0; q < Q; ++q) {
             const double t = -__dadd_rn(m, __dmul_rn(s, sx[q]));

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from _pg_edges import estep_restated as _estep_restated
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,23 +102,6 @@ def test_seeded_fits_are_bit_identical():
         assert np.array_equal(getattr(a, attr), getattr(b, attr)), attr
     assert a.history_ == b.history_
     assert np.array_equal(a.predict_proba(g["X_test"]), b.predict_proba(g["X_test"]))
-
-
-def _estep_restated(S, delta, y, rho, probes, pg_b):
-    """efgp_pg_estep_update in torch, with the probe sum in the kernel's order (sequential over j, no FMA)."""
-    from polyagamma_classification import _pg_omega_expectation, approximate_logistic_gaussian_prob
-    J = probes.shape[0]
-    mean = S[0].clone()
-    acc = torch.zeros_like(mean)
-    for j in range(J):
-        acc = acc + probes[j] * S[j + 1]
-    sd = acc / torch.full_like(acc, J)                   # a true division (torch turns `/ J` into a product with 1/J)
-    c = torch.sqrt((sd + mean.pow(2)).clamp_min(1e-12))
-    lam = _pg_omega_expectation(c, pg_b if pg_b is not None else torch.ones_like(mean))
-    dn = (delta * (1.0 - rho) + rho * lam).clamp(min=0.0)
-    resid = float((dn - lam).abs().max())
-    correct = int((approximate_logistic_gaussian_prob(mean, sd).gt(0.5) == y.bool()).sum())
-    return mean, sd, dn, resid, correct
 
 
 @pytest.mark.parametrize("form", ["probe_pointer", "device_hash"])
