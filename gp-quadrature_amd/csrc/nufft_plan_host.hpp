@@ -87,6 +87,9 @@ struct LevelWanted {
 };
 LevelWanted plan_level(const NufftSite& s, const int64_t* nf, int W);
 
+// chunk length of a level of the point layout (points_layout.hip cuts every band into chunks of at most this many sorted points)
+int chunk_length(int64_t npts, int num_cu);
+
 // ---- one type-1 pass ------------------------------------------------------------------------------------------------------------
 // The mode boxes the caller wants from the transformed grid (G2MRequest without its pointers): part = 0 | 3 | 4 as in G2MArgs,
 // nmb only for part == 4.

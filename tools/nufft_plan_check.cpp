@@ -9,7 +9,7 @@
 //       t2     dim nm0 nm1 nm2              tol N real_only batch normal dense layout span0 span1 span2 num_cu max_lds
 //     (mode counts of the unused axes: 1; t1pair: the two boxes of the fit's pair pass, the window is made for the larger; dense: 1
 //     takes the dense rule's window whatever N; layout: 0 no point layout, 1 | 8 a layout and that band height forced, -1 a layout and
-//     the unforced rule; span: extent of the points per axis in periods)
+//     the unforced rule; span: extent of the points per axis in periods; a pass on the layout also prints the chunk length of its level)
 //   ./nufft_plan_check --sweep     the products listed at sweep() (a second unsanitized, two under the sanitizers)
 //
 // Hooks (EFGP_NO_*, EFGP_CELLSORT, EFGP_DENSE_POINTS, EFGP_G2M_V1 ...) come from the environment, as in the library; only
@@ -161,6 +161,7 @@ static void print_case(const Case& c, const Planned& pl) {
                     (int)p.g2m_two_launch, p.g2m_split, p.g2m_h[0], p.g2m_h[1]);
         print_axes("nc", d, p.nc);
         if (p.spreader == Spreader::tiles || p.spreader == Spreader::cells) print_tile(d, p.tile);
+        if (p.spreader == Spreader::layout) std::printf(" chunk_len=%d", chunk_length(c.N, c.num_cu));      // what points_layout.hip cuts the bands into
     }
     std::printf("\n");
 }
